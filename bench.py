@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched game-step hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--loop auto|pair] [--gather-every K]
+  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--loop auto|pair] [--gather-every K] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: every env is stepped one frame (transition + auto-reset, actions
 generated on the device by the counter-based rule of SURVEY 8d) and one uint8[N,H,W,3] frame batch is rasterised into HBM.
@@ -93,7 +93,9 @@ SEED_BASE = 1234
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps per region of `value` (default 200; --protocol reference: steps per repetition, default 10 000); "
+                         "the BASELINE configs and the strong-scaling probe beside it time their own step counts, printed with them")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each (median reported)")
     ap.add_argument("--preroll", type=int, default=1000, help="untimed step-only frames before the warm-up (mid-game states)")
@@ -148,7 +150,13 @@ def parse():
                     help="agent protocol: 'stack' = the rolled uint8[N,84,84,4] on the device (VecFrameStack's array); 'ring' = one new "
                          "plane per step into a ring of the last 4 (tbx_agent_config_t::new_plane = 2: the reference's data flow)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall-time budget of the CPU arm at the headline batch")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(batch protocol, one game; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 10000 if args.protocol == "reference" else 200
+    return args
 
 
 def usable_cores():
@@ -406,7 +414,7 @@ def bench_reference_protocol(args):
     from toybox_amd import toybox as tbmod
     from toybox_amd.envs import ENV_IDS
     from toybox_amd.toybox import Toybox
-    nsteps = args.steps if args.steps != 200 else 10000      # (200 is this script's batch-protocol default; the harness uses 10 000)
+    nsteps = args.steps
     reps = max(1, args.reps)
     env_id = {"breakout": "BreakoutToyboxNoFrameskip-v4", "amidar": "AmidarToyboxNoFrameskip-v4",
               "space_invaders": "SpaceInvadersToyboxNoFrameskip-v4"}.get(args.game)
@@ -898,6 +906,54 @@ def verify_gather(eng, hip, rank, world, n_local, shard_sizes, start):
     return True
 
 
+DUMP_BYTES = 48 << 20          # --dump-outputs: the most the files of ALL ranks take together (the limit is 64 MB)
+DUMP_SAMPLE_SEED = 0
+DUMP_PER_ENV = ("reward", "done", "lives", "score")
+
+
+def dump_budget(n, frame_bytes, world):
+    """frames of this rank's sample under --dump-outputs: its 1/world share of DUMP_BYTES after its per-env arrays (float64) and
+    the two small ones; None when not even one frame fits (a batch too large for the dump)"""
+    room = DUMP_BYTES // world - 8 * n * (len(DUMP_PER_ENV) + 1) - 1024
+    k = min(n, room // (4 * frame_bytes)) if frame_bytes else n
+    return int(k) if k >= 1 else None
+
+
+def dump_outputs(eng, hip, directory, start, channels, render, world, frame_after_step, prefix=""):
+    """What the last timed step handed its caller, as DIR/<prefix><name>.npy: the step outputs of every env of this rank (reward,
+    done, lives, score; float64, exact for their int32 / uint8 values) and the frame the step's call rasterised (TBX_BUF_FRAME) for
+    a fixed seeded sample of envs (float32; env_index holds their global indices), all ranks together within DUMP_BYTES.  The
+    frame shows the state before the step in the fused and chunk forms and after it in the pair form: frame_after_step.npy says
+    which (1 or 0), so that two builds whose loops resolved to different forms are not compared frame for frame.  The inputs depend
+    on the arguments only, so two builds run with the same arguments can be compared array for array."""
+    from toybox_amd import _abi
+    n, frame_bytes = eng.n_envs, eng.height * eng.width * channels
+    ids = {"reward": _abi.BUF_REWARD, "done": _abi.BUF_DONE, "lives": _abi.BUF_LIVES, "score": _abi.BUF_SCORE}
+    if render:
+        ids["frame"] = _abi.BUF_FRAME
+    ptrs = {name: eng.device_buffer(which) for name, which in ids.items()}      # (asking joins the caller's stream)
+    hip.synchronize()
+    out = {}
+    for name, dtype in (("reward", np.int32), ("done", np.uint8), ("lives", np.int32), ("score", np.int32)):
+        a = np.empty(n, dtype)
+        assert ptrs[name][1] >= a.nbytes, name
+        hip.memcpy_dtoh(a, ptrs[name][0], a.nbytes)
+        out[name] = a.astype(np.float64)
+    if render:
+        k = dump_budget(n, frame_bytes, world)
+        assert ptrs["frame"][1] >= n * frame_bytes
+        local = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED + start).choice(n, size=k, replace=False))
+        frames = np.empty((k, eng.height, eng.width, channels), np.uint8)
+        for j, i in enumerate(local):
+            hip.memcpy_dtoh(frames[j], ptrs["frame"][0] + int(i) * frame_bytes, frame_bytes)
+        out["frame"] = frames.astype(np.float32)
+        out["env_index"] = (start + local).astype(np.float64)
+        out["frame_after_step"] = np.array([1.0 if frame_after_step else 0.0])
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, prefix + name + ".npy"), a)
+
+
 def run_reading(args, hip, game, rank, world, local_rank, scaling, tag, with_extras, extras=("serialised", "step_only")):
     """One reading of the metric on this rank: engine for its shard, communicator (N > 1 or --with-gather) with one verified
     exchange, pre-roll, the timed arm (fused where the engine fuses, unless --loop pair), and with_extras the serialised
@@ -925,6 +981,11 @@ def run_reading(args, hip, game, rank, world, local_rank, scaling, tag, with_ext
     ranks = FileWorld(rank, world, key=rendezvous_key() + "_ident_" + tag).allgather(ident) if world > 1 else [ident]
     H, W, C = eng.height, eng.width, args.channels
     render = not args.no_render
+    dumping = tag == "main" and bool(getattr(args, "dump_outputs", None))
+    if dumping and dump_budget(n, H * W * C if render else 0, world) is None:
+        print("bench.py: --dump-outputs: %d envs per rank do not fit the %d-byte dump" % (n, DUMP_BYTES), file=sys.stderr)
+        eng.close()
+        return 2
     gather = world > 1 or args.with_gather
     gather_note, rccl, fw = None, None, None
     if gather:
@@ -986,6 +1047,9 @@ def run_reading(args, hip, game, rank, world, local_rank, scaling, tag, with_ext
     fused = render and args.loop != "pair" and C >= 3 and eng.get_option(_abi.OPT_RENDER_STEP_FUSED) == 1
     rep, launch, mode, t = timed_arm(eng, hip, reg, stream, start, C, gather, render, args.pipeline, t, K, Wm, R, fused=fused,
                                      rollout=render and args.loop != "pair")
+    if dumping:
+        dump_outputs(eng, hip, args.dump_outputs, start, C, render, world, not (fused or LAST_LOOP_FORM["chunk_k"]),
+                     prefix="rank%d_" % rank if world > 1 else "")
     res = {"n": n, "n_total": n_total, "start": start, "H": H, "W": W, "C": C, "render": render, "gather": gather, "rccl": rccl,
            "gather_note": gather_note, "rep": rep, "launch": launch, "mode": mode, "fused": fused, "steps": K, "extras": {},
            "overlapped": LAST_LOOP_FORM["overlapped"], "chunk_k": LAST_LOOP_FORM["chunk_k"], "ranks": ranks}
@@ -1033,6 +1097,9 @@ def main():
     FUSED_OVERLAP = args.fused_overlap
     ROLLOUT_CHUNKS = args.rollout_chunks
     CHUNK_K = max(1, args.gather_every)
+    if args.dump_outputs and (args.protocol != "batch" or args.game == "mixed" or args.dry_run):
+        print("bench.py: --dump-outputs covers the batch protocol of one game only", file=sys.stderr)
+        return 2
     if args.protocol == "reference":
         return bench_reference_protocol(args)
     if args.protocol == "agent":

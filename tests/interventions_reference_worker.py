@@ -1,30 +1,37 @@
-"""Run by tests/test_batched_interventions.py in a subprocess, build container only (PYTHONPATH = tests/shim, the repo, the
-reference tree).  The reference's OWN intervention classes -- toybox.interventions.{breakout,amidar,space_invaders}, imported
-unmodified, over the `ctoybox` shim and one-env oracle engines -- are the yardstick for the batched helpers of
-toybox_amd.interventions.BatchIntervention: every env's state of a played batch is written into a reference Toybox, the
-reference's helper is called on it, and its answer (or the state it leaves behind) must equal what the batched form produced
-for that env.  Builder-authored; contains no reference code."""
+"""The batched helpers of toybox_amd.interventions.BatchIntervention against the reference's OWN intervention classes.
+
+batched(lib) plays three small batches and records, env by env, what the batched forms answer and the states their edits leave.
+tests/test_batched_interventions.py compares that record with tests/golden/interventions_reference.json.gz.
+
+The stored record comes from running this file as a script with the reference tree and tests/shim on PYTHONPATH:
+    PYTHONPATH=tests/shim:.:tests:<reference tree> PYTHONDONTWRITEBYTECODE=1 python tests/interventions_reference_worker.py [--write]
+Every env's state is then written into a reference Toybox, the reference's classes -- toybox.interventions.{breakout,amidar,
+space_invaders}, imported unmodified, over the `ctoybox` shim and one-env oracle engines -- are asked the same questions and
+made to do the same edits, and their answers and the states they leave must equal the record; --write then stores it.
+Builder-authored; contains no reference code."""
+import gzip
 import json
+import os
+import sys
 
 import numpy as np
 
-import ctoybox
-from ctoybox import Toybox
 from support import splitmix64, synthetic_actions
-from toybox.interventions import amidar as ref_ami
-from toybox.interventions.amidar import AmidarIntervention
-from toybox.interventions.breakout import BreakoutIntervention
-from toybox.interventions.core import Direction
-from toybox.interventions.space_invaders import SpaceInvadersIntervention
 from toybox_amd import Engine
 from toybox_amd.games import codec
 from toybox_amd.interventions import BatchIntervention
 
-LIB = ctoybox._lib
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "interventions_reference.json.gz")
+
+# find_brick (:400-404): predicates over the static attributes, evaluated once on the host, + the per-env alive flag
+BREAKOUT_PREDS = {"row2_right": lambda b: b.row == 2 and b.col >= 5, "cheap": lambda b: b.points == 1, "red": lambda b: b.color.r > 150,
+                  "none": lambda b: b.row > 99}
+AMIDAR_PROBE = [(0, 0), (5, 6), (31, 15), (12, 12), (1, 1)]
+AMIDAR_TAGS = ["Empty", "Unpainted", "Painted", "ChaseMarker"]
 
 
-def played(game, n, frames, seed):
-    e = Engine(game, n, lib=LIB)
+def played(game, n, frames, seed, lib):
+    e = Engine(game, n, lib=lib)
     e.seed(seed)
     e.new_game()
     for t in range(frames):
@@ -40,9 +47,25 @@ def same_json(a, b, what):
     assert json.dumps(a, sort_keys=True) == json.dumps(b, sort_keys=True), what
 
 
-def breakout():
+def plain(x):
+    """the record as JSON values (numpy arrays and scalars as lists and numbers, tuple keys as strings)"""
+    if isinstance(x, dict):
+        return {str(k): plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [plain(v) for v in x]
+    if isinstance(x, np.ndarray):
+        return plain(x.tolist())
+    if isinstance(x, np.generic):
+        return x.item()
+    return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the batched side
+
+def breakout_batched(lib):
     n = 10
-    e = played("breakout", n, 300, 5)
+    e = played("breakout", n, 300, 5, lib)
     rng = np.random.default_rng(2)
     with BatchIntervention(e) as bi:                         # a few channels first, so that the counts are not all zero
         bi.add_channel(rng.integers(0, 18, n))
@@ -53,16 +76,93 @@ def breakout():
         q = dict(remaining=bi.num_bricks_remaining(), bricks=bi.num_bricks(), rows=bi.num_rows(), columns=bi.num_columns(),
                  count=bi.channel_count(), find=bi.find_channel(), col=bi.get_column(cols), is_chan=bi.is_channel(cols),
                  ppos=bi.get_paddle_position(), pvel=bi.get_paddle_velocity(), bpos=bi.get_ball_position(), bvel=bi.get_ball_velocity())
-        # find_brick (:400-404): predicates over the static attributes, evaluated once on the host, + the per-env alive flag
-        preds = {"row2_right": lambda b: b.row == 2 and b.col >= 5, "cheap": lambda b: b.points == 1, "red": lambda b: b.color.r > 150,
-                 "none": lambda b: b.row > 99}
-        q["find_alive"] = {k: bi.find_brick(p, alive=True) for k, p in preds.items()}
-        q["find_dead"] = {k: bi.find_brick(p, alive=False) for k, p in preds.items()}
-        q["find_any"] = {k: bi.find_brick(p) for k, p in preds.items()}
+        q["find_alive"] = {k: bi.find_brick(p, alive=True) for k, p in BREAKOUT_PREDS.items()}
+        q["find_dead"] = {k: bi.find_brick(p, alive=False) for k, p in BREAKOUT_PREDS.items()}
+        q["find_any"] = {k: bi.find_brick(p) for k, p in BREAKOUT_PREDS.items()}
         q["find_mask"] = bi.find_brick(np.arange(108) % 7 == 3, alive=True)
         bi.add_channel(cols)
         bi.fill_column((cols + 1) % 18)
         bi.clear_board(envs=np.arange(n) == 4)
+    after = [env_json(e, i) for i in range(n)]
+    e.close()
+    return {"n": n, "before": before, "cols": cols, "q": q, "after": after}
+
+
+def amidar_batched(lib):
+    n = 8
+    e = played("amidar", n, 500, 9, lib)
+    with BatchIntervention(e) as bi:
+        bi.set_mode("chase", set_time=40, envs=[1, 2])       # so that modes differ over the batch
+        bi.set_mode("jump", envs=[2, 3])
+    before = [env_json(e, i) for i in range(n)]
+    probe = AMIDAR_PROBE
+    with BatchIntervention(e) as bi:
+        q = dict(regular=bi.get_regular_mode(), jump=bi.get_jump_mode(), chase=bi.get_chase_mode(), caught=bi.any_enemy_caught(),
+                 tile={p: bi.get_tile_by_pos(*p) for p in probe}, walk={p: bi.is_tile_walkable(*p) for p in probe},
+                 count={t: bi.count_tiles(t) for t in AMIDAR_TAGS}, dist={p: bi.enemy_distances_from_tile(*p) for p in probe},
+                 ptile=bi.player_tile(), pdist=bi.player_enemy_distances(), painted=bi.player_on_painted(),
+                 near={r: bi.player_near_unpainted(r) for r in (2, 5)})
+        # the mask / counter-RNG forms of the predicate- and `random`-driven helpers (VERDICT r04 #6)
+        walk_pred = lambda tag: tag != "Empty"
+        q["filter"] = {"walk": bi.filter_tiles(walk_pred), "painted": bi.filter_tiles("Painted"), "all": bi.filter_tiles()}
+        q["fcount"] = bi.count_filtered_tiles(["Painted", "ChaseMarker"])
+        q["rtile"] = {k: bi.get_random_tile(walk_pred, seed=77, draw=k, env_offset=1000) for k in range(3)}
+        q["rtile_far"] = bi.get_random_tile(seed=5, draw=1, min_enemy_distance=9)
+        q["rtrack"] = bi.get_random_track_position(seed=77, draw=0, env_offset=1000)
+        q["rdir"] = {p: bi.get_random_dir_for_tile(*p, seed=3, draw=2) for p in probe}
+        bi.set_mode("regular", envs=[1])
+        bi.set_mode("jump", set_time=33, envs=[0, 5])
+        bi.set_mode("chase", envs=[6])
+        bi.set_tile_tag(5, 6, "Painted")
+        bi.set_tile_tag(1, 1, "Unpainted", envs=[7])
+        bi.set_enemy_protocol(4, "EnemyPerimeterAI", start={"tx": 0, "ty": 0})
+        bi.set_enemy_protocol(3, "EnemyAmidarMvmt", vert="Down", horiz="Left", start_vert="Up", start_horiz="Right", start={"tx": 6, "ty": 0}, envs=[0, 1, 2])
+        bi.set_enemy_protocol(2, "EnemyTargetPlayer", start={"tx": 0, "ty": 30}, vision_distance=10, player_seen=None, start_dir="Right", dir="Up", envs=[3])
+        bi.set_enemy_protocol(1, "EnemyRandomMvmt", start={"tx": 31, "ty": 30}, start_dir="Up", dir="Left", envs=[4])
+        bi.set_enemy_protocol(0, "EnemyLookupAI", next=3, default_route_index=10, envs=[5])
+    after = [env_json(e, i) for i in range(n)]
+    # set_player_random_start (:541-548): the batched edit, with the tile the counter rule chooses for each env
+    with BatchIntervention(e) as bi:
+        chosen = bi.get_random_tile(seed=11, draw=4, env_offset=50, min_enemy_distance=5)
+        bi.set_player_random_start(5, seed=11, draw=4, env_offset=50, envs=np.arange(n) != 2)
+    after_start = [env_json(e, i) for i in range(n)]
+    e.close()
+    return {"n": n, "before": before, "q": q, "after": after, "chosen": chosen, "after_start": after_start}
+
+
+def space_invaders_batched(lib):
+    n = 6
+    e = played("space_invaders", n, 250, 4, lib)
+    before = [env_json(e, i) for i in range(n)]
+    with BatchIntervention(e) as bi:
+        q = dict(ship=bi.get_player(), jitter=bi.get_jitter())
+        bi.remove_mothership(envs=[0, 3])
+        bi.set_lives(1, envs=[5])
+    after = [env_json(e, i) for i in range(n)]
+    # set_jitter: a config intervention (new game on exit)
+    with BatchIntervention(e) as bi:
+        bi.set_jitter(0.125)
+    q["jitter_config"] = codec("space_invaders").config_to_json(e.get_config())["jitter"]
+    e.close()
+    return {"n": n, "before": before, "q": q, "after": after}
+
+
+def batched(lib):
+    return {"breakout": breakout_batched(lib), "amidar": amidar_batched(lib), "space_invaders": space_invaders_batched(lib)}
+
+
+def record(b):
+    """what the golden file holds: the answers and the states the edits leave (the played states are their inputs)"""
+    return plain({game: {k: v for k, v in r.items() if k not in ("n", "before", "cols")} for game, r in b.items()})
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the reference side (script only)
+
+def breakout_reference(r):
+    from ctoybox import Toybox
+    from toybox.interventions.breakout import BreakoutIntervention
+    n, before, cols, q = r["n"], r["before"], r["cols"], r["q"]
 
     def ref_find(iv, pred):
         try:
@@ -73,7 +173,7 @@ def breakout():
         tb = Toybox("breakout")
         tb.write_state_json(before[i])
         with BreakoutIntervention(tb) as iv:
-            for k, p in preds.items():
+            for k, p in BREAKOUT_PREDS.items():
                 assert ref_find(iv, lambda b, p=p: p(b) and b.alive) == q["find_alive"][k][i], (i, k)
                 assert ref_find(iv, lambda b, p=p: p(b) and not b.alive) == q["find_dead"][k][i], (i, k)
                 assert ref_find(iv, p) == q["find_any"][k][i], (i, k)
@@ -96,44 +196,17 @@ def breakout():
             iv.fill_column(int((cols[i] + 1) % 18))
             if i == 4:
                 iv.clear_board()
-        same_json(tb.to_state_json(), env_json(e, i), "breakout env %d after the edits" % i)
+        same_json(tb.to_state_json(), r["after"][i], "breakout env %d after the edits" % i)
         tb.close() if hasattr(tb, "close") else None
     print("breakout ok")
 
 
-def amidar():
-    n = 8
-    e = played("amidar", n, 500, 9)
-    with BatchIntervention(e) as bi:
-        bi.set_mode("chase", set_time=40, envs=[1, 2])       # so that modes differ over the batch
-        bi.set_mode("jump", envs=[2, 3])
-    before = [env_json(e, i) for i in range(n)]
-    probe = [(0, 0), (5, 6), (31, 15), (12, 12), (1, 1)]
-    tags = ["Empty", "Unpainted", "Painted", "ChaseMarker"]
-    with BatchIntervention(e) as bi:
-        q = dict(regular=bi.get_regular_mode(), jump=bi.get_jump_mode(), chase=bi.get_chase_mode(), caught=bi.any_enemy_caught(),
-                 tile={p: bi.get_tile_by_pos(*p) for p in probe}, walk={p: bi.is_tile_walkable(*p) for p in probe},
-                 count={t: bi.count_tiles(t) for t in tags}, dist={p: bi.enemy_distances_from_tile(*p) for p in probe},
-                 ptile=bi.player_tile(), pdist=bi.player_enemy_distances(), painted=bi.player_on_painted(),
-                 near={r: bi.player_near_unpainted(r) for r in (2, 5)})
-        # the mask / counter-RNG forms of the predicate- and `random`-driven helpers (VERDICT r04 #6)
-        walk_pred = lambda tag: tag != "Empty"
-        q["filter"] = {"walk": bi.filter_tiles(walk_pred), "painted": bi.filter_tiles("Painted"), "all": bi.filter_tiles()}
-        q["fcount"] = bi.count_filtered_tiles(["Painted", "ChaseMarker"])
-        q["rtile"] = {k: bi.get_random_tile(walk_pred, seed=77, draw=k, env_offset=1000) for k in range(3)}
-        q["rtile_far"] = bi.get_random_tile(seed=5, draw=1, min_enemy_distance=9)
-        q["rtrack"] = bi.get_random_track_position(seed=77, draw=0, env_offset=1000)
-        q["rdir"] = {p: bi.get_random_dir_for_tile(*p, seed=3, draw=2) for p in probe}
-        bi.set_mode("regular", envs=[1])
-        bi.set_mode("jump", set_time=33, envs=[0, 5])
-        bi.set_mode("chase", envs=[6])
-        bi.set_tile_tag(5, 6, "Painted")
-        bi.set_tile_tag(1, 1, "Unpainted", envs=[7])
-        bi.set_enemy_protocol(4, "EnemyPerimeterAI", start={"tx": 0, "ty": 0})
-        bi.set_enemy_protocol(3, "EnemyAmidarMvmt", vert="Down", horiz="Left", start_vert="Up", start_horiz="Right", start={"tx": 6, "ty": 0}, envs=[0, 1, 2])
-        bi.set_enemy_protocol(2, "EnemyTargetPlayer", start={"tx": 0, "ty": 30}, vision_distance=10, player_seen=None, start_dir="Right", dir="Up", envs=[3])
-        bi.set_enemy_protocol(1, "EnemyRandomMvmt", start={"tx": 31, "ty": 30}, start_dir="Up", dir="Left", envs=[4])
-        bi.set_enemy_protocol(0, "EnemyLookupAI", next=3, default_route_index=10, envs=[5])
+def amidar_reference(r):
+    from ctoybox import Toybox
+    from toybox.interventions import amidar as ref_ami
+    from toybox.interventions.amidar import AmidarIntervention
+    from toybox.interventions.core import Direction
+    n, before, q, probe = r["n"], r["before"], r["q"], AMIDAR_PROBE
     for i in range(n):
         tb = Toybox("amidar")
         tb.write_state_json(before[i])
@@ -144,14 +217,14 @@ def amidar():
                 t = iv.get_tile_by_pos(*p)
                 assert t.tag == q["tile"][p][i] and iv.is_tile_walkable(t) == bool(q["walk"][p][i])
                 assert iv.enemy_distances_from_tile(t) == [d for d in q["dist"][p][i] if d >= 0], (i, p)
-            for t in tags:
+            for t in AMIDAR_TAGS:
                 assert len(iv.filter_tiles(lambda x, t=t: x.tag == t)) == q["count"][t][i]
             ptp = iv.worldpoint_to_tilepoint(iv.game.player.position)
             assert (ptp.tx, ptp.ty) == (q["ptile"][0][i], q["ptile"][1][i]) and iv.player_tile().tag == q["ptile"][2][i]
             assert iv.player_enemy_distances() == [d for d in q["pdist"][i] if d >= 0]
             assert iv.player_on_painted() == bool(q["painted"][i])
-            for r in (2, 5):
-                assert iv.player_near_unpainted(r) == bool(q["near"][r][i]), (i, r)
+            for rr in (2, 5):
+                assert iv.player_near_unpainted(rr) == bool(q["near"][rr][i]), (i, rr)
             # filter_tiles(pred) in the reference's order; the drawn tile is element (r mod len) of that list
             def where(tiles):
                 return [(iv.tile_to_tilepoint(t).tx, iv.tile_to_tilepoint(t).ty) for t in tiles]
@@ -162,8 +235,8 @@ def amidar():
             assert len(iv.filter_tiles(lambda t: t.tag in ("Painted", "ChaseMarker"))) == q["fcount"][i]
             for k in range(3):
                 tx, ty, tag, cnt = (v[i] for v in q["rtile"][k])
-                r = int(splitmix64(77 ^ ((1000 + i) << 32) ^ k))
-                assert cnt == len(walk) and (tx, ty) == walk[r % len(walk)] and tag == iv.get_tile_by_pos(tx, ty).tag
+                rv = int(splitmix64(77 ^ ((1000 + i) << 32) ^ k))
+                assert cnt == len(walk) and (tx, ty) == walk[rv % len(walk)] and tag == iv.get_tile_by_pos(tx, ty).tag
                 # the reference's own get_random_tile, its two randint draws scripted to land on that tile: accepted at once
                 draws = iter([int(ty), int(tx)])
                 ref_ami.random.randint = lambda a, b: next(draws)
@@ -211,38 +284,31 @@ def amidar():
                 iv.set_enemy_protocol(en[1], "EnemyRandomMvmt", start=TP(31, 30), start_dir=D("Up"), dir=D("Left"))
             if i == 5:
                 iv.set_enemy_protocol(en[0], "EnemyLookupAI", next=3, default_route_index=10)
-        got, want = tb.to_state_json(), env_json(e, i)
-        got["board"]["junctions"], want["board"]["junctions"] = sorted(got["board"]["junctions"]), sorted(want["board"]["junctions"])
+        got, want = tb.to_state_json(), dict(r["after"][i])
+        got["board"]["junctions"], want["board"] = sorted(got["board"]["junctions"]), dict(want["board"], junctions=sorted(want["board"]["junctions"]))
         same_json(got, want, "amidar env %d after the edits" % i)
-    # set_player_random_start (:541-548): the batched edit, then the reference's method with its draws scripted to the tile the
-    # counter rule chose for that env -- the reference must accept it at once and leave the same state
-    before = [env_json(e, i) for i in range(n)]
-    with BatchIntervention(e) as bi:
-        chosen = bi.get_random_tile(seed=11, draw=4, env_offset=50, min_enemy_distance=5)
-        bi.set_player_random_start(5, seed=11, draw=4, env_offset=50, envs=np.arange(n) != 2)
+    # set_player_random_start (:541-548): the reference's method with its draws scripted to the tile the counter rule chose for
+    # that env -- the reference must accept it at once and leave the same state as the batched edit
+    chosen = r["chosen"]
     for i in range(n):
         tb = Toybox("amidar")
-        tb.write_state_json(before[i])
+        tb.write_state_json(r["after"][i])
         if i != 2:
             with AmidarIntervention(tb) as iv:
                 draws = iter([int(chosen[1][i]), int(chosen[0][i])])
                 ref_ami.random.randint = lambda a, b: next(draws)
                 iv.set_player_random_start(5)
-        got, want = tb.to_state_json(), env_json(e, i)
-        got["board"]["junctions"], want["board"]["junctions"] = sorted(got["board"]["junctions"]), sorted(want["board"]["junctions"])
+        got, want = tb.to_state_json(), dict(r["after_start"][i])
+        got["board"]["junctions"], want["board"] = sorted(got["board"]["junctions"]), dict(want["board"], junctions=sorted(want["board"]["junctions"]))
         same_json(got, want, "amidar env %d after set_player_random_start" % i)
     print("amidar ok")
 
 
-def space_invaders():
-    n = 6
-    e = played("space_invaders", n, 250, 4)
-    before = [env_json(e, i) for i in range(n)]
-    with BatchIntervention(e) as bi:
-        ship = bi.get_player()
-        assert bi.get_jitter() == 0.5
-        bi.remove_mothership(envs=[0, 3])
-        bi.set_lives(1, envs=[5])
+def space_invaders_reference(r):
+    from ctoybox import Toybox
+    from toybox.interventions.space_invaders import SpaceInvadersIntervention
+    n, before, ship = r["n"], r["before"], r["q"]["ship"]
+    assert r["q"]["jitter"] == 0.5
     for i in range(n):
         tb = Toybox("space_invaders")
         tb.write_state_json(before[i])
@@ -250,24 +316,27 @@ def space_invaders():
             s = iv.get_player()
             assert (s.x, s.y, s.w, s.h, s.speed, bool(s.alive)) == (ship["x"][i], ship["y"][i], ship["w"][i], ship["h"][i], ship["speed"][i], bool(ship["alive"][i]))
             assert (-1 if s.death_counter is None else s.death_counter) == ship["death_counter"][i]
-            assert iv.get_jitter() == 0.5
+            assert iv.get_jitter() == r["q"]["jitter"]
             if i in (0, 3):
                 iv.remove_mothership(None)
             if i == 5:
                 iv.game.lives = 1
-        same_json(tb.to_state_json(), env_json(e, i), "space_invaders env %d after the edits" % i)
-    # set_jitter: a config intervention on both sides (new game on exit)
-    with BatchIntervention(e) as bi:
-        bi.set_jitter(0.125)
+        same_json(tb.to_state_json(), r["after"][i], "space_invaders env %d after the edits" % i)
     tb = Toybox("space_invaders")
     with SpaceInvadersIntervention(tb) as iv:
         iv.set_jitter(0.125)
-    assert tb.config_to_json()["jitter"] == 0.125 == codec("space_invaders").config_to_json(e.get_config())["jitter"]
+    assert tb.config_to_json()["jitter"] == 0.125 == r["q"]["jitter_config"]
     print("space_invaders ok")
 
 
 if __name__ == "__main__":
-    breakout()
-    amidar()
-    space_invaders()
+    import ctoybox
+    b = batched(ctoybox._lib)
+    breakout_reference(b["breakout"])
+    amidar_reference(b["amidar"])
+    space_invaders_reference(b["space_invaders"])
+    if "--write" in sys.argv[1:]:
+        with gzip.GzipFile(GOLDEN, "wb", mtime=0) as f:
+            f.write(json.dumps(record(b), sort_keys=True).encode())
+        print("wrote", GOLDEN)
     print("WORKER_OK")

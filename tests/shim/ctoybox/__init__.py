@@ -1,7 +1,7 @@
 """`ctoybox`-named shim used ONLY by the test-suite in the build container: it lets the UNMODIFIED reference
 code (/root/reference/toybox/interventions, /root/reference/test/interventions) import `ctoybox` and run
 against this repo's host layer.  Engines are backed by the CPU oracle here because the container has no GPU
-(tests/test_reference_suite.py); the same host code is exercised over the HIP library by the GPU tests."""
+(tests/golden/run_reference_suite.py, tests/interventions_reference_worker.py); the same host code is exercised over the HIP library by the GPU tests."""
 import ctypes
 import os
 

@@ -35,6 +35,22 @@ def test_batched_get_set_equals_single(game, lib):
         assert bytes(e.get_state(k)) == bytes(rec[k + 1].tobytes())
 
 
+def test_space_invaders_lives_edit_marks_the_state_dirty(lib):
+    """the SpaceInvaders self-test of the reference (interventions/space_invaders.py, run as a module): setting lives = 1 marks the
+    state dirty, and leaving the intervention writes it back"""
+    n = 4
+    e = Engine("space_invaders", n, lib=lib)
+    e.seed(3)
+    e.new_game()
+    with BatchIntervention(e) as bi:
+        assert not bi.dirty_state
+        bi.states["lives"][2] = 1
+        assert bi.dirty_state
+    with BatchIntervention(e) as bi:
+        assert not bi.dirty_state and bi.states["lives"][2] == 1 and (bi.states["lives"][[0, 1, 3]] > 1).all()
+    e.close()
+
+
 def test_breakout_channel_sweep(lib, oracle_lib):
     """add_channel in 64 envs with one vectorised write (the reference does this one env and one JSON round-trip at a
     time, test_breakout_interventions.py:60-76), then play on both engines."""
@@ -169,8 +185,8 @@ def test_seed_array_equals_per_env_seed(lib):
 # The reference's helper methods (interventions/breakout.py:303-429, amidar.py:360-615, space_invaders.py:165-176) as
 # device-side kernels (tbx_edit / tbx_reduce).  Three checks: (1) every query against a second formulation -- numpy over the
 # POD records -- on whichever library runs; (2) HIP against the oracle after a sequence of edits, states and rollout;
-# (3) (build container only) the oracle's batched forms against the reference's OWN single-env classes driven through the
-# ctoybox shim, tests/interventions_reference_worker.py.
+# (3) the oracle's batched forms against what the reference's OWN single-env classes answered, driven through the ctoybox shim
+# and recorded by tests/interventions_reference_worker.py.
 
 def _played(game, n, lib, frames=260, seed=17):
     e = Engine(game, n, lib=lib)
@@ -471,21 +487,21 @@ def test_device_pointer_forms_of_edit_and_reduce(oracle_lib):
 
 
 def test_batched_helpers_equal_the_references_own_classes(oracle_lib):
-    """Build container only: tests/interventions_reference_worker.py imports the reference's UNMODIFIED
-    toybox.interventions.{breakout,amidar,space_invaders} (over the ctoybox shim, one-env oracle engines), replays each env's
-    state into it, calls the reference's helper and compares with what the batched form answered for that env."""
-    import os
-    import subprocess
-    import sys
-    from conftest import ROOT
-    ref = os.environ.get("TOYBOX_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(ref, "toybox", "interventions")):
-        pytest.skip("the reference tree is only present in the build container")
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "tests", "shim"), ROOT, os.path.join(ROOT, "tests"), ref]),
-               PYTHONDONTWRITEBYTECODE="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "interventions_reference_worker.py")], cwd="/tmp", env=env,
-                       capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0 and "WORKER_OK" in p.stdout, (p.stdout + p.stderr)[-4000:]
+    """What the reference's UNMODIFIED toybox.interventions.{breakout,amidar,space_invaders} classes answered for every env of three
+    played batches, and the states their edits left, as tests/interventions_reference_worker.py recorded them (it asserts the batched
+    record against those classes before it writes tests/golden/interventions_reference.json.gz): the batched helpers still answer
+    and leave exactly that."""
+    import gzip
+    import json
+    import interventions_reference_worker as worker
+    with gzip.open(worker.GOLDEN, "rt") as f:
+        want = json.load(f)
+    got = json.loads(json.dumps(worker.record(worker.batched(oracle_lib)), sort_keys=True))
+    assert sorted(got) == sorted(want)
+    for game in want:
+        assert sorted(got[game]) == sorted(want[game]), game
+        for key in want[game]:
+            assert got[game][key] == want[game][key], (game, key)
 
 
 def test_counter_rule_arguments_are_folded_or_refused(lib):

@@ -386,6 +386,115 @@ def test_bench_n_process_flow_end_to_end_on_the_checker(world, extra, oracle_lib
     assert rf["avg_launch_ms"] > 0 and rf["launches_timed"] >= 1 and "never" in rf["timing"]
 
 
+def _last_step_of_an_engine_alone(lib, n, frames_played, frame_after_step, verified_steps=0):
+    """what bench.py's timed path hands its caller after `frames_played` steps of n Breakout envs (seeds 1234 + env, the
+    counter-based actions of seed 1337), from an engine stepped on its own: the frame of the state before or after the last step,
+    and the last step's outputs.  verified_steps: the steps of the verified exchange in front of a run with a gather (a new game
+    follows them; the envs' random streams go on from where those steps left them)."""
+    from support import read_buffer
+    from toybox_amd import Engine, _abi
+    e = Engine("breakout", n, lib=lib)
+    e.seed(1234)
+    e.new_game()
+    for t in range(verified_steps):
+        e.step_synthetic(1337, t, auto_reset=True)
+    if verified_steps:
+        e.new_game()
+    for t in range(frames_played - 1):
+        e.step_synthetic(1337, t, auto_reset=True)
+    frame = None if frame_after_step else e.render(3)
+    e.step_synthetic(1337, frames_played - 1, auto_reset=True)
+    frame = e.render(3) if frame_after_step else frame
+    outs = {name: read_buffer(e, which, (n,), dtype).astype(np.float64)
+            for name, which, dtype in (("reward", _abi.BUF_REWARD, np.int32), ("done", _abi.BUF_DONE, np.uint8),
+                                       ("lives", _abi.BUF_LIVES, np.int32), ("score", _abi.BUF_SCORE, np.int32))}
+    e.close()
+    return frame, outs
+
+
+def _check_dump(d, prefixes, n, frames_played, lib, verified_steps=0):
+    """the files of every rank in d against an engine stepped on its own; returns their total size"""
+    got = {p: {f[len(p):-4]: np.load(d / f) for f in os.listdir(d) if f.startswith(p) and f.endswith(".npy")} for p in prefixes}
+    assert sum(len(g) for g in got.values()) == len(os.listdir(d))
+    after = {float(g["frame_after_step"][0]) for g in got.values()}
+    assert len(after) == 1
+    frame, outs = _last_step_of_an_engine_alone(lib, n, frames_played, after.pop() == 1.0, verified_steps)
+    seen = []
+    for p, g in got.items():
+        assert sorted(g) == ["done", "env_index", "frame", "frame_after_step", "lives", "reward", "score"], (p, sorted(g))
+        assert all(a.dtype in (np.float32, np.float64) for a in g.values()), p
+        idx = g["env_index"].astype(np.int64)
+        assert np.array_equal(idx, np.unique(idx)) and np.array_equal(g["frame"], frame[idx].astype(np.float32)), p
+        seen.append(idx)
+    # the per-env arrays of the ranks, in rank order, are the whole batch's
+    for name in outs:
+        assert np.array_equal(np.concatenate([got[p][name] for p in prefixes]), outs[name]), name
+    return sum(os.path.getsize(d / f) for f in os.listdir(d)), seen
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(oracle_lib, tmp_path):
+    """--dump-outputs DIR: after R regions of exactly --steps steps, what the last timed step returned -- step outputs of every env,
+    the frame of a seeded sample of envs -- as float .npy files within 64 MB; the same arguments give the same files, and they equal
+    an engine stepped to the same frame on its own (the checker reports no fused launch: pair form, the frame after the step)."""
+    import json
+    n, preroll, settle, warmup, steps, repeats = 64, 300, 3, 2, 5, 2
+    argv = ["--envs", str(n), "--steps", str(steps), "--warmup", str(warmup), "--repeats", str(repeats), "--preroll", str(preroll),
+            "--settle", str(settle), "--no-cpu-baseline", "--no-extras"]
+    script = tmp_path / "worker.py"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TBX_RDZV_KEY")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        script.write_text(BENCH_FLOW_WORKER.format(root=ROOT, argv=argv + ["--dump-outputs", str(d)]))
+        p = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
+        assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["repeats"]["n"] == repeats
+        assert line["check"]["frames_played"] == preroll + settle + warmup + repeats * steps
+        size, _ = _check_dump(d, [""], n, line["check"]["frames_played"], oracle_lib)
+        assert size <= 64 << 20 and np.load(d / "frame_after_step.npy")[0] == 1.0
+        dumps.append({f: np.load(d / f) for f in os.listdir(d)})
+    assert sorted(dumps[0]) == sorted(dumps[1]) and all(np.array_equal(a, dumps[1][f]) for f, a in dumps[0].items())
+
+
+def test_bench_dump_outputs_of_all_ranks_share_one_budget(oracle_lib, tmp_path):
+    """--gpus N --dump-outputs DIR: every rank writes rank<r>_*.npy for its shard, and all of them together stay within
+    bench.DUMP_BYTES -- here cut to a few frames, so that each rank's frames are a seeded sample of its shard (global env indices)."""
+    import json
+    world, n, frame_file = 2, 96, 160 * 240 * 3 * 4
+    budget = world * (6 * frame_file + 8 * 5 * (n // world) + 1024)
+    argv = ["--gpus", str(world), "--envs", str(n), "--steps", "4", "--warmup", "1", "--repeats", "2", "--preroll", "300", "--settle", "2",
+            "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(tmp_path / "dump")]
+    script = tmp_path / "worker.py"
+    script.write_text(BENCH_FLOW_WORKER.format(root=ROOT, argv=argv).replace("sys.argv = ", "bench.DUMP_BYTES = %d\nsys.argv = " % budget))
+    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT="6", TBX_RDZV_DIR=str(tmp_path))
+    env.pop("TBX_RDZV_KEY", None)
+    procs = [subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
+                              stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, text=True) for r in range(world)]
+    out0 = procs[0].communicate(timeout=600)[0]
+    for p in procs:
+        assert p.wait(timeout=600) == 0, out0[-2000:]
+    line = json.loads([ln for ln in out0.splitlines() if ln.startswith("{")][-1])
+    size, seen = _check_dump(tmp_path / "dump", ["rank%d_" % r for r in range(world)], n, line["check"]["frames_played"], oracle_lib,
+                             verified_steps=line["gather"]["gather_every"])
+    assert size <= budget
+    for r, idx in enumerate(seen):
+        lo, hi = shard_range(n, world, r)
+        assert 1 <= len(idx) < hi - lo and lo <= idx.min() and idx.max() < hi, (r, idx)
+
+
+def test_bench_dump_outputs_refuses_a_batch_it_cannot_hold(oracle_lib, tmp_path):
+    """a batch whose per-env arrays alone would pass the dump's budget is refused before anything is timed (rc 2), not cut short"""
+    argv = ["--envs", "64", "--steps", "2", "--warmup", "1", "--repeats", "1", "--preroll", "2", "--settle", "1", "--no-cpu-baseline",
+            "--no-extras", "--dump-outputs", str(tmp_path / "dump")]
+    script = tmp_path / "worker.py"
+    script.write_text(BENCH_FLOW_WORKER.format(root=ROOT, argv=argv).replace("sys.argv = ", "bench.DUMP_BYTES = 4096\nsys.argv = "))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TBX_RDZV_KEY")}
+    p = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
+    assert p.returncode == 2 and "do not fit" in p.stderr, (p.stdout + p.stderr)[-2000:]
+    assert not (tmp_path / "dump").exists()
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -752,3 +861,30 @@ def test_mixed_batch_segment_sizes(oracle_lib):
     mb.close()
     for e in refs:
         e.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form,extra", [("chunks", ["--rollout-chunks", "on"]),
+                                        ("fused_overlapped", ["--rollout-chunks", "off", "--fused-overlap", "on"]),
+                                        ("fused", ["--rollout-chunks", "off", "--fused-overlap", "off"]),
+                                        ("pair", ["--loop", "pair"])])
+def test_gpu_bench_dump_outputs_in_every_loop_form(form, extra, oracle_lib, tmp_path):
+    """--dump-outputs on real HIP after each loop form of the timed path -- rollout chunks and overlapped fused launches (whose
+    results are read behind tbx_device_buffer's lazy join), single fused launches, the two-launch pair -- equals the CPU checker
+    stepped on its own to the same frame; frame_after_step names the form's frame (before the step, except in the pair form)."""
+    import json
+    n = 2048
+    d = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TBX_RDZV_KEY")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--envs", str(n), "--steps", "8", "--warmup", "3",
+                        "--repeats", "2", "--preroll", "60", "--settle", "5", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d)] + extra,
+                       capture_output=True, text=True, timeout=900, cwd="/tmp", env=env)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    lf = line["loop"]
+    assert lf["form"] == {"fused_overlapped": "fused"}.get(form, form), lf
+    if form.startswith("fused"):
+        assert lf["overlapped"] == (form == "fused_overlapped"), lf
+    size, seen = _check_dump(d, [""], n, line["check"]["frames_played"], oracle_lib)
+    assert size <= 64 << 20 and 1 <= len(seen[0]) < n
+    assert np.load(d / "frame_after_step.npy")[0] == (1.0 if form == "pair" else 0.0)
