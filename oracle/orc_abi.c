@@ -442,6 +442,17 @@ int tbx_render_env(tbx_engine* e, int env, uint8_t* out, int channels)
     return TBX_OK;
 }
 
+/* envs first .. first + count - 1 into out ([count][H][W][C]) with the engine's batch painter: the frame checker's slices
+ * (tests/support.py) -- a whole batch at once can be more host memory than a test may hold, one env per call too slow */
+int orc_render_envs(tbx_engine* e, int first, int count, uint8_t* out, int channels)
+{
+    if (!e) return TBX_E_INVALID;
+    if (first < 0 || count < 0 || count > e->n - first || (!out && count)) return fail(e, TBX_E_INVALID, "env range out of range");
+    if (channels != 1 && channels != 3 && channels != 4) return fail(e, TBX_E_INVALID, "channels must be 1, 3 or 4");
+    if (count) orc_render_batch(e->game, e->cfg, e->states + e->ssz * (size_t)first, count, out, channels, e->threads);
+    return TBX_OK;
+}
+
 int tbx_get_state(tbx_engine* e, int env, void* pod, size_t size)
 {
     if (!e) return TBX_E_INVALID;

@@ -29,6 +29,7 @@ static int run_game(int game, int n, int steps)
         for (int i = 0; i < n; i++) dones += done[i];
         if (t % 97 == 0) {
             for (int c = 1; c <= 4; c += (c == 1 ? 2 : 1)) CHECK(tbx_render(e, frame, c));
+            CHECK(orc_render_envs(e, n / 3, n - n / 3, frame, 4));
             CHECK(tbx_get_states(e, 0, n, st, ssz));
             CHECK(tbx_set_states(e, 0, n, st, ssz));
         }

@@ -68,3 +68,88 @@ def stack_from_ring(ring, head):
     """uint8[stack][N][h][w] + the newest slot -> uint8[N][h][w][stack], oldest first (include/toybox_amd.h, new_plane = 2)"""
     k = ring.shape[0]
     return np.stack([ring[(head + 1 + c) % k] for c in range(k)], axis=-1)
+
+
+# ---------------------------------------------------------------- whole-output frame checks
+# A device frame buffer is compared with the oracle's frames of the same envs in slices of bounded size: one reused host array
+# receives each device slice, another the oracle's (orc_render_envs paints just that env range), so a 10 GB chunk buffer never
+# needs 10 GB of host memory.  uint8 frames and an exact oracle: equal means every byte.
+
+FRAME_SLICE_BYTES = 384 << 20          # per host array; the two together stay under 1 GB
+
+
+def bind_render_envs(lib):
+    """orc_render_envs(engine, first, count, out, channels) of the oracle library (not part of the product ABI)"""
+    import ctypes as C
+    f = lib.orc_render_envs
+    if f.argtypes is None:
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    return f
+
+
+def oracle_render_envs(engine, first, count, out, channels):
+    """envs first .. first + count - 1 of an oracle Engine into out[:count]"""
+    assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.shape[0] >= count
+    engine._check(bind_render_envs(engine._lib)(engine._h, int(first), int(count), out.ctypes.data, int(channels)))
+
+
+def oracle_frames(engine, channels, first_env=0):
+    """expected-frames source for FrameChecker.compare: frame f = env first_env + f of the oracle engine as it stands"""
+    return lambda lo, hi, out: oracle_render_envs(engine, first_env + lo, hi - lo, out, channels)
+
+
+def device_frames(ptr, frame_bytes):
+    """frames-under-test source for FrameChecker.compare: frame f lies at device address ptr + f * frame_bytes"""
+    def fetch(lo, hi, out):
+        from toybox_amd import hip
+        hip.memcpy_dtoh(out, ptr + lo * frame_bytes, (hi - lo) * frame_bytes)
+    return fetch
+
+
+class FrameChecker:
+    """compare(got, want, count): frames 0 .. count-1 of two sources, each a callable (lo, hi, out) that fills out[:hi - lo] with
+    frames lo .. hi-1, slice by slice.  A mismatch fails with the first differing byte as (frame j, env i, y, x, channel, got,
+    want) -- j = frame // n, i = frame % n with frames numbered from frame0 -- and the number of frames and envs that differ."""
+
+    def __init__(self, shape, slice_bytes=FRAME_SLICE_BYTES, pinned=False):
+        self.shape = tuple(int(d) for d in shape)
+        fb = int(np.prod(self.shape))
+        self.per = max(1, slice_bytes // fb)
+        self._pinned = pinned
+        self._got = self._want = None
+
+    def _buffers(self, m):
+        if self._got is None or self._got.shape[0] < m:
+            m = self.per if m > self.per // 2 else m              # (a small batch keeps small buffers)
+            if self._pinned:
+                from toybox_amd import hip
+                self._pin = hip.PinnedArray((m,) + self.shape)
+                self._got = self._pin.array
+            else:
+                self._got = np.empty((m,) + self.shape, np.uint8)
+            self._want = np.empty((m,) + self.shape, np.uint8)
+        return self._got, self._want
+
+    def compare(self, got, want, count, n=None, frame0=0, what=""):
+        n = n or count
+        g, w = self._buffers(min(count, self.per))
+        first, bad_frames, bad_envs = None, 0, set()
+        for lo in range(0, count, self.per):
+            hi = min(count, lo + self.per)
+            m = hi - lo
+            got(lo, hi, g[:m])
+            want(lo, hi, w[:m])
+            if np.array_equal(g[:m], w[:m]):
+                continue
+            rows = np.flatnonzero((g[:m] != w[:m]).reshape(m, -1).any(axis=1))
+            bad_frames += len(rows)
+            bad_envs.update(((frame0 + lo + rows) % n).tolist())
+            if first is None:
+                r = int(rows[0])
+                y, x, ch = (int(v) for v in np.argwhere(g[r] != w[r])[0])
+                f = frame0 + lo + r
+                first = (f // n, f % n, y, x, ch, int(g[r][y, x, ch]), int(w[r][y, x, ch]))
+        if first is not None:
+            raise AssertionError("%s: frames differ: first at frame j=%d env i=%d y=%d x=%d channel %d (got %d, want %d); "
+                                 "%d frames of %d, %d envs" % ((what,) + first + (bad_frames, count, len(bad_envs))))

@@ -307,14 +307,13 @@ def test_big_batch_launch_frames_parity(game, hip_lib, oracle_lib, monkeypatch):
     """The batched RGB launch at a size where the big-launch forms are in force -- Breakout's render in two parts (1 024 envs,
     then the rest), SpaceInvaders' staggered first waves, GridWorld's five waves per frame, Amidar's six waves per SIMD --
     against the oracle's frames: the envs on both sides of the part boundary, the ends of the batch and a random sample, after
-    a mid-game pre-roll, and again after more steps."""
-    from toybox_amd import hip
+    a mid-game pre-roll, and again after more steps: every env's frame (tests/support.py FrameChecker)."""
+    from support import FrameChecker, device_frames, oracle_frames
     monkeypatch.setenv("TBX_ORACLE_THREADS", str(min(16, len(__import__("os").sched_getaffinity(0)))))
     n = 16384
     g, o = _pair(game, n, hip_lib, oracle_lib, seed=77)
     H, W = g.height, g.width
-    one = np.empty((H, W, 3), np.uint8)
-    picks = [0, 1, 1022, 1023, 1024, 1025, 2047, 2048, n - 2, n - 1] + [int(i) for i in np.random.default_rng(3).choice(n, 30, replace=False)]
+    chk = FrameChecker((H, W, 3), pinned=True)
     t = 0
     for rounds in (120, 40):
         for _ in range(rounds):
@@ -325,9 +324,7 @@ def test_big_batch_launch_frames_parity(game, hip_lib, oracle_lib, monkeypatch):
         g.sync()
         p, nbytes = g.device_buffer(_abi.BUF_FRAME)
         assert nbytes >= n * H * W * 3
-        for i in picks:
-            hip.memcpy_dtoh(one, p + i * H * W * 3, H * W * 3)
-            assert np.array_equal(one, o.render_env(i, 3)), (game, t, i)
+        chk.compare(device_frames(p, H * W * 3), oracle_frames(o, 3), n, what="%s t=%d" % (game, t))
 
 
 def test_space_invaders_interventions_parity(hip_lib, oracle_lib):

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from support import LEGAL, synthetic_actions
+from support import LEGAL, FrameChecker, device_frames, oracle_frames, synthetic_actions
 from toybox_amd import Engine, ToyboxAmdError, _abi
 
 GAMES = ["breakout", "space_invaders", "amidar", "gridworld"]
@@ -612,9 +612,12 @@ def test_pipelined_mode_keeps_program_order(same_stream, game, n, mode, hip_lib,
     rng = np.random.default_rng(2)
     t = 0
 
-    def check_frame(tag):
+    def check_frame(tag, every_env=False):
         hip.synchronize()
         p, nbytes = g.device_buffer(_abi.BUF_FRAME)
+        if every_env:
+            FrameChecker((H, W, 3)).compare(device_frames(p, H * W * 3), oracle_frames(o, 3), n, what="%s %s" % (game, tag))
+            return
         for i in sample:
             hip.memcpy_dtoh(one, p + i * H * W * 3, H * W * 3)
             assert np.array_equal(one, o.render_env(i, 3)), (tag, i)
@@ -625,7 +628,7 @@ def test_pipelined_mode_keeps_program_order(same_stream, game, n, mode, hip_lib,
             g.render_device(0, 3, stream=rp)
             o.step(synthetic_actions(game, n, t, seed=1337), auto_reset=True)
             t += 1
-        check_frame("round %d" % rnd)
+        check_frame("round %d" % rnd, every_env=rnd == 6)
         # the step's outputs, read behind the stream the step call named
         g.step_synthetic(1337, t, auto_reset=True, stream=sp)
         ro = o.step(synthetic_actions(game, n, t, seed=1337), auto_reset=True)
@@ -667,7 +670,7 @@ def test_pipelined_mode_keeps_program_order(same_stream, game, n, mode, hip_lib,
             g.render_device(0, 1, stream=rp)
             _same_states(g, o, sample[:5], "gray %d" % rnd)
     g.render_device(0, 3, stream=rp)
-    check_frame("end")
+    check_frame("end", every_env=True)
     _same_states(g, o, sample, "end")
     for x, y in zip(g.scalars(), o.scalars()):
         assert np.array_equal(x, y)
@@ -1054,7 +1057,11 @@ def test_rollout_chunks_equal_oracle(game, n, channels, K, ring, form, hip_lib, 
             e.set_option(_abi.OPT_GATHER_EVERY, K)
             e.gather_init(1, 0, e.gather_unique_id())
     assert g.get_option(_abi.OPT_ROLLOUT_CHUNKS_ACTIVE) == 1
-    sample = sorted({0, 1, 255, 256, n // 2, n - 1})
+    # the ends of the batch, its middle, the first envs past a block's / a two-part launch's head (256, 1 024), and the frames at
+    # the ends of every span launch and beside its head's boundary (frame f of a span = env f % n)
+    per = max(1, min(K, 65536 // n))
+    span_frames = [f for j0 in range(0, K, per) for f in (0, 1023, 1024, 1025, min(per, K - j0) * n - 1)]
+    sample = sorted({0, 1, 255, 256, 1023, 1024, 1025, n // 2, n - 1} & set(range(n)) | {f % n for f in span_frames})
     s = hip.Stream()
     chunks = 14
     per_out = 4 * n * 3 + n

@@ -2174,9 +2174,10 @@ struct BreakoutOps : GameOps {
         // 32 768: 0.615-0.621 / 0.618-0.692; 16 384: 0.319-0.320 / 0.317-0.345; 8 192: 0.171-0.173 / 0.165-0.181.  First
         // parts of 256 or 512 envs leave some buffers slow, 2 048 costs 3 us more.  Render-only loops pay 8 us per launch for
         // it (1.195 against 1.187 ms).
-        // Launches of 16 384 .. 32 767 blocks (6 554 .. 13 107 envs) keep the staggered first waves instead: there the second
-        // kernel boundary costs as much as it saves (scripts/pipeline_sweep.py, 8 192 envs: 0.172 / 0.169-0.173 ms per step two
-        // parts / stagger, with a per-step gather 0.179 / 0.175).
+        // Launches of 16 384 .. 32 767 blocks (6 554 .. 13 106 envs at ten waves per frame; 13 107 envs are 32 768 blocks and go
+        // out in two parts) keep the staggered first waves instead: there the second kernel boundary costs as much as it saves
+        // (scripts/pipeline_sweep.py, 8 192 envs: 0.172 / 0.169-0.173 ms per step two parts / stagger, with a per-step gather
+        // 0.179 / 0.175).
         // overlapped = true: one part, no stagger -- a launch that starts behind another rasteriser launch on its stream (a rollout chunk's
         // span launch, rollout_render_span).  (Tried for the per-frame rasteriser launches of a chunk on two lanes, which start side by
         // side: 8 192 envs 0.193 against 0.156 ms per step, 16 384: 0.363 against 0.314; those keep the launch forms of the stream-order loop)
