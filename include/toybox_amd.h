@@ -601,7 +601,14 @@ int tbx_reduce_device(tbx_engine* engine, int query, const double* args, int n_a
  * obs = uint8[N][out_h][out_w][stack], reward float32[N], done uint8[N].
  * Not the Python's: NoopResetEnv draws its count from numpy's RandomState; here it is counter-based (below) unless counts
  * are injected with tbx_agent_set_noops.  bench.Monitor raises when an env is stepped after its game ended inside
- * EpisodicLifeEnv's ignored no-op step; here that is TBX_E_NEEDS_RESET and the stack carries on as it does without a Monitor. */
+ * EpisodicLifeEnv's ignored no-op step; here that is TBX_E_NEEDS_RESET and the stack carries on as it does without a Monitor.
+ * Accepted output geometries, for an H x W frame (tbx_frame_dims): 1 <= out_h <= H, 1 <= out_w <= W, out_w <= 128 and
+ * out_h * out_w <= 7056 (else TBX_E_INVALID), and at most 8 source pixels per output pixel on each axis,
+ * ceil(H / out_h) + 1 <= 8 and ceil(W / out_w) + 1 <= 8 (else TBX_E_UNSUPPORTED).  Per game, out_w and out_h range over:
+ *   Breakout       160 x 240  out_w 35..128, out_h 23..min(160, 7056 / out_w)  (out_h = 160 for out_w <= 44)
+ *   SpaceInvaders  210 x 320  out_w 46..128, out_h 30..min(210, 7056 / out_w)  (out_h = 210 never: at most 153)
+ *   Amidar         250 x 160  out_w 23..128, out_h 36..min(250, 7056 / out_w)  (out_h = 250 for out_w <= 28)
+ *   GridWorld      128 x 160  out_w 23..128, out_h 19..min(128, 7056 / out_w)  (out_h = 128 for out_w <= 55) */
 typedef struct tbx_agent_config {
     int32_t skip;          /* >= 1 (4) */
     int32_t out_h, out_w;  /* 84, 84 */

@@ -1,4 +1,7 @@
 """Helpers shared by the test-suite (host-side numpy restatements of tiny pure functions)."""
+import functools
+from fractions import Fraction
+
 import numpy as np
 
 M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -31,6 +34,102 @@ def synthetic_actions(game, n, t, seed=1337, env_offset=0):
 def noop_count(noop_seed, global_env, episode_index, noop_max):
     """the engine's default no-op rule (include/toybox_amd.h, tbx_agent_init): 1 + splitmix64(seed ^ env << 32 ^ k) % noop_max"""
     return 1 + int(splitmix64(int(noop_seed) ^ (int(global_env) << 32) ^ int(episode_index)) % np.uint64(noop_max))
+
+
+# ---------------------------------------------------------------- the observation resize (WarpFrame) by its definition
+# include/toybox_amd.h, tbx_agent_config_t: an area average with exact rational weights, rounded half up.
+
+def area_resize_exact(img, oh, ow):
+    """INTER_AREA by its definition, in exact rational arithmetic, round half up."""
+    H, W = img.shape
+    out = np.zeros((oh, ow), np.uint8)
+    for oy in range(oh):
+        y0, y1 = Fraction(oy * H, oh), Fraction((oy + 1) * H, oh)
+        for ox in range(ow):
+            x0, x1 = Fraction(ox * W, ow), Fraction((ox + 1) * W, ow)
+            acc = Fraction(0)
+            sy = int(y0)
+            while sy < y1:
+                wy = min(y1, sy + 1) - max(y0, sy)
+                sx = int(x0)
+                while sx < x1:
+                    acc += wy * (min(x1, sx + 1) - max(x0, sx)) * int(img[sy, sx])
+                    sx += 1
+                sy += 1
+            mean = acc / ((y1 - y0) * (x1 - x0))
+            out[oy, ox] = int(mean + Fraction(1, 2))      # floor(mean + 1/2)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def overlap_matrix(src, out):
+    """M[o, s] = length of the overlap of output cell o with source pixel s, in units of 1/out source pixels (read-only)."""
+    m = np.zeros((out, src), np.int64)
+    for o in range(out):
+        lo, hi = o * src, (o + 1) * src
+        for s_ in range(lo // out, src):
+            if s_ * out >= hi:
+                break
+            m[o, s_] = min(hi, (s_ + 1) * out) - max(lo, s_ * out)
+    m.flags.writeable = False
+    return m
+
+
+def area_sums(img, oh, ow):
+    """int64[..., oh, ow]: the weighted sums of the definition, sum = mean x H x W, for one image or a batch [..., H, W].
+    The products run in binary64 (BLAS): every operand and partial sum is an integer below 255 H W < 2^25, so exact."""
+    H, W = img.shape[-2:]
+    my, mx = overlap_matrix(H, oh).astype(np.float64), overlap_matrix(W, ow).T.astype(np.float64)
+    return np.rint(my @ np.asarray(img, np.float64) @ mx).astype(np.int64)
+
+
+def area_resize_int(img, oh, ow):
+    """The same definition from the integer sums (fast enough for whole rollouts; one image or a batch [..., H, W])."""
+    H, W = img.shape[-2:]
+    return ((area_sums(img, oh, ow) + (H * W) // 2) // (H * W)).astype(np.uint8)
+
+
+# ---------------------------------------------------------------- the output geometries tbx_agent_init accepts
+# include/toybox_amd.h, tbx_agent_config_t: 1 <= out <= frame, out_w <= 128, out_h * out_w <= 7056, and at most 8 source pixels
+# per output pixel and axis, ceil(frame / out) + 1 <= 8 (else TBX_E_UNSUPPORTED).  Restated here, not read from either library.
+
+FRAME_DIMS = {"breakout": (160, 240), "space_invaders": (210, 320), "amidar": (250, 160), "gridworld": (128, 160)}
+AGENT_MAX_OUT_W, AGENT_MAX_OUT_PX, AGENT_MAX_TAPS = 128, 84 * 84, 8
+
+
+def agent_range_violations(H, W, oh, ow):
+    """the range limits (TBX_E_INVALID) this output geometry breaks, by name"""
+    limits = {"out_h >= 1": oh >= 1, "out_w >= 1": ow >= 1, "out_h <= H": oh <= H, "out_w <= W": ow <= W,
+              "out_w <= 128": ow <= AGENT_MAX_OUT_W, "out_h * out_w <= 7056": oh * ow <= AGENT_MAX_OUT_PX}
+    return [k for k, ok in limits.items() if not ok]
+
+
+def agent_taps_ok(H, W, oh, ow):
+    """at most 8 source pixels per output pixel on each axis (else TBX_E_UNSUPPORTED); oh, ow >= 1"""
+    return -(-H // oh) + 1 <= AGENT_MAX_TAPS and -(-W // ow) + 1 <= AGENT_MAX_TAPS
+
+
+def agent_geometry_code(H, W, oh, ow):
+    """what tbx_agent_init returns for this output geometry (other fields in range): 0, TBX_E_INVALID (-1), TBX_E_UNSUPPORTED (-4)"""
+    if agent_range_violations(H, W, oh, ow):
+        return -1
+    return 0 if agent_taps_ok(H, W, oh, ow) else -4
+
+
+def agent_geometry_ok(H, W, oh, ow):
+    return agent_geometry_code(H, W, oh, ow) == 0
+
+
+def agent_out_h_range(H, W, ow):
+    """(smallest, largest) accepted out_h for this out_w, or None"""
+    hs = [h for h in range(1, H + 1) if agent_geometry_ok(H, W, h, ow)]
+    return (hs[0], hs[-1]) if hs else None
+
+
+def agent_out_w_range(H, W, oh):
+    """(smallest, largest) accepted out_w for this out_h, or None"""
+    ws = [w for w in range(1, min(W, AGENT_MAX_OUT_W) + 1) if agent_geometry_ok(H, W, oh, w)]
+    return (ws[0], ws[-1]) if ws else None
 
 
 # ---------------------------------------------------------------- Amidar state edits of the wrapper corner cases

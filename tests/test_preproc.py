@@ -3,56 +3,15 @@ own wrapper classes (tests/golden/wrappers/, generator tests/golden/make_wrapper
 restatement here and through the HIP library on the GPU box -- and (b) on the GPU box, the HIP library against the CPU
 restatement on larger batches, bit for bit."""
 import ctypes as C
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from support import synthetic_actions
+import support
+from support import area_resize_exact, area_resize_int, synthetic_actions
 from toybox_amd import Engine, _abi
 
 GAMES = ["breakout", "space_invaders", "amidar"]
-
-
-def area_resize_exact(img, oh, ow):
-    """INTER_AREA by its definition, in exact rational arithmetic, round half up."""
-    H, W = img.shape
-    out = np.zeros((oh, ow), np.uint8)
-    for oy in range(oh):
-        y0, y1 = Fraction(oy * H, oh), Fraction((oy + 1) * H, oh)
-        for ox in range(ow):
-            x0, x1 = Fraction(ox * W, ow), Fraction((ox + 1) * W, ow)
-            acc = Fraction(0)
-            sy = int(y0)
-            while sy < y1:
-                wy = min(y1, sy + 1) - max(y0, sy)
-                sx = int(x0)
-                while sx < x1:
-                    acc += wy * (min(x1, sx + 1) - max(x0, sx)) * int(img[sy, sx])
-                    sx += 1
-                sy += 1
-            mean = acc / ((y1 - y0) * (x1 - x0))
-            out[oy, ox] = int(mean + Fraction(1, 2))      # floor(mean + 1/2)
-    return out
-
-
-def overlap_matrix(src, out):
-    """M[o, s] = length of the overlap of output cell o with source pixel s, in units of 1/out source pixels."""
-    m = np.zeros((out, src), np.int64)
-    for o in range(out):
-        lo, hi = o * src, (o + 1) * src
-        for s_ in range(lo // out, src):
-            if s_ * out >= hi:
-                break
-            m[o, s_] = min(hi, (s_ + 1) * out) - max(lo, s_ * out)
-    return m
-
-
-def area_resize_int(img, oh, ow):
-    """The same definition as two integer matrix products (fast enough for whole rollouts)."""
-    H, W = img.shape
-    acc = overlap_matrix(H, oh) @ img.astype(np.int64) @ overlap_matrix(W, ow).T
-    return ((acc + (H * W) // 2) // (H * W)).astype(np.uint8)
 
 
 def test_warp_area_matches_definition(oracle_lib):
@@ -71,6 +30,81 @@ def test_warp_area_matches_definition(oracle_lib):
     got = np.zeros((84, 84), np.uint8)
     oracle_lib.orc_warp_area(flat.ctypes.data, 160, 240, got.ctypes.data, 84, 84)
     assert (got == 137).all()
+
+
+def edge_geometries(H, W):
+    """the output geometries at the edges of what tbx_agent_init accepts for an H x W frame: every out_w with the smallest and the
+    largest out_h, every out_h with the smallest and the largest out_w (so the corners, out_h = H and out_w = 128 where they
+    are accepted), every 7 056-pixel plane and every integer ratio"""
+    g = set()
+    for ow in range(1, 129):
+        r = support.agent_out_h_range(H, W, ow)
+        if r:
+            g.update({(r[0], ow), (r[1], ow)})
+    for oh in range(1, H + 1):
+        r = support.agent_out_w_range(H, W, oh)
+        if r:
+            g.update({(oh, r[0]), (oh, r[1])})
+    for oh in range(1, H + 1):
+        for ow in range(1, 129):
+            if support.agent_geometry_ok(H, W, oh, ow) and (oh * ow == support.AGENT_MAX_OUT_PX or (H % oh == 0 and W % ow == 0)):
+                g.add((oh, ow))
+    return sorted(g)
+
+
+def half_up_profile(src, out, rng):
+    """uint8[src]: a profile whose area means over `out` cells are exactly k + 1/2 in as many cells as the weights allow -- each
+    cell's last source pixel is chosen (left to right) to bring its weighted sum to src/2 modulo src"""
+    m = support.overlap_matrix(src, out)
+    c = rng.integers(0, 256, src).astype(np.int64)
+    v = np.arange(256)
+    for o in range(out):
+        last = int(np.flatnonzero(m[o])[-1])
+        rest = int(m[o] @ c) - int(m[o, last]) * int(c[last])
+        ok = np.flatnonzero((rest + int(m[o, last]) * v) % src == src // 2)
+        if len(ok):
+            c[last] = ok[rng.integers(len(ok))]
+    return c.astype(np.uint8)
+
+
+@pytest.mark.parametrize("game", list(support.FRAME_DIMS))
+def test_warp_area_matches_definition_at_every_edge_geometry(game, oracle_lib):
+    """orc_warp_area (what the oracle's agent layer and so every GPU observation test measures against) == the definition in
+    include/toybox_amd.h at the edges of the accepted geometry space of the game's frame: random bytes, all 255 (the largest
+    sums: 255 x 67 200 for SpaceInvaders, near the 2^25 bound of the device's reciprocal), flat images, and images whose area
+    means are exactly k + 1/2 (round half UP) along either axis; the exact rational form on the smallest planes."""
+    oracle_lib.orc_warp_area.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    H, W = support.FRAME_DIMS[game]
+    rng = np.random.default_rng(H * 1000 + W)
+    geoms = edge_geometries(H, W)
+    halves = 0
+    for (oh, ow) in geoms:
+        imgs = np.stack([rng.integers(0, 256, (H, W), dtype=np.uint8), np.full((H, W), 255, np.uint8),
+                         np.full((H, W), int(rng.integers(0, 256)), np.uint8),
+                         np.broadcast_to(half_up_profile(W, ow, rng)[None, :], (H, W)),
+                         np.broadcast_to(half_up_profile(H, oh, rng)[:, None], (H, W))])
+        imgs = np.ascontiguousarray(imgs)
+        acc = support.area_sums(imgs, oh, ow)
+        want = ((acc + (H * W) // 2) // (H * W)).astype(np.uint8)
+        halves += int((2 * (acc % (H * W)) == H * W).sum())
+        got = np.zeros((len(imgs), oh, ow), np.uint8)
+        for k in range(len(imgs)):
+            oracle_lib.orc_warp_area(imgs[k].ctypes.data, H, W, got[k].ctypes.data, oh, ow)
+            if not np.array_equal(got[k], want[k]):
+                y, x = (int(v) for v in np.argwhere(got[k] != want[k])[0])
+                raise AssertionError("%s %dx%d -> %dx%d image %d: first difference at y=%d x=%d (got %d, want %d; sum %d / %d), %d pixels"
+                                     % (game, H, W, oh, ow, k, y, x, got[k][y, x], want[k][y, x], acc[k][y, x], H * W,
+                                        int((got[k] != want[k]).sum())))
+        assert (want[1] == 255).all() and (want[2] == imgs[2][0, 0]).all()
+    assert halves > 10 * len(geoms)                             # the k + 1/2 images do reach the rounding edge
+    # the exact rational form of the definition on the smallest accepted planes (it takes ~1 s per 10^3 output pixels)
+    small = sorted(geoms, key=lambda g: g[0] * g[1])[:2]
+    for (oh, ow) in small:
+        img = rng.integers(0, 256, (H, W), dtype=np.uint8)
+        got = np.zeros((oh, ow), np.uint8)
+        oracle_lib.orc_warp_area(img.ctypes.data, H, W, got.ctypes.data, oh, ow)
+        assert np.array_equal(got, area_resize_exact(img, oh, ow)), (game, oh, ow)
+        assert np.array_equal(got, area_resize_int(img, oh, ow)), (game, oh, ow)
 
 
 # ------------------------------------------------------------------ the reference's wrapper stack, as committed fixtures
@@ -158,6 +192,81 @@ def lib(request, oracle_lib):
         return oracle_lib
     from toybox_amd import _lib
     return _lib.load()
+
+
+def boundary_configs(H, W):
+    """(limit, at, past): for each limit of tbx_agent_config_t a config (skip, out_h, out_w, stack) at it that is accepted (or None
+    where the frame allows none) and one just past it that breaks that limit alone -- no other range limit would refuse it"""
+    ow_lo = min(w for w in range(1, 129) if support.agent_out_h_range(H, W, w))
+    oh_lo = min(h for h in range(1, H + 1) if support.agent_out_w_range(H, W, h))
+    oh_of_ow_lo, ow_of_oh_lo = support.agent_out_h_range(H, W, ow_lo)[1], support.agent_out_w_range(H, W, oh_lo)[1]
+    at_h = support.agent_out_w_range(H, W, H)                       # out_h = H is accepted for some out_w (not SpaceInvaders')
+    w_past_h = min(ow_lo, support.AGENT_MAX_OUT_PX // (H + 1))     # (a plane that fits: only out_h <= H refuses it)
+    oh_128 = support.AGENT_MAX_OUT_PX // 129                        # 54: 54 x 129 fits in 7 056 pixels, so only out_w <= 128 refuses it
+    # the largest accepted plane, and the smallest plane above 7 056 pixels that passes every other limit
+    others_ok = [(h, w) for h in range(1, H + 1) for w in range(1, min(W, 128) + 1) if support.agent_taps_ok(H, W, h, w)]
+    biggest = max((g for g in others_ok if g[0] * g[1] <= support.AGENT_MAX_OUT_PX), key=lambda g: (g[0] * g[1], g))
+    over = min((g for g in others_ok if g[0] * g[1] > support.AGENT_MAX_OUT_PX), key=lambda g: (g[0] * g[1], g))
+    geo = [("taps: smallest out_w", (oh_of_ow_lo, ow_lo), (oh_of_ow_lo, ow_lo - 1)),
+           ("taps: smallest out_h", (oh_lo, ow_of_oh_lo), (oh_lo - 1, ow_of_oh_lo)),
+           ("out_h <= H", (H, at_h[0]) if at_h else None, (H + 1, w_past_h)),
+           ("out_w <= 128", (oh_128, 128), (oh_128, 129)),
+           ("out_h * out_w <= 7056", biggest, over),
+           ("out_h >= 1", None, (0, 84)),                             # (one row is never accepted: more than 8 taps)
+           ("out_w >= 1", None, (84, 0))]
+    cfgs = [(name, at and (4,) + at + (4,), (4,) + past + (4,)) for name, at, past in geo]
+    cfgs += [("stack 1..4", (4, 84, 84, 1), (4, 84, 84, 0)), ("stack 1..4", (4, 84, 84, 4), (4, 84, 84, 5)),
+             ("skip 1..64", (1, 84, 84, 4), (0, 84, 84, 4)), ("skip 1..64", (64, 84, 84, 4), (65, 84, 84, 4))]
+    return cfgs
+
+
+def _agent_init_code(lib, game, cfg, reset):
+    """what tbx_agent_init returns for (skip, out_h, out_w, stack); reset: an accepted config must then reset every env"""
+    from toybox_amd._lib import ToyboxAmdError
+    skip, oh, ow, stack = cfg
+    with Engine(game, 3, lib=lib) as e:
+        try:
+            e.agent_init(skip=skip, out_h=oh, out_w=ow, stack=stack)
+        except ToyboxAmdError as err:
+            return err.code
+        if reset:
+            e.seed(1)
+            assert e.agent_reset().shape == (3, oh, ow, stack)
+    return 0
+
+
+@pytest.mark.parametrize("game", list(support.FRAME_DIMS))
+def test_agent_config_limits_on_both_libraries(game, lib, oracle_lib):
+    """tbx_agent_init at each limit the header states for tbx_agent_config_t and one past it: smallest out_w / out_h (8 source
+    pixels per output pixel and axis, else TBX_E_UNSUPPORTED), out_h = H and H + 1, out_w = 128 and 129 (54 rows: a plane
+    within 7 056 pixels), the largest accepted plane and the next plane size above 7 056 pixels, out_h / out_w 0, stack 0 / 1 /
+    4 / 5, skip 0 / 1 / 64 / 65 (out of range: TBX_E_INVALID).  Every config past a limit breaks that limit alone, so removing
+    any one check changes a result.  (out_w <= W cannot be reached on its own: every frame is wider than 128.)  An accepted
+    config resets; the library under test and the oracle decide every config alike, and as the header says."""
+    H, W = support.FRAME_DIMS[game]
+    h, w = C.c_int(), C.c_int()
+    assert lib.tbx_frame_dims(getattr(_abi, "GAME_" + game.upper()), C.byref(h), C.byref(w)) == 0 and (h.value, w.value) == (H, W)
+    seen = set()
+    for name, at, past in boundary_configs(H, W):
+        # each config past a limit breaks that limit alone: without it, the config would be accepted or refused otherwise
+        skip, oh, ow, stack = past
+        broken = support.agent_range_violations(H, W, oh, ow) + (["stack 1..4"] if not 1 <= stack <= 4 else []) + \
+            (["skip 1..64"] if not 1 <= skip <= 64 else [])
+        if name.startswith("taps"):
+            assert broken == [] and not support.agent_taps_ok(H, W, oh, ow), (game, name, past)
+        else:
+            assert broken == [name], (game, name, past, broken)
+        for cfg, want in ((at, 0), (past, _abi.E_UNSUPPORTED if name.startswith("taps") else _abi.E_INVALID)):
+            if cfg is None:
+                continue
+            assert want == (support.agent_geometry_code(H, W, cfg[1], cfg[2]) if 1 <= cfg[0] <= 64 and 1 <= cfg[3] <= 4 else _abi.E_INVALID)
+            got = _agent_init_code(lib, game, cfg, reset=want == 0)   # (a config the header refuses is never run)
+            assert got == want, "%s, %s: skip %d out %d x %d stack %d: tbx_agent_init returned %d, the header's limits say %d" % (
+                (game, name) + cfg + (got, want))
+            if lib is not oracle_lib:
+                assert _agent_init_code(oracle_lib, game, cfg, reset=want == 0) == got, (game, name, cfg)
+            seen.add(want)
+    assert seen == {0, _abi.E_INVALID, _abi.E_UNSUPPORTED}
 
 
 @pytest.mark.parametrize("game", GAMES)

@@ -261,7 +261,12 @@ class ToyboxPreprocVecEnv:
                                 uint8[N, size, size, stack] array of the rotating pool (tbx_host_stack_push: np.roll's data
                                 movement as threaded host code; 9 bytes of host memory traffic per pixel, so at 10^4 envs it is
                                 the host's memory system that sets the rate, not the link).
-    step_async() queues the device work and the copies; step_wait() waits for them (vec_env/__init__.py:67-87)."""
+    step_async() queues the device work and the copies; step_wait() waits for them (vec_env/__init__.py:67-87).
+
+    size: the side of the square observation, from the smallest size with at most 8 source pixels per output pixel on each axis
+    (frame / size, rounded up, plus one <= 8) to 84 (size x size <= 7056): Breakout 35..84, SpaceInvaders 46..84, Amidar
+    36..84, GridWorld 23..84.  Engine.agent_init takes non-square out_h x out_w within the limits of include/toybox_amd.h
+    (tbx_agent_config_t); anything outside them raises ToyboxAmdError."""
 
     def __init__(self, game, num_envs, skip=4, size=84, stack=4, clip_rewards=True, seed=None, engine=None,
                  episode_life=False, fire_reset=False, noop_max=0, noop_seed=0, env_offset=0, frame_stack="vec", scale=False,
