@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched game-step hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--loop auto|pair] [--gather-every K] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--loop auto|pair] [--gather-every K] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: every env is stepped one frame (transition + auto-reset, actions
 generated on the device by the counter-based rule of SURVEY 8d) and one uint8[N,H,W,3] frame batch is rasterised into HBM.
 Workload: Breakout, 65 536 envs IN TOTAL (the metric names one 64k-env batch on 1/2/4/8 MI355X: `--scaling strong`, the
 default -- rank r owns the contiguous shard r of N), env seeds 1234 + global env index.  For N > 1 there is one
 process per GPU: started by any launcher that exports RANK / LOCAL_RANK / WORLD_SIZE (torch.distributed.run does), or by this
-script itself when it finds no RANK in its environment; the other reading (65 536 envs PER GPU, `weak`) is measured in the
-same invocation with a communicator of its own and printed beside `value`, and `share_of_linear` = strong total / weak total.
+script itself when it finds no RANK in its environment; with --full the other reading (65 536 envs PER GPU, `weak`) is measured
+in the same invocation with a communicator of its own and printed beside `value`, and `share_of_linear` = strong total / weak total.
 The only exchange is the all-gather of the packed 8-byte {reward, done, lives} records -- tbx_gather, RCCL behind the C-ABI,
 no PyTorch -- through a K-step record ring (--gather-every, default 4: one collective per 4 steps carrying all 4 steps'
 records; 1 = one per step); before anything is timed one exchange is verified (own slice == TBX_BUF_PACKED, every other rank's
@@ -21,21 +21,26 @@ of frame t and the step to frame t+1 as ONE launch; `pair` is tbx_step_synthetic
 order, the rate a policy-driven loop gets.  `chunks` (round 6; where the engine runs them: Breakout up to 32 768 envs,
 SpaceInvaders up to 8 192, --rollout-chunks) is one tbx_rollout_synthetic per --gather-every steps -- step launches on a step
 lane, the chunk's rasteriser launches on other internal streams (Breakout: ONE launch over the chunk's frames, chunk behind
-chunk), the ring's collective queued by the call -- when the timed region is a whole number of chunks.  Whenever `value` is not the pair form in stream order, that is measured on the same engine and reported beside it
-as `serialised`.
+chunk), the ring's collective queued by the call -- when the timed region is a whole number of chunks.  Whenever `value` is not the
+pair form in stream order, --full measures that on the same engine and reports it beside it as `serialised`.
 
 Protocol (mirroring the repeat-and-summarise shape of the reference's test/benchmark.py:119-148): an untimed
 pre-roll of step-only frames so that the timed region sees mid-game states with episodes ending and auto-resets firing,
 W warm-up steps, then R regions of exactly K steps, each bracketed by device-sync + rank barrier on both sides; a region's
 time is the MAX over ranks; the reported value is the MEDIAN region (min / max alongside).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, pre-rolls, warms up, times the R regions, writes the --dump-outputs files and
+prints it: besides the contract fields it carries only what those steps yield --
   roofline       -- the dominant kernel (the rasteriser; fused: rasteriser + step launch) priced against HBM bandwidth with HIP
                     events on the caller's stream: fused, around runs of 8 back-to-back launches (time / 8); two-launch form,
                     around every 8th rasteriser launch; never next to a synchronisation,
   loop           -- which loop form `value` was measured with (form, chunk_k, overlapped),
   ranks          -- one record per rank: HIP ordinal, PCI address, arch, shard (tbx_device_identity); two ranks of an RCCL run on one
                     PCI address end the run with rc 7,
+  metric_version -- what `value` means (it changed between rounds 3 and 4) and which arms carry the older reading,
+  rccl           -- ranks the communicator spans as RCCL reports it, ring depth, bytes per collective, library, verified,
+  check          -- the rollout really played (mean score, lives, frames played; a rollout whose score never moved is rc 3).
+--full adds every arm that takes runs of its own (--no-extras / --no-configs / --no-cpu-baseline leave parts of them out):
   serialised     -- the two-launch loop in stream order on the same engine (when `value` is anything else),
   step_only      -- the same loop without the rasteriser (not bandwidth-bound: no roofline),
   weak / strong  -- (N > 1) the other reading, and share_of_linear,
@@ -47,10 +52,9 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                     whole-step fraction of 8 TB/s,
   agent_path     -- (N = 1, Breakout) agent steps/s of the fused baselines wrapper stack at the headline batch size, every game,
                     rolled stack and plane ring (`--protocol agent --deepmind [--obs ring]` in short form),
-  metric_version -- what `value` means (it changed between rounds 3 and 4) and which arms carry the older reading,
-  rccl           -- ranks the communicator spans as RCCL reports it, ring depth, bytes per collective, library, verified,
-  cpu_baseline   -- the CPU oracle (oracle/, a port: ctoybox itself cannot be built offline) on this box's host cores, a
-                    bounded sample of the same 65 536-env workload, plus BASELINE config 1 (one env, one thread); rank 0, every N.
+  cpu_baseline   -- the CPU oracle (oracle/, a port: ctoybox itself cannot be built offline) on the host's cores, a bounded
+                    sample of the same 65 536-env workload, plus BASELINE config 1 (one env, one thread); rank 0, every N;
+                    likewise beside --game mixed and --protocol reference.
 --dry-run walks the N-process launch, id exchange, barriers and teardown without touching a GPU (CPU test of the launcher).
 """
 import argparse
@@ -121,9 +125,13 @@ def parse():
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--channels", type=int, default=3)
     ap.add_argument("--no-render", action="store_true", help="step-only mode as the main arm (no roofline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the step-only arm and the strong-scaling share probe")
-    ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 2-5 beside the headline line (N = 1, Breakout)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every arm beside the headline, each timed in runs of its own: serialised, step_only, the other reading "
+                         "(N > 1), scaling_strong, configs, agent_path and the CPU oracle (--no-extras / --no-configs / --no-cpu-baseline "
+                         "leave parts of it out).  Without it a run sets up, warms up, times its regions and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip every arm but the CPU oracle")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip BASELINE configs 2-5 and the agent path (N = 1, Breakout)")
     ap.add_argument("--with-gather", action="store_true", help="run the RCCL record gather even at one rank (1-rank communicator)")
     ap.add_argument("--gather", default="rccl", choices=["rccl", "host"],
                     help="transport of the record gather (TBX_OPT_GATHER_TRANSPORT): rccl = ncclAllGather over xGMI; host = staged through "
@@ -138,7 +146,7 @@ def parse():
                     help="N > 1 only: if no RCCL communicator can be made, run without the per-step gather (file barrier) instead of failing")
     ap.add_argument("--pipeline", type=int, default=1, choices=[0, 1, 2, 3], help="TBX_OPT_PIPELINE of the main arm (1 = engine's choice)")
     ap.add_argument("--in-process-arms", action="store_true",
-                    help="run BASELINE configs 2-5 and the strong-scaling probe in this process instead of one process per arm")
+                    help="--full: run BASELINE configs 2-5 and the strong-scaling probe in this process instead of one process per arm")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / barrier walk-through without any GPU call")
     ap.add_argument("--gym", action="store_true", help="reference protocol: also the env.step() arm (test/benchmark.py:83-97)")
     ap.add_argument("--reps", type=int, default=30, help="reference protocol: repetitions (mean and s.e.m. reported)")
@@ -149,13 +157,15 @@ def parse():
     ap.add_argument("--obs", default="stack", choices=["stack", "ring"],
                     help="agent protocol: 'stack' = the rolled uint8[N,84,84,4] on the device (VecFrameStack's array); 'ring' = one new "
                          "plane per step into a ring of the last 4 (tbx_agent_config_t::new_plane = 2: the reference's data flow)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall-time budget of the CPU arm at the headline batch")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: wall-time budget of the CPU arm at the headline batch")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed regions, write what the last timed step returned to its caller as DIR/<name>.npy "
                          "(batch protocol, one game; see dump_outputs)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 10000 if args.protocol == "reference" else 200
+    if not args.full:           # the headline alone: every arm beside it, CPU oracle included, is a --full one
+        args.no_extras = args.no_configs = args.no_cpu_baseline = True
     return args
 
 
@@ -409,7 +419,7 @@ def bench_reference_protocol(args):
     random agent, obs, reward, done, _ = env.step(action), reset when done -- the observation is rendered and copied to the host
     every step); FPS = steps / elapsed per repetition, --reps repetitions, mean and s.e.m. as :119-148 print them, and the
     harness's "slowdown" of the env arm against the raw arm.  One FFI round trip per frame: on a GPU this measures latency,
-    not throughput; the CPU oracle runs the same loops beside it."""
+    not throughput; with --full the CPU oracle runs the same loops beside it."""
     from toybox_amd import Engine
     from toybox_amd import toybox as tbmod
     from toybox_amd.envs import ENV_IDS

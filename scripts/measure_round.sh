@@ -8,24 +8,24 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$REPO"
-B="python bench.py --no-cpu-baseline"
-# ---- bench lines.  The first one is the driver's own command: it carries serialised, step_only, scaling_strong, BASELINE
+B="python bench.py --full --no-cpu-baseline"
+# ---- bench lines.  The first one is the headline command with --full: it carries serialised, step_only, scaling_strong, BASELINE
 # configs 2-5, cpu_baseline, cpu_config1
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_breakout_65536.json" 2> "$OUT/bench_breakout_65536.err"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_breakout_65536.json" 2> "$OUT/bench_breakout_65536.err"
 $B --no-configs > "$OUT/bench_breakout_65536_steps200.json" 2>/dev/null
 for g in space_invaders amidar; do $B --game $g > "$OUT/bench_${g}_65536.json" 2>/dev/null; done
 $B --game gridworld --no-extras > "$OUT/bench_gridworld_65536.json" 2>/dev/null
 for g in breakout space_invaders amidar; do $B --game $g --envs 4096 --steps 400 > "$OUT/bench_${g}_4096.json" 2>/dev/null; done
-python bench.py --game mixed --envs 32768 --with-gather --cpu-seconds 8 > "$OUT/bench_mixed_32768.json" 2>/dev/null
+python bench.py --game mixed --envs 32768 --with-gather --cpu-seconds 8 --full > "$OUT/bench_mixed_32768.json" 2>/dev/null
 $B --game mixed --envs 32768 --with-gather --loop pair --gather-every 1 > "$OUT/bench_mixed_32768_pair_k1.json" 2>/dev/null
 $B --envs 8192 --with-gather --no-extras --steps 400 > "$OUT/bench_breakout_8192_gather.json" 2>/dev/null
 $B --envs 8192 --with-gather --no-extras --steps 400 --loop pair > "$OUT/bench_breakout_8192_gather_pair_k4.json" 2>/dev/null
 $B --envs 8192 --with-gather --no-extras --steps 400 --loop pair --gather-every 1 > "$OUT/bench_breakout_8192_gather_pair_k1.json" 2>/dev/null
 # ---- the N-process flow on ONE GPU: 2 and 8 ranks on device 0, host transport of the gather (no RCCL between two ranks of one device)
-python bench.py --gpus 2 --gather host --one-device --cpu-seconds 4 > "$OUT/rehearsal_2ranks_host_transport.json" 2> "$OUT/rehearsal_2ranks.err"
-python bench.py --gpus 8 --gather host --one-device --cpu-seconds 4 --steps 20 --warmup 5 > "$OUT/rehearsal_8ranks_host_transport.json" 2> "$OUT/rehearsal_8ranks.err"
+python bench.py --gpus 2 --gather host --one-device --cpu-seconds 4 --full > "$OUT/rehearsal_2ranks_host_transport.json" 2> "$OUT/rehearsal_2ranks.err"
+python bench.py --gpus 8 --gather host --one-device --cpu-seconds 4 --steps 20 --warmup 5 --full > "$OUT/rehearsal_8ranks_host_transport.json" 2> "$OUT/rehearsal_8ranks.err"
 # ... and under the driver's own launch line for N > 1 (torch.distributed.run exports RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*)
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 --gather host --one-device --cpu-seconds 4 > "$OUT/rehearsal_2ranks_torch_distributed_run.json" 2> "$OUT/rehearsal_2ranks_tdr.err"
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 --gather host --one-device --cpu-seconds 4 --full > "$OUT/rehearsal_2ranks_torch_distributed_run.json" 2> "$OUT/rehearsal_2ranks_tdr.err"
 for g in breakout space_invaders amidar gridworld; do
   python bench.py --protocol agent --game $g --steps 100 --warmup 10 > "$OUT/agent_${g}.json" 2>/dev/null
   python bench.py --protocol agent --deepmind --game $g --steps 100 --warmup 10 > "$OUT/agent_${g}_deepmind.json" 2>/dev/null
@@ -33,7 +33,7 @@ for g in breakout space_invaders amidar gridworld; do
   python bench.py --protocol agent --obs ring --deepmind --game $g --steps 100 --warmup 10 > "$OUT/agent_${g}_ring_deepmind.json" 2>/dev/null
 done
 for g in breakout space_invaders amidar; do
-  python bench.py --protocol reference --gym --game $g --reps 10 > "$OUT/reference_${g}.json" 2>/dev/null        # 10 reps x 10 000 steps, both arms, CPU beside
+  python bench.py --protocol reference --gym --game $g --reps 10 --full > "$OUT/reference_${g}.json" 2>/dev/null        # 10 reps x 10 000 steps, both arms, CPU beside
 done
 for g in breakout space_invaders amidar; do
   python bench.py --protocol host --game $g --envs 8192 --steps 20 --warmup 3 > "$OUT/host_${g}.json" 2>/dev/null        # PCIe-inclusive: frames / observations to host memory

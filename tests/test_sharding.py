@@ -351,7 +351,7 @@ def test_bench_n_process_flow_end_to_end_on_the_checker(world, extra, oracle_lib
     exchange, share_of_linear as a fraction -- over the oracle's shared-memory gather."""
     import json
     # world 2 also carries the CPU arm: the north star wants it "in the same run" at every GPU count (rank 0, bounded sample)
-    argv = ["--gpus", str(world), "--envs", "96", "--steps", "6", "--warmup", "2", "--repeats", "2", "--preroll", "300"] + \
+    argv = ["--gpus", str(world), "--envs", "96", "--steps", "6", "--warmup", "2", "--repeats", "2", "--preroll", "300", "--full"] + \
            (["--cpu-seconds", "0.3"] if world == 2 else ["--no-cpu-baseline"]) + extra
     script = tmp_path / "worker.py"
     script.write_text(BENCH_FLOW_WORKER.format(root=ROOT, argv=argv))
@@ -384,6 +384,37 @@ def test_bench_n_process_flow_end_to_end_on_the_checker(world, extra, oracle_lib
         assert "cpu_baseline" not in line
     rf = line["roofline"]
     assert rf["avg_launch_ms"] > 0 and rf["launches_timed"] >= 1 and "never" in rf["timing"]
+
+
+FULL_ONLY_KEYS = ("serialised", "step_only", "weak", "strong", "share_of_linear", "scaling_strong", "configs", "agent_path", "cpu_baseline",
+                  "cpu_config1")
+
+
+def test_bench_plain_line_is_the_headline_alone(oracle_lib, tmp_path):
+    """Without --full, `bench.py --gpus N` sets up, warms up, times its regions and prints the line: no arm beside the headline runs
+    (no other reading, no serialised or step-only loop, no CPU oracle), so the engine plays the pre-roll, settle, warm-up and timed
+    steps and nothing after them."""
+    import json
+    world, preroll, settle, warmup, steps, repeats = 2, 300, 3, 2, 6, 2
+    argv = ["--gpus", str(world), "--envs", "96", "--steps", str(steps), "--warmup", str(warmup), "--repeats", str(repeats),
+            "--preroll", str(preroll), "--settle", str(settle)]
+    script = tmp_path / "worker.py"
+    script.write_text(BENCH_FLOW_WORKER.format(root=ROOT, argv=argv))
+    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT="7", TBX_RDZV_DIR=str(tmp_path))
+    env.pop("TBX_RDZV_KEY", None)
+    procs = [subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
+                              stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, text=True) for r in range(world)]
+    out0 = procs[0].communicate(timeout=600)[0]
+    for p in procs:
+        assert p.wait(timeout=600) == 0, out0[-2000:]
+    lines = [ln for ln in out0.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out0[-2000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == world and line["steps"] == steps and line["warmup"] == warmup and line["repeats"]["n"] == repeats
+    assert line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f64" and line["value"] > 0
+    assert line["rccl"]["verified"] is True and line["roofline"]["launches_timed"] >= 1
+    assert not [k for k in FULL_ONLY_KEYS if k in line], sorted(line)
+    assert line["check"]["frames_played"] == preroll + settle + warmup + repeats * steps
 
 
 def _last_step_of_an_engine_alone(lib, n, frames_played, frame_after_step, verified_steps=0):
@@ -510,7 +541,8 @@ def test_bench_n_process_flow_under_torch_distributed_run(oracle_lib, tmp_path):
     import json
     pytest.importorskip("torch")
     world = 2
-    argv = ["--gpus", str(world), "--envs", "96", "--steps", "6", "--warmup", "2", "--repeats", "2", "--preroll", "300", "--cpu-seconds", "0.3"]
+    argv = ["--gpus", str(world), "--envs", "96", "--steps", "6", "--warmup", "2", "--repeats", "2", "--preroll", "300", "--cpu-seconds", "0.3",
+            "--full"]
     script = tmp_path / "worker.py"
     script.write_text(BENCH_FLOW_WORKER.format(root=ROOT, argv=argv))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TBX_RDZV_KEY", "MASTER_ADDR", "MASTER_PORT")}
@@ -777,7 +809,7 @@ def test_gpu_bench_n_process_flow_on_one_device_with_the_host_transport(launcher
     head = [sys.executable] if launcher == "own" else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                                                          "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
     p = subprocess.run(head + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gather", "host", "--one-device", "--envs", "4096",
-                               "--steps", "6", "--warmup", "2", "--repeats", "2", "--preroll", "300", "--settle", "4", "--cpu-seconds", "0.5"],
+                               "--steps", "6", "--warmup", "2", "--repeats", "2", "--preroll", "300", "--settle", "4", "--cpu-seconds", "0.5", "--full"],
                        capture_output=True, text=True, timeout=900, cwd="/tmp", env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -796,13 +828,14 @@ def test_gpu_bench_n_process_flow_on_one_device_with_the_host_transport(launcher
 
 
 @pytest.mark.gpu
-def test_gpu_bench_default_line_carries_every_arm():
-    """The driver's own N = 1 command (`bench.py --gpus 1 --steps 20 --warmup 5`; the CPU arm cut to a second here): ONE JSON line
-    whose roofline timing is consistent with the step it sits in, with BASELINE configs 2-5, the strong-scaling probe incl. the
-    policy loop, the agent path of every game in both observation forms, and the CPU oracle beside it."""
+def test_gpu_bench_full_line_carries_every_arm():
+    """The headline N = 1 command with --full (`bench.py --gpus 1 --steps 20 --warmup 5 --full`; the CPU arm cut to a second here):
+    ONE JSON line whose roofline timing is consistent with the step it sits in, with BASELINE configs 2-5, the strong-scaling probe incl.
+    the policy loop, the agent path of every game in both observation forms, and the CPU oracle beside it."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TBX_RDZV_KEY")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd="/tmp", env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -829,6 +862,32 @@ def test_gpu_bench_default_line_carries_every_arm():
         assert ap[game]["rolled_stack"]["value"] > 1e6 and ap[game]["plane_ring"]["value"] > 0.9 * ap[game]["rolled_stack"]["value"]
     assert j["cpu_baseline"]["value"] > 0 and j["cpu_baseline"]["kind"] == "port" and j["cpu_config1"]["step_only"] > 0
     assert j["check"]["mean_score"] > 0
+
+
+@pytest.mark.gpu
+def test_gpu_bench_plain_line_is_the_headline_alone(tmp_path):
+    """The headline N = 1 command without --full (`bench.py --gpus 1 --steps 20 --warmup 5`): ONE JSON line with the contract
+    fields and the roofline of the timed launches, none of the --full arms, and at most 30 s of the whole run -- from start to exit --
+    spent outside its warm-up and timed steps."""
+    import json
+    import time
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TBX_RDZV_KEY")}
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                       capture_output=True, text=True, timeout=900, cwd=str(tmp_path), env=env)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["metric"] == "env steps/sec (whole node), Breakout 64k-env batch" and j["unit"] == "env-steps/s" and j["dtype"] == "f64"
+    assert j["higher_is_better"] is True and j["n_gpus"] == 1 and j["steps"] == 20 and j["warmup"] == 5 and j["value"] > 1e7
+    assert abs(j["value"] - 65536 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    rf = j["roofline"]
+    assert rf["bound"] == "hbm" and 0.5 < rf["frac"] < 1.0 and rf["avg_launch_ms"] <= 1.01 * j["ms_per_step"]
+    assert not [k for k in FULL_ONLY_KEYS if k in j], sorted(j)
+    assert j["check"]["mean_score"] > 0
+    assert wall - 25 * j["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 def test_mixed_batch_segment_sizes(oracle_lib):
