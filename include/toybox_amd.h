@@ -79,8 +79,22 @@ extern "C" {
 #define TBX_BUF_DONE    1   /* uint8[N]  lives <= 0 after the last step (envs/atari/base.py:25-27,142)          */
 #define TBX_BUF_LIVES   2   /* int32[N]  (pre-reset value when auto-reset fired)                                */
 #define TBX_BUF_SCORE   3   /* int32[N]  (pre-reset value when auto-reset fired)                                */
-#define TBX_BUF_FRAME   4   /* uint8[N,H,W,C] last tbx_render_device() into the engine-owned frame buffer       */
+#define TBX_BUF_FRAME   4   /* uint8[N,H,W,C] the last frame rasterised into an engine-owned buffer -- see below   */
 #define TBX_BUF_PACKED  5   /* uint64[N] {reward:i32, done:u8, lives:u8, pad:u16} record for the multi-GPU gather */
+
+/* What TBX_BUF_FRAME names, and how many bytes tbx_device_buffer reports for it.
+ *   - After a call that rasterises every env into an engine-owned buffer -- tbx_render_device(out_dev = NULL),
+ *     tbx_render_step_synthetic(out_dev = NULL), tbx_step_begin with a frame, and the host-pointer tbx_render, which paints there and
+ *     copies out of it -- the id names the frame of that call, in that call's channel count.
+ *   - After tbx_rollout_synthetic it names the chunk's LAST frame (frame k - 1: the state before the chunk's last step), in whichever
+ *     form the chunk ran.
+ *   - Every other call leaves the id as it was: calls that rasterise into a caller's buffer (tbx_render_device / tbx_render_step_synthetic
+ *     with out_dev != NULL, tbx_render_env, tbx_step1_frame), steps, new games, state writes, edits.
+ *   - The size reported is that of the frame the id names, N * H * W * channels of the call that produced it -- never the capacity of
+ *     the allocation behind it (a gray frame after an RGBA one reports the gray size).  Before the first such call: NULL, 0 bytes.
+ * The address may change with every such call (pipelined mode, overlapped fused launches, chunks): ask again after each.
+ * TBX_BUF_ROLLOUT_FRAMES / TBX_BUF_ROLLOUT_PACKED keep the last chunk's k frames and k rows of records until the next chunk, whatever
+ * is called in between (rows that ARE a record ring: until that ring is opened again, K steps later). */
 
 /* RGBA colour, memory order r,g,b,a (interventions/core.py:179-187) */
 typedef struct tbx_color { uint8_t r, g, b, a; } tbx_color_t;
@@ -422,7 +436,7 @@ int tbx_get_scalars(tbx_engine* engine, int32_t* score_host, int32_t* lives_host
 
 /* Rasterise every env's current state: out[N][H][W][channels], channels 1 (gray), 3 (RGB), 4 (RGBA).
  * replaces Toybox.get_state / get_rgb_frame (envs/atari/base.py:109,164). */
-int tbx_render(tbx_engine* engine, uint8_t* out_host, int channels);
+int tbx_render(tbx_engine* engine, uint8_t* out_host, int channels);   /* (paints the engine-owned buffer: TBX_BUF_FRAME names this frame) */
 /* out_dev == NULL renders into the engine-owned TBX_BUF_FRAME buffer. */
 int tbx_render_device(tbx_engine* engine, uint8_t* out_dev, int channels, void* stream);
 /* The random-rollout loop body as ONE call: rasterise every env's CURRENT state into out_dev (NULL: TBX_BUF_FRAME) and step

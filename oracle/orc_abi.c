@@ -25,7 +25,8 @@ struct tbx_engine {
     uint8_t* done;
     uint64_t* packed;
     uint8_t* frame;
-    size_t frame_bytes;
+    size_t frame_bytes;   /* TBX_BUF_FRAME: the size of the frame the id names, N * H * W * channels */
+    size_t frame_cap;     /* ... and of the allocation behind it */
     int pending_action_error;
     int threads;
     char err[256];
@@ -363,7 +364,8 @@ int tbx_render_device(tbx_engine* e, uint8_t* out, int channels, void* stream)
     orc_frame_dims(e->game, &h, &w);
     if (!out) {
         size_t bytes = (size_t)e->n * h * w * channels;
-        if (e->frame_bytes < bytes) { free(e->frame); e->frame = (uint8_t*)malloc(bytes); e->frame_bytes = bytes; }
+        if (e->frame_cap < bytes) { free(e->frame); e->frame = (uint8_t*)malloc(bytes); e->frame_cap = bytes; }
+        e->frame_bytes = bytes;
         out = e->frame;
     }
     orc_render_batch(e->game, e->cfg, e->states, e->n, out, channels, e->threads);
@@ -417,10 +419,8 @@ int tbx_rollout_synthetic(tbx_engine* e, int channels, uint64_t seed, uint64_t t
     e->chunk_k = k; e->chunk_channels = channels;
     e->chunk_packed_base = ring ? ring_base : e->chunk_packed;
     e->chunk_stride = ring ? (size_t)e->gather_width : n;
-    /* TBX_BUF_FRAME: the chunk's last frame, as after the k-th single call into a caller's buffer it is whatever it was -- the HIP
-     * library names the last frame of the chunk; so does this one */
-    free(e->frame);
-    e->frame = (uint8_t*)malloc(fb);
+    /* TBX_BUF_FRAME: the chunk's last frame (include/toybox_amd.h), whichever way the chunk ran */
+    if (e->frame_cap < fb) { free(e->frame); e->frame = (uint8_t*)malloc(fb); e->frame_cap = fb; }
     memcpy(e->frame, e->chunk_frames + fb * (size_t)(k - 1), fb);
     e->frame_bytes = fb;
     return TBX_OK;
@@ -430,7 +430,11 @@ int tbx_render(tbx_engine* e, uint8_t* out, int channels)
 {
     if (!e) return TBX_E_INVALID;
     if (!out) return fail(e, TBX_E_INVALID, "output pointer is NULL");
-    return tbx_render_device(e, out, channels, NULL);
+    /* as the HIP library does it: into the engine-owned buffer, which TBX_BUF_FRAME then names, and copied out of it */
+    int rc = tbx_render_device(e, NULL, channels, NULL);
+    if (rc) return rc;
+    memcpy(out, e->frame, e->frame_bytes);
+    return TBX_OK;
 }
 
 int tbx_render_env(tbx_engine* e, int env, uint8_t* out, int channels)
@@ -1695,8 +1699,9 @@ int tbx_step_begin(tbx_engine* e, const int32_t* actions, uint32_t flags, const 
     if (out->lives) memcpy(out->lives, e->lives, n * 4);
     if (out->score) memcpy(out->score, e->score, n * 4);
     if (out->frame) {
-        rc = tbx_render_device(e, out->frame, out->channels, NULL);
+        rc = tbx_render_device(e, NULL, out->channels, NULL);      /* (the engine-owned buffer, then the copy: TBX_BUF_FRAME names it) */
         if (rc) return rc;
+        memcpy(out->frame, e->frame, e->frame_bytes);
     }
     e->host_pending = 1;
     return TBX_OK;

@@ -148,19 +148,38 @@ def amidar_edit_last_lives(js, lives, jump_timer, perimeter_from_start):
     return js
 
 
-def read_buffer(engine, which, shape, dtype=np.uint8):
-    """host copy of an engine-owned buffer (TBX_BUF_*): device memory of the HIP library, plain memory of the CPU checker"""
+def read_buffer(engine, which, shape, dtype=np.uint8, stream=None):
+    """host copy of an engine-owned buffer (TBX_BUF_*): device memory of the HIP library, plain memory of the CPU checker.
+    stream (a toybox_amd.hip.Stream, the one the producing call named): the copy is queued on it right behind tbx_device_buffer and
+    only that stream is waited for -- the reader of include/toybox_amd.h's contract, which leaves an overlapped form of the engine
+    in force; without one the whole engine is synchronised first (tbx_sync, which also joins every internal stream)."""
     import ctypes as C
     ptr, nbytes = engine.device_buffer(which)
     out = np.empty(shape, dtype)
     assert out.nbytes == nbytes, (out.nbytes, nbytes)
     if hasattr(engine._lib, "orc_splitmix64"):
         C.memmove(out.ctypes.data, ptr, nbytes)
+    elif stream is not None:
+        from toybox_amd import hip
+        hip.check(hip.runtime().hipMemcpyAsync(C.c_void_p(out.ctypes.data), C.c_void_p(ptr), C.c_size_t(nbytes), C.c_int(2), stream.handle),
+                  "hipMemcpyAsync D2H")
+        stream.synchronize()
     else:
         from toybox_amd import hip
         engine.sync()
         hip.memcpy_dtoh(out, ptr, nbytes)
     return out
+
+
+# ---------------------------------------------------------------- what the engines choose by themselves (include/toybox_amd.h)
+# TBX_OPT_PIPELINE = 1 resolves to this mode for (game, envs) without a gather; TBX_OPT_ROLLOUT_CHUNKS = 0 makes a chunk of
+# tbx_rollout_synthetic(channels = 3) run as overlapped launches (1) or as single calls (0), (without a gather, under a K-step ring).
+# tests/test_gpu_paths.py checks both tables against TBX_OPT_*_ACTIVE; tests/test_buffer_contract.py takes its large sizes from them.
+ENGINES_CHOICE_PIPELINE = {("breakout", 1024): 0, ("breakout", 4096): 3, ("breakout", 16384): 0, ("space_invaders", 1024): 3,
+                           ("space_invaders", 16384): 0, ("amidar", 4096): 0, ("gridworld", 4096): 0}
+ENGINES_CHOICE_ROLLOUT_CHUNKS = {("breakout", 1024): (1, 0), ("breakout", 2048): (1, 1), ("breakout", 8192): (1, 1), ("breakout", 32768): (1, 1),
+                                 ("breakout", 40000): (0, 0), ("space_invaders", 4096): (1, 1), ("space_invaders", 8192): (1, 1),
+                                 ("space_invaders", 12000): (0, 0), ("amidar", 4096): (0, 0), ("gridworld", 4096): (0, 0)}
 
 
 def stack_from_ring(ring, head):

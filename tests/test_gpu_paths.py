@@ -343,7 +343,8 @@ def test_every_device_buffer_id(lib):
             continue
         p, b = e.device_buffer(declared[name])
         assert p and b == want[name], (name, p, b)
-        if name != "BUF_FRAME":                              # (after a chunk TBX_BUF_FRAME may name the chunk's last frame)
+        if name != "BUF_FRAME":                              # (after a chunk TBX_BUF_FRAME names the chunk's last frame, inside the chunk's
+                                                             # frames: what it holds after which call is tests/test_buffer_contract.py's)
             seen.add(p)
     assert len(seen) == len(ALL_BUFS) - 2, "two buffer ids share an address"
     e.agent_init(skip=2, out_h=42, out_w=60, stack=3, new_plane=2)
@@ -1007,9 +1008,11 @@ def test_rollout_synthetic_call_contract(game, lib):
         frames = read_buffer(a, _abi.BUF_ROLLOUT_FRAMES, (k, n, H, W, 3))
         packed = read_buffer(a, _abi.BUF_ROLLOUT_PACKED, (k, n), np.uint64)
         for j in range(k):
-            assert np.array_equal(frames[j], b.render(3)), (game, c, j)
+            last = b.render(3)                                   # (after the loop: the state before the chunk's last step)
+            assert np.array_equal(frames[j], last), (game, c, j)
             b.step_synthetic(1337, t + j, auto_reset=True)
             assert np.array_equal(packed[j], read_buffer(b, _abi.BUF_PACKED, (n,), np.uint64)), (game, c, j)
+        assert np.array_equal(read_buffer(a, _abi.BUF_FRAME, (n, H, W, 3)), last), (game, c, "BUF_FRAME")   # the chunk's last frame, in either form
         for which, dt in ((_abi.BUF_REWARD, np.int32), (_abi.BUF_LIVES, np.int32), (_abi.BUF_SCORE, np.int32), (_abi.BUF_DONE, np.uint8), (_abi.BUF_PACKED, np.uint64)):
             assert np.array_equal(read_buffer(a, which, (n,), dt), read_buffer(b, which, (n,), dt)), (game, c, which)
         t += k
@@ -1222,8 +1225,7 @@ def test_options_are_validated_and_reported(hip_lib, oracle_lib):
 def test_engines_choice_of_pipelined_mode(hip_lib):
     """TBX_OPT_PIPELINE = 1: overlapped launches (3) for small Breakout / SpaceInvaders batches while no per-step gather is
     initialised, stream order (0) otherwise -- what include/toybox_amd.h says, read back through TBX_OPT_PIPELINE_ACTIVE."""
-    want = {("breakout", 1024): 0, ("breakout", 4096): 3, ("breakout", 16384): 0, ("space_invaders", 1024): 3,
-            ("space_invaders", 16384): 0, ("amidar", 4096): 0, ("gridworld", 4096): 0}
+    from support import ENGINES_CHOICE_PIPELINE as want
     for (game, n), mode in want.items():
         e = Engine(game, n, lib=hip_lib)
         assert e.get_option(_abi.OPT_PIPELINE_ACTIVE) == 0                     # the option is off by default
@@ -1245,9 +1247,7 @@ def test_engines_choice_of_rollout_chunks(hip_lib):
     rollout_auto), read back through TBX_OPT_ROLLOUT_CHUNKS_ACTIVE: Breakout chunks up to 32 768 envs, under a K-step
     record ring only from 2 048; SpaceInvaders up to 8 192; never with a collective per step, never for Amidar / GridWorld; 1 / 3 / 4
     switch them on wherever the engine can, 2 off."""
-    want = {("breakout", 1024): (1, 0), ("breakout", 2048): (1, 1), ("breakout", 8192): (1, 1), ("breakout", 32768): (1, 1), ("breakout", 40000): (0, 0),
-            ("space_invaders", 4096): (1, 1), ("space_invaders", 8192): (1, 1), ("space_invaders", 12000): (0, 0), ("amidar", 4096): (0, 0),
-            ("gridworld", 4096): (0, 0)}
+    from support import ENGINES_CHOICE_ROLLOUT_CHUNKS as want
     for (game, n), (plain, ring) in want.items():
         e = Engine(game, n, lib=hip_lib)
         assert e.get_option(_abi.OPT_ROLLOUT_CHUNKS_ACTIVE) == plain, (game, n)

@@ -38,6 +38,19 @@ void tbx_set_out_parity(tbx_engine* e, int p)
     if (e->ops) e->ops->rebind_outputs(e);
 }
 
+// TBX_BUF_PACKED leaves a chunk's record array (tbx_use_stream): the records it names are copied into the current output set on s,
+// which the caller has ordered behind the chunk's step launch, and the step kernels write there again.  TBX_BUF_ROLLOUT_PACKED keeps
+// all k rows of the chunk.
+hipError_t tbx_packed_leaves_chunk(tbx_engine* e, hipStream_t s)
+{
+    uint64_t* own = e->outs[e->out_par].packed;
+    hipError_t r = hipMemcpyAsync(own, e->packed, sizeof(uint64_t) * (size_t)e->n, hipMemcpyDeviceToDevice, s);
+    if (r != hipSuccess) return r;
+    e->packed = own;
+    if (e->ops) e->ops->rebind_outputs(e);
+    return hipSuccess;
+}
+
 namespace {
 
 int hip_fail(tbx_engine* e, const char* what, hipError_t err)
@@ -210,7 +223,7 @@ int ensure_frame(tbx_engine* e, size_t bytes)
         e->frame_own_bytes = bytes;
     }
     e->frame = e->frame_own;
-    e->frame_bytes = e->frame_own_bytes;
+    e->frame_bytes = bytes;                                    // TBX_BUF_FRAME: the size of the frame it names, not of the allocation
     return TBX_OK;
 }
 
@@ -734,10 +747,10 @@ static int pipe_render(tbx_engine* e, uint8_t* out_dev, int channels, hipStream_
         EHIP(hipStreamWaitEvent(user, p.render_ev[rp], 0));
         p.frame_par = rp;
         e->frame = p.frame[rp];
-        e->frame_bytes = p.frame_bytes[rp];
+        e->frame_bytes = bytes;
     } else if (out_dev == e->frame_own) {
         e->frame = e->frame_own;
-        e->frame_bytes = e->frame_own_bytes;
+        e->frame_bytes = bytes;
     }
     e->last_stream = user;
     e->has_last = true;
@@ -850,7 +863,7 @@ static int fused_overlapped(tbx_engine* e, int channels, const ActionSource& src
     p.user_waits[wp] = false;
     if (OVL_DIAG(diag, 16)) { EHIP(hipStreamWaitEvent(user, p.launch_ev[wp], 0)); p.user_waits[wp] = true; }    // (DIAG: the eager join of the first build)
     e->frame = p.frame[fb];
-    e->frame_bytes = p.frame_bytes[fb];
+    e->frame_bytes = bytes;
     e->step_carries_order_ev = false;
     e->last_stream = user;
     e->has_last = true;
@@ -1197,8 +1210,6 @@ int tbx_step_begin(tbx_engine* e, const int32_t* actions_host, uint32_t flags, c
         if (rc) return rc;
         rc = e->ops->render(e, e->frame_own, out->channels, 0, e->n, e->stream);
         if (rc) return rc;
-        e->frame = e->frame_own;
-        e->frame_bytes = e->frame_own_bytes;
         EHIP(hipMemcpyAsync(out->frame, e->frame_own, bytes, hipMemcpyDeviceToHost, e->stream));
     }
     e->host_out = *out;
@@ -1517,6 +1528,8 @@ int tbx_rollout_synthetic(tbx_engine* e, int channels, uint64_t action_seed, uin
     p.chunk_cur = 0; p.chunk_k = k; p.chunk_channels = channels;
     p.chunk_packed_base = e->gather_ring ? ring_base : p.chunk_packed[0];
     p.chunk_packed_stride = e->gather_ring ? (size_t)e->gather_ring_width : (size_t)e->n;
+    e->frame = p.chunk_frames[0] + (size_t)(k - 1) * fb;        // TBX_BUF_FRAME: the chunk's last frame, as in rollout_chunked
+    e->frame_bytes = fb;
     return TBX_OK;
 }
 

@@ -441,8 +441,9 @@ struct tbx_engine {
     tbx_step_host_out_t host_out{}; // where they go
     uint8_t* frame_own = nullptr;   // engine-owned frame buffer (lazy)
     size_t frame_own_bytes = 0;
-    uint8_t* frame = nullptr;       // what TBX_BUF_FRAME reports: frame_own, or in pipelined mode the buffer the last render wrote
-    size_t frame_bytes = 0;
+    uint8_t* frame = nullptr;       // what TBX_BUF_FRAME reports: frame_own, in the overlapped forms the buffer the last launch wrote,
+                                    // after tbx_rollout_synthetic the last frame of the chunk's frames (include/toybox_amd.h)
+    size_t frame_bytes = 0;         // ... and the size of that frame, N * H * W * channels of the call that produced it
     double* edit_args = nullptr;    // [N][n_args] per-env arguments of tbx_edit / tbx_reduce (host-pointer forms)
     size_t edit_args_bytes = 0;
     double* reduce_out = nullptr;   // [N][width] result staging of tbx_reduce
@@ -511,6 +512,8 @@ inline hipEvent_t tbx_step_order_event(tbx_engine* e)
             hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, s, __VA_ARGS__);                                             \
     } while (0)
 
+hipError_t tbx_packed_leaves_chunk(tbx_engine* e, hipStream_t s);   // engine.hip: TBX_BUF_PACKED out of a chunk's record array
+
 // Every entry point that queues work names the stream it is about to use.  When that differs from the stream the previous
 // entry point used (the "_device" forms run on the caller's stream -- including the NULL stream, which does not order itself
 // against the engine's non-blocking stream -- the host-pointer forms on the engine's own), the new stream first waits for an
@@ -557,6 +560,12 @@ inline hipError_t tbx_use_stream(tbx_engine* e, hipStream_t s)
                         if (r != hipSuccess) return r;
                     }
             }
+    }
+    // after a rollout chunk without a record ring TBX_BUF_PACKED names the LAST ROW of the chunk's records: a step of any other
+    // form would write its records there, so the row moves into the engine's own array first (behind the joins above)
+    if (!e->gather_ring && e->packed != e->outs[e->out_par].packed) {
+        r = tbx_packed_leaves_chunk(e, s);
+        if (r != hipSuccess) return r;
     }
     e->step_carries_order_ev = false;          // whatever this call queues moves the tail
     e->pipe.active = false;
