@@ -685,7 +685,10 @@ int tbx_agent_reset(tbx_engine* engine, uint8_t* obs_host);
 /* one agent step with host pointers (synchronous); any output pointer may be NULL */
 int tbx_agent_step(tbx_engine* engine, const int32_t* ale_actions_host, float* reward_host, uint8_t* done_host, uint8_t* obs_host);
 /* device-resident forms: actions in HBM, or generated on the device like tbx_step_synthetic with t = agent step index
- * (every sub-frame of an agent step repeats the same action); results in TBX_BUF_AGENT_* */
+ * (every sub-frame of an agent step repeats the same action); results in TBX_BUF_AGENT_*.  Both return before the step has
+ * run: their return code speaks of the call alone (TBX_E_INVALID before tbx_agent_init or for a NULL action pointer), and what the
+ * synchronous tbx_agent_step returns about the step itself -- TBX_E_ACTION, TBX_E_NEEDS_RESET -- arrives with the next tbx_sync,
+ * once for all steps queued since the last one (see there for which code wins). */
 int tbx_agent_step_device(tbx_engine* engine, const int32_t* ale_actions_dev, void* stream);
 int tbx_agent_step_synthetic(tbx_engine* engine, uint64_t action_seed, uint64_t t, uint64_t env_offset, void* stream);
 
@@ -898,7 +901,14 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
 #define TBX_OPT_ROLLOUT_CHUNKS_ACTIVE 104
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
-/* Block until all work queued by this engine has finished; reports a pending TBX_E_ACTION. */
+/* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could
+ * not return themselves: the device keeps ONE error word for all of them, read and cleared here (and by the synchronous forms,
+ * which report it as their own return code).  In order of precedence, one code per call:
+ *   TBX_E_NO_DEVICE    an overlapped fused launch timed out waiting for the launch before it (TBX_OPT_FUSED_OVERLAP);
+ *   TBX_E_NEEDS_RESET  an agent step ran on an env that needed a reset (tbx_agent_step_device / _synthetic);
+ *   TBX_E_ACTION       an illegal ALE action id was seen (any "_dev" step) and played as NOOP.
+ * So when the steps since the last report had both an illegal id and an env that needed a reset, TBX_E_NEEDS_RESET is what
+ * comes back, and the illegal id is not reported again later.  Every step has been carried out either way. */
 int tbx_sync(tbx_engine* engine);
 
 #ifdef __cplusplus

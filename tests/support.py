@@ -171,6 +171,22 @@ def read_buffer(engine, which, shape, dtype=np.uint8, stream=None):
     return out
 
 
+def queue_read_buffer(engine, which, out, stream=None):
+    """read_buffer without the wait: the copy of an engine-owned buffer (TBX_BUF_*) into `out` (a C-contiguous array of exactly
+    the buffer's size; page-locked, or the copy is not asynchronous) is queued on `stream`, the one the producing call named,
+    and the call returns -- the reader include/toybox_amd.h allows between a call and the next one on the handle.  `out` holds
+    the result once the stream has been synchronised.  The CPU checker has nothing in flight: there the copy happens here."""
+    import ctypes as C
+    ptr, nbytes = engine.device_buffer(which)
+    assert out.flags["C_CONTIGUOUS"] and out.nbytes == nbytes, (which, out.nbytes, nbytes)
+    if hasattr(engine._lib, "orc_splitmix64"):
+        C.memmove(out.ctypes.data, ptr, nbytes)
+        return
+    from toybox_amd import hip
+    hip.check(hip.runtime().hipMemcpyAsync(C.c_void_p(out.ctypes.data), C.c_void_p(ptr), C.c_size_t(nbytes), C.c_int(2),
+                                           stream.handle if stream is not None else None), "hipMemcpyAsync D2H")
+
+
 # ---------------------------------------------------------------- what the engines choose by themselves (include/toybox_amd.h)
 # TBX_OPT_PIPELINE = 1 resolves to this mode for (game, envs) without a gather; TBX_OPT_ROLLOUT_CHUNKS = 0 makes a chunk of
 # tbx_rollout_synthetic(channels = 3) run as overlapped launches (1) or as single calls (0), (without a gather, under a K-step ring).
@@ -222,6 +238,54 @@ def device_frames(ptr, frame_bytes):
     def fetch(lo, hi, out):
         from toybox_amd import hip
         hip.memcpy_dtoh(out, ptr + lo * frame_bytes, (hi - lo) * frame_bytes)
+    return fetch
+
+
+def host_frames(ptr, frame_bytes):
+    """source for FrameChecker.compare over plain memory (a buffer of the CPU checker): frame f lies at ptr + f * frame_bytes"""
+    def fetch(lo, hi, out):
+        import ctypes as C
+        C.memmove(out.ctypes.data, ptr + lo * frame_bytes, (hi - lo) * frame_bytes)
+    return fetch
+
+
+def engine_is_oracle(engine):
+    return hasattr(engine._lib, "orc_splitmix64")
+
+
+def agent_stack_frames(engine):
+    """source for FrameChecker.compare over shape (out_h, out_w, stack): frame f = the observation stack of env f as the engine
+    holds it right now, whichever form it keeps -- TBX_BUF_AGENT_OBS as it lies there, or (new_plane = 2) TBX_BUF_AGENT_RING read
+    through tbx_agent_ring_head the way include/toybox_amd.h states it (stack_from_ring, slice by slice: channel c of env i is
+    ring[(head + 1 + c) % stack][i]).  The caller has synchronised whatever wrote the buffers."""
+    import ctypes as C
+    from toybox_amd import _abi
+    n, oh, ow, stack = engine._agent_shape
+    px = oh * ow
+    if engine_is_oracle(engine):
+        def copy(dst, src, nbytes):
+            C.memmove(dst.ctypes.data, src, nbytes)
+    else:
+        from toybox_amd import hip
+        copy = hip.memcpy_dtoh
+    if not engine._agent_ring:
+        ptr, nbytes = engine.device_buffer(_abi.BUF_AGENT_OBS)
+        assert nbytes == n * px * stack
+        return lambda lo, hi, out: copy(out, ptr + lo * px * stack, (hi - lo) * px * stack)
+    ptr, nbytes = engine.device_buffer(_abi.BUF_AGENT_RING)
+    assert nbytes == n * px * stack
+    head = engine.agent_ring_head()
+    keep = {}
+
+    def fetch(lo, hi, out):
+        m = hi - lo
+        if "plane" not in keep or keep["plane"].shape[0] < m:
+            keep["plane"] = engine.host_array((m, px))
+        plane = keep["plane"][:m]
+        channels = out[:m].reshape(m, px, stack)
+        for c in range(stack):
+            copy(plane, ptr + (((head + 1 + c) % stack) * n + lo) * px, m * px)
+            channels[:, :, c] = plane
     return fetch
 
 

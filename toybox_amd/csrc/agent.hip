@@ -321,6 +321,7 @@ AgentResetArgs reset_args(tbx_engine* e)
     r.was_real_done = a.was_real_done; r.needs_reset = a.needs_reset;
     r.ep_done = a.ep_done; r.ep_ret_out = a.ep_ret_out; r.ep_len_out = a.ep_len_out;
     r.mode = a.mode; r.buf_valid = a.buf_valid; r.err_flag = e->err_flag;
+    r.keep_obs = (e->ops->agent_fused() && !a.force_generic) ? 1 : 0;   // (the generic path's renders know slots A / B only)
     return r;
 }
 

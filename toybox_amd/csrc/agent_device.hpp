@@ -14,7 +14,9 @@ struct AgentTaps {          // area-resize taps of one output row / column
 struct AgentWarpArgs {
     const uint8_t* zero;       // [N] the env reported done in this agent step: VecFrameStack zeroes its older slots
     const uint8_t* mode;       // [N] 1: the observation is the raw frame of the live state (what a reset without FireResetEnv
-                               //     returns after a new game); 0: the max over the two-frame buffer (MaxAndSkipEnv.step)
+                               //     returns after a new game); 0: the max over the two-frame buffer (MaxAndSkipEnv.step);
+                               //     2: the max over the KEPT copy of the buffer (AgentResetProc::run: FireResetEnv.reset returns
+                               //     what step(2) returned although a no-op step rewrote the buffer after it)
     const uint8_t* valid;      // [N] bit 0 / 1: buffer slot A / B has been written since construction (else a zero frame)
     const AgentTaps* tx;       // [out_w] column taps
     uint8_t* obs;              // [N][out_h][out_w][stack]
@@ -44,6 +46,7 @@ struct ObsSel {
     bool none;    // both buffer slots still hold np.zeros: the observation is black
     bool two;     // max(slot A, slot B)
     int single;   // !two: the one source -- 0 live state, 1 slot A, 2 slot B
+    bool keep;    // slots A / B are read from their kept copies (mode 2)
 };
 
 __device__ __forceinline__ ObsSel agent_obs_sel(const AgentWarpArgs& a, int env)
@@ -56,6 +59,7 @@ __device__ __forceinline__ ObsSel agent_obs_sel(const AgentWarpArgs& a, int env)
     s.none = !raw && (valid & 3u) == 0u;
     s.two = !raw && (valid & 3u) == 3u;
     s.single = raw ? 0 : (valid & 2u) ? 2 : 1;
+    s.keep = !raw && (mode & 2u) != 0;
     return s;
 }
 
@@ -252,6 +256,7 @@ struct AgentResetArgs {
     float* ep_ret_out;
     int32_t* ep_len_out;
     uint8_t *mode, *buf_valid;  // [N] see AgentWarpArgs
+    int keep_obs;               // the observation kernel in use reads kept buffer copies (mode 2): Env::keep() may make one
     uint32_t* err_flag;         // bit 1: an env was stepped although Monitor.needs_reset (TBX_E_NEEDS_RESET)
 };
 
@@ -272,20 +277,22 @@ __device__ __forceinline__ AgentMonitor agent_monitor_load(const AgentResetArgs&
 }
 
 // (one lane / thread per env calls this)
-__device__ __forceinline__ void agent_monitor_store(const AgentResetArgs& r, int env, const AgentMonitor& m, uint32_t valid, bool obs_raw)
+__device__ __forceinline__ void agent_monitor_store(const AgentResetArgs& r, int env, const AgentMonitor& m, uint32_t valid, bool obs_raw,
+                                                    bool obs_keep = false)
 {
     r.ep_ret[env] = m.ep_ret; r.ep_len[env] = m.ep_len; r.ep_index[env] = m.ep_index; r.prev_lives[env] = m.prev_lives;
     r.was_real_done[env] = m.was_real_done ? 1 : 0; r.needs_reset[env] = m.needs_reset ? 1 : 0;
     if (m.emitted) { r.ep_done[env] = 1; r.ep_ret_out[env] = (float)m.out_ret; r.ep_len_out[env] = m.out_len; }
     if (m.stale) atomicOr(r.err_flag, 2u);
     r.buf_valid[env] = (uint8_t)valid;
-    r.mode[env] = obs_raw ? 1 : 0;
+    r.mode[env] = obs_raw ? 1 : obs_keep ? 2 : 0;
 }
 
 // reset() of one env's wrapper stack, class by class (baselines/baselines/common/atari_wrappers.py, bench/monitor.py):
 //   FireResetEnv.reset :144-152 -> EpisodicLifeEnv.reset / .step :166-191 -> Monitor.reset / .step (monitor.py:36-76)
 //   -> MaxAndSkipEnv.step :201-216 / .reset :218-219 -> NoopResetEnv.reset :117-132 -> ToyboxBaseEnv.step / .reset
-// run in-kernel for one env.  Env provides step(buttons), new_game(), lives(), score(), snapshot(slot); every call is
+// run in-kernel for one env.  Env provides step(buttons), new_game(), lives(), score(), snapshot(slot), keep() (copy both buffer
+// slots aside for the observation kernel and return true, or return false: the game has no kept copies); every call is
 // wave-uniform for wave-per-env games.  `prev` is ToyboxBaseEnv.score, `valid` the written slots of the frame buffer,
 // `obs_raw` what the last wrapper call returned: a raw frame of the live state (true) or the buffer max (false).
 template <class Env>
@@ -298,6 +305,7 @@ struct AgentResetProc {
     uint32_t valid;
     int32_t noop_override;
     bool obs_raw;
+    bool obs_keep = false;      // the observation is the max over the kept copy of the buffer (Env::keep)
 
     __device__ __forceinline__ bool base_step(uint32_t buttons, int& reward)   // ToyboxBaseEnv.step
     {
@@ -378,7 +386,12 @@ struct AgentResetProc {
         if (r.fire_reset) {
             if (episodic_step(r.fire_buttons)) episodic_reset();
             const bool d = episodic_step(r.third_buttons);
-            if (d) episodic_reset();
+            if (d) {
+                // only a life went: the reset is a no-op STEP, which rewrites the frame buffer -- but the observation stays the
+                // one step(2) returned (atari_wrappers.py:149-152), so the buffer as step(2) left it is kept for the kernel
+                if (r.episodic_life && !m.was_real_done && r.keep_obs) obs_keep = env.keep();
+                episodic_reset();
+            }
             obs_raw = false;                     // the observation is the one step(2) returned, whatever followed
         }
     }

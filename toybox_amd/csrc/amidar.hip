@@ -1269,14 +1269,23 @@ struct AmiAgentEnv {
     const AmiDev& slot_a;
     const AmiDev& slot_b;
     int env;
+    const AmiDev& keep_a;
+    const AmiDev& keep_b;
     __device__ __forceinline__ void snapshot(int slot) { ami_store(slot ? slot_b : slot_a, env, lane, s); }
+    __device__ __forceinline__ bool keep()                     // both buffer slots of this env aside, for the observation kernel (mode 2)
+    {
+        AmiRegs t;
+        ami_load(slot_a, env, lane, t); ami_store(keep_a, env, lane, t);
+        ami_load(slot_b, env, lane, t); ami_store(keep_b, env, lane, t);
+        return true;
+    }
     __device__ __forceinline__ void step(uint32_t buttons) { ami_step(c, lane, buttons, s); }
     __device__ __forceinline__ void new_game() { ami_new_game(c, lane, sim, s); }
     __device__ __forceinline__ int lives() const { return wave_uniform(s.f[A_LIVES]); }
     __device__ __forceinline__ int score() const { return wave_uniform(s.f[A_SCORE]); }
 };
 
-__global__ __launch_bounds__(TBX_BLOCK) void ami_agent_reset_kernel(AmiDev d, AmiDev slot_a, AmiDev slot_b, AgentResetArgs r)
+__global__ __launch_bounds__(TBX_BLOCK) void ami_agent_reset_kernel(AmiDev d, AmiDev slot_a, AmiDev slot_b, AmiDev keep_a, AmiDev keep_b, AgentResetArgs r)
 {
     const int lane = threadIdx.x & 63;
     // a persistent grid walks the compact list of flagged envs (or every env when there is no list)
@@ -1291,7 +1300,7 @@ __global__ __launch_bounds__(TBX_BLOCK) void ami_agent_reset_kernel(AmiDev d, Am
         Rng sim;
         sim.s0 = d.sim_rng[env]; sim.s1 = d.sim_rng[N + env];
         AgentMonitor m = agent_monitor_load(r, env);
-        AmiAgentEnv ops{*d.tab, lane, s, sim, slot_a, slot_b, env};
+        AmiAgentEnv ops{*d.tab, lane, s, sim, slot_a, slot_b, env, keep_a, keep_b};
         AgentResetProc<AmiAgentEnv> proc{ops, r, m, r.env_offset + (uint64_t)env, wave_uniform(d.prev_score[env]),
                                          (uint32_t)wave_uniform((int)r.buf_valid[env]), r.noop_override ? wave_uniform(r.noop_override[env]) : 0, false};
         proc.run();
@@ -1299,7 +1308,7 @@ __global__ __launch_bounds__(TBX_BLOCK) void ami_agent_reset_kernel(AmiDev d, Am
         if (lane == 0) {
             d.sim_rng[env] = sim.s0; d.sim_rng[N + env] = sim.s1;
             d.prev_score[env] = proc.prev;
-            agent_monitor_store(r, env, m, proc.valid, proc.obs_raw);
+            agent_monitor_store(r, env, m, proc.valid, proc.obs_raw, proc.obs_keep);
         }
     }
 }
@@ -1662,7 +1671,7 @@ template <int S>
 // the depth-4 instantiation asked for 99-101 VGPRs -- four waves -- and the agent step at 65 536 envs lost 3-7 % against round 4;
 // at 96 VGPRs it spills 16-52 bytes per lane and runs 3.5 % AHEAD of round 4 (same box: Amidar 1.848 / 1.987 / 1.911 ms pinned /
 // unpinned / round 4, GridWorld 1.053 / 1.156 / 1.091).
-__global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(5))) void ami_agent_warp_kernel(AmiDev dLive, AmiDev dA, AmiDev dB, AgentWarpArgs a, int n)
+__global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(5))) void ami_agent_warp_kernel(AmiDev dLive, AmiDev dA, AmiDev dB, AmiDev dKA, AmiDev dKB, AgentWarpArgs a, int n)
 {
     __shared__ AgentFusedLds<AmiGrayPainter> lds[TBX_WAVES_PER_BLOCK];
     const int lane = threadIdx.x & 63;
@@ -1670,7 +1679,9 @@ __global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(5))) 
     const int env = wave_uniform(a.first + blockIdx.x * TBX_WAVES_PER_BLOCK + wave);
     if (env >= a.end) return;
     AmiGrayPainter pa, pb;
-    agent_fused_wave<S, AmiGrayPainter>(pa, pb, dLive, dA, dB, a, env, lane, lds[wave]);
+    // (mode 2: the buffer as FireResetEnv.reset's step(2) left it, kept aside before a no-op step rewrote slots A / B)
+    const bool kept = (__builtin_amdgcn_readfirstlane((int)a.mode[env]) & 2) != 0;
+    agent_fused_wave<S, AmiGrayPainter>(pa, pb, dLive, kept ? dKA : dA, kept ? dKB : dB, a, env, lane, lds[wave]);
 }
 
 // ------------------------------------------------------------------ state pack / unpack, scalars
@@ -2040,6 +2051,8 @@ struct AmiOps : GameOps {
         hipFree(d.rng); hipFree(d.sc); hipFree(d.tiles); hipFree(d.boxes); hipFree(d.movers); hipFree(d.mh); hipFree(tab_dev);
         hipFree(dA.rng); hipFree(dA.sc); hipFree(dA.tiles); hipFree(dA.boxes); hipFree(dA.movers); hipFree(dA.mh);
         hipFree(dB.rng); hipFree(dB.sc); hipFree(dB.tiles); hipFree(dB.boxes); hipFree(dB.movers); hipFree(dB.mh);
+        hipFree(dKA.rng); hipFree(dKA.sc); hipFree(dKA.tiles); hipFree(dKA.boxes); hipFree(dKA.movers); hipFree(dKA.mh);
+        hipFree(dKB.rng); hipFree(dKB.sc); hipFree(dKB.tiles); hipFree(dKB.boxes); hipFree(dKB.movers); hipFree(dKB.mh);
     }
 
     int get_config(tbx_engine*, void* pod) override { memcpy(pod, &cfg, sizeof cfg); return TBX_OK; }
@@ -2089,7 +2102,7 @@ struct AmiOps : GameOps {
     {
         int first = 0, count = e->n;
         if (src.single_env >= 0) { first = src.single_env; count = 1; }
-        dA.tab = dB.tab = d.tab;
+        dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         // TBX_OPT_STEP_FORM: 2 = never, 1 = always, 0 = by batch size.  The thread form is one wave per 64 envs with a long
         // serial path per thread (~45 us whatever the batch), the wave form scales with the batch.  Measured in the step + render
         // loop (scripts/pipeline_sweep.py amidar, PS_STEP_FORM=1|2, one box): ms per step thread / wave form 0.246 / 0.215 at
@@ -2128,6 +2141,7 @@ struct AmiOps : GameOps {
 
     // ---- agent layer: MaxAndSkipEnv's two-frame buffer is two snapshots of the dynamic SoA state per env
     AmiDev dA{}, dB{};
+    AmiDev dKA{}, dKB{};     // copies of the two slots for the observation of one agent step (AgentResetProc::run, mode 2)
     bool agent_fused() const override { return true; }
     bool multi_frame_step() const override { return true; }
     bool agent_reset_supported() const override { return true; }
@@ -2150,20 +2164,22 @@ struct AmiOps : GameOps {
     int agent_prepare(tbx_engine* e) override
     {
         int rc = alloc_slot(e, dA);
-        if (rc) return rc;
-        return alloc_slot(e, dB);
+        if (!rc) rc = alloc_slot(e, dB);
+        if (!rc) rc = alloc_slot(e, dKA);
+        if (!rc) rc = alloc_slot(e, dKB);
+        return rc;
     }
 
     int agent_warp(tbx_engine* e, const AgentWarpArgs& a, hipStream_t s) override
     {
-        dA.tab = dB.tab = d.tab;
+        dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
         switch (a.obs ? a.stack : 0) {
-        case 0: hipLaunchKernelGGL(ami_agent_warp_kernel<0>, grid, block, 0, s, d, dA, dB, a, e->n); break;      // the plane ring (new_plane = 2), any depth
-        case 1: hipLaunchKernelGGL(ami_agent_warp_kernel<1>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        case 2: hipLaunchKernelGGL(ami_agent_warp_kernel<2>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        case 3: hipLaunchKernelGGL(ami_agent_warp_kernel<3>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        default: hipLaunchKernelGGL(ami_agent_warp_kernel<4>, grid, block, 0, s, d, dA, dB, a, e->n); break;
+        case 0: hipLaunchKernelGGL(ami_agent_warp_kernel<0>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;      // the plane ring (new_plane = 2), any depth
+        case 1: hipLaunchKernelGGL(ami_agent_warp_kernel<1>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
+        case 2: hipLaunchKernelGGL(ami_agent_warp_kernel<2>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
+        case 3: hipLaunchKernelGGL(ami_agent_warp_kernel<3>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
+        default: hipLaunchKernelGGL(ami_agent_warp_kernel<4>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
         }
         TBX_HIP(hipGetLastError());
         return TBX_OK;
@@ -2171,16 +2187,16 @@ struct AmiOps : GameOps {
 
     int agent_reset_envs(tbx_engine* e, const AgentResetArgs& r, hipStream_t s) override
     {
-        dA.tab = dB.tab = d.tab;
+        dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         const dim3 grid = r.list ? dim3(std::min<unsigned>(grid_for(e->n).x, 512u)) : grid_for(e->n);
-        hipLaunchKernelGGL(ami_agent_reset_kernel, grid, dim3(TBX_BLOCK), 0, s, d, dA, dB, r);
+        hipLaunchKernelGGL(ami_agent_reset_kernel, grid, dim3(TBX_BLOCK), 0, s, d, dA, dB, dKA, dKB, r);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
 
     int render_from(tbx_engine* e, int source, const uint8_t* pick_live, uint8_t* out_dev, int channels, hipStream_t s) override
     {
-        dA.tab = dB.tab = d.tab;
+        dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         const AmiDev& src = source == 1 ? dA : source == 2 ? dB : d;
         return render_impl(e, src, d, source ? pick_live : nullptr, out_dev, channels, 0, e->n, s);
     }
@@ -2234,8 +2250,8 @@ struct AmiOps : GameOps {
     // mirror, of the live state and of the agent layer's two slots
     void copy_envs(tbx_engine*, TbxForkPlan& plan) override
     {
-        const AmiDev* const all[3] = {&d, &dA, &dB};
-        for (int k = 0; k < 3; k++) {
+        const AmiDev* const all[5] = {&d, &dA, &dB, &dKA, &dKB};   // (the kept copies too: mode 2 travels with the env)
+        for (int k = 0; k < 5; k++) {
             const AmiDev& x = *all[k];
             plan.soa(x.rng, 2, k == 0 ? 1 : 0);
             plan.soa(x.sc, ANF);

@@ -921,7 +921,10 @@ struct BrkTEnv {
     Rng& sim;
     BrkRenderRec* slot_a;
     BrkRenderRec* slot_b;
+    BrkRenderRec* keep_a;
+    BrkRenderRec* keep_b;
     __device__ __forceinline__ void snapshot(int slot) { *(slot ? slot_b : slot_a) = t_record(s); }
+    __device__ __forceinline__ bool keep() { *keep_a = *slot_a; *keep_b = *slot_b; return true; }
     __device__ __forceinline__ void step(uint32_t buttons) { brk_t_step(c, s, buttons); }
     __device__ __forceinline__ void new_game() { t_new_game(c, sim, s); }
     __device__ __forceinline__ int lives() const { return s.lives; }
@@ -929,7 +932,7 @@ struct BrkTEnv {
 };
 
 __global__ __launch_bounds__(128) void brk_agent_reset_kernel(BrkDev d, const BrkCfg* __restrict__ cp, AgentResetArgs r, BrkRenderRec* recs,
-                                                              BrkRenderRec* recs_a, BrkRenderRec* recs_b)
+                                                              BrkRenderRec* recs_a, BrkRenderRec* recs_b, BrkRenderRec* keep_a, BrkRenderRec* keep_b)
 {
     const BrkCfg& c = *cp;
     const int env = blockIdx.x * blockDim.x + threadIdx.x;
@@ -941,14 +944,14 @@ __global__ __launch_bounds__(128) void brk_agent_reset_kernel(BrkDev d, const Br
     Rng sim;
     sim.s0 = d.sim_rng[env]; sim.s1 = d.sim_rng[N + env];
     AgentMonitor m = agent_monitor_load(r, env);
-    BrkTEnv env_ops{c, s, sim, recs_a + env, recs_b + env};
+    BrkTEnv env_ops{c, s, sim, recs_a + env, recs_b + env, keep_a + env, keep_b + env};
     AgentResetProc<BrkTEnv> proc{env_ops, r, m, r.env_offset + (uint64_t)env, d.prev_score[env], (uint32_t)r.buf_valid[env],
                                  r.noop_override ? r.noop_override[env] : 0, false};
     proc.run();
     t_store(d, env, s);
     d.sim_rng[env] = sim.s0; d.sim_rng[N + env] = sim.s1;
     d.prev_score[env] = proc.prev;
-    agent_monitor_store(r, env, m, proc.valid, proc.obs_raw);
+    agent_monitor_store(r, env, m, proc.valid, proc.obs_raw, proc.obs_keep);
     recs[env] = t_record(s);
 }
 
@@ -1479,7 +1482,8 @@ __device__ __forceinline__ uint32_t brk_gray_line(const BrkRenderRec& rec, const
 // 10 % slower than before the run-based walk; held to five it stays under 96)
 template <int S>
 __global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(5))) void brk_agent_warp_kernel(const BrkRenderRec* __restrict__ recsLive, const BrkRenderRec* __restrict__ recsA,
-                                                                   const BrkRenderRec* __restrict__ recsB, BrkGrayPal pal, AgentWarpArgs a, int n)
+                                                                   const BrkRenderRec* __restrict__ recsB, const BrkRenderRec* __restrict__ keepA,
+                                                                   const BrkRenderRec* __restrict__ keepB, BrkGrayPal pal, AgentWarpArgs a, int n)
 {
     constexpr int W = TBX_BRK_W, H = TBX_BRK_H;
     __shared__ __attribute__((aligned(16))) uint8_t lds_all[TBX_WAVES_PER_BLOCK][352];
@@ -1499,8 +1503,10 @@ __global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(5))) 
     const bool fresh = !sel.two;                           // one frame alone: record B is its source, record A is not composed
     // the SOURCE ARRAY is selected (wave-uniform pointer), then one scalar load: a select between loaded records would
     // move them into vector registers
-    const BrkRenderRec* __restrict__ srcB = sel.single == 0 ? recsLive : sel.single == 1 ? recsA : recsB;
-    const BrkRenderRec recA = recsA[env];
+    // (sel.keep: the buffer as FireResetEnv.reset's step(2) left it, kept aside before a no-op step rewrote slots A / B)
+    const BrkRenderRec* __restrict__ srcA = sel.keep ? keepA : recsA;
+    const BrkRenderRec* __restrict__ srcB = sel.single == 0 ? recsLive : sel.single == 1 ? srcA : sel.keep ? keepB : recsB;
+    const BrkRenderRec recA = srcA[env];
     const BrkRenderRec recB = srcB[env];
     const int x0 = lane * 4;
     const bool active = x0 < W;
@@ -1936,6 +1942,8 @@ struct BreakoutOps : GameOps {
         hipFree(recs_third);
         hipFree(recs_chunk[0]); hipFree(recs_chunk[1]);
         hipFree(recsA);
+        hipFree(keepA);
+        hipFree(keepB);
         hipFree(recsB);
         hipFree(cfg_dev);
     }
@@ -2216,6 +2224,8 @@ struct BreakoutOps : GameOps {
     // ---- agent layer: MaxAndSkipEnv's two-frame buffer is two 64-byte render records per env
     BrkRenderRec* recsA = nullptr;
     BrkRenderRec* recsB = nullptr;
+    BrkRenderRec* keepA = nullptr;   // copies of slots A / B for the observation of one agent step (AgentResetProc::run, mode 2)
+    BrkRenderRec* keepB = nullptr;
 
     bool agent_fused() const override { return !custom; }
     bool multi_frame_step() const override { return !custom && use_tpe; }
@@ -2225,6 +2235,10 @@ struct BreakoutOps : GameOps {
     {
         if (!recsA) TBX_HIP(hipMalloc((void**)&recsA, sizeof(BrkRenderRec) * (size_t)e->n));
         if (!recsB) TBX_HIP(hipMalloc((void**)&recsB, sizeof(BrkRenderRec) * (size_t)e->n));
+        if (!keepA) TBX_HIP(hipMalloc((void**)&keepA, sizeof(BrkRenderRec) * (size_t)e->n));
+        if (!keepB) TBX_HIP(hipMalloc((void**)&keepB, sizeof(BrkRenderRec) * (size_t)e->n));
+        TBX_HIP(hipMemset(keepA, 0, sizeof(BrkRenderRec) * (size_t)e->n));
+        TBX_HIP(hipMemset(keepB, 0, sizeof(BrkRenderRec) * (size_t)e->n));
         TBX_HIP(hipMemset(recsA, 0, sizeof(BrkRenderRec) * (size_t)e->n));
         TBX_HIP(hipMemset(recsB, 0, sizeof(BrkRenderRec) * (size_t)e->n));
         return TBX_OK;
@@ -2255,7 +2269,7 @@ struct BreakoutOps : GameOps {
     int agent_reset_envs(tbx_engine* e, const AgentResetArgs& r, hipStream_t s) override
     {
         if (custom) return e->fail(TBX_E_UNSUPPORTED, "breakout: episodic-life / fire-reset / no-op-reset need the canonical brick wall");
-        hipLaunchKernelGGL(brk_agent_reset_kernel, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, r, recs, recsA, recsB);
+        hipLaunchKernelGGL(brk_agent_reset_kernel, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, r, recs, recsA, recsB, keepA, keepB);
         TBX_HIP(hipGetLastError());
         // every other env's live record is still current if it was; the flagged envs' records were just rewritten
         return TBX_OK;
@@ -2286,11 +2300,11 @@ struct BreakoutOps : GameOps {
         }
         const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
         switch (a.obs ? a.stack : 0) {
-        case 0: hipLaunchKernelGGL(brk_agent_warp_kernel<0>, grid, block, 0, s, recs, recsA, recsB, pal, a, e->n); break;      // the plane ring (new_plane = 2), any depth
-        case 1: hipLaunchKernelGGL(brk_agent_warp_kernel<1>, grid, block, 0, s, recs, recsA, recsB, pal, a, e->n); break;
-        case 2: hipLaunchKernelGGL(brk_agent_warp_kernel<2>, grid, block, 0, s, recs, recsA, recsB, pal, a, e->n); break;
-        case 3: hipLaunchKernelGGL(brk_agent_warp_kernel<3>, grid, block, 0, s, recs, recsA, recsB, pal, a, e->n); break;
-        default: hipLaunchKernelGGL(brk_agent_warp_kernel<4>, grid, block, 0, s, recs, recsA, recsB, pal, a, e->n); break;
+        case 0: hipLaunchKernelGGL(brk_agent_warp_kernel<0>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;      // the plane ring (new_plane = 2), any depth
+        case 1: hipLaunchKernelGGL(brk_agent_warp_kernel<1>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;
+        case 2: hipLaunchKernelGGL(brk_agent_warp_kernel<2>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;
+        case 3: hipLaunchKernelGGL(brk_agent_warp_kernel<3>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;
+        default: hipLaunchKernelGGL(brk_agent_warp_kernel<4>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;
         }
         TBX_HIP(hipGetLastError());
         return TBX_OK;
@@ -2384,6 +2398,8 @@ struct BreakoutOps : GameOps {
         plan.rows(d.custom, sizeof(BrkCustom));
         plan.rows(recsA, sizeof(BrkRenderRec));
         plan.rows(recsB, sizeof(BrkRenderRec));
+        plan.rows(keepA, sizeof(BrkRenderRec));        // (an env copied while its observation is the kept buffer's: mode 2 travels too)
+        plan.rows(keepB, sizeof(BrkRenderRec));
         recs_valid = false;
     }
 

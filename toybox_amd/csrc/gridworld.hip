@@ -232,6 +232,7 @@ struct GwAgentEnv {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // lane 0's scalars land after the copied ones
         if (lane == 0) gw_store(dst, env, s);
     }
+    __device__ __forceinline__ bool keep() { return false; }
     __device__ __forceinline__ void step(uint32_t buttons) { gw_step(d, env, s, buttons); }
     __device__ __forceinline__ void new_game()
     {

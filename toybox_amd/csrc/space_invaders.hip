@@ -852,14 +852,23 @@ struct SiAgentEnv {
     const SiDev& slot_a;
     const SiDev& slot_b;
     int env;
+    const SiDev& keep_a;
+    const SiDev& keep_b;
     __device__ __forceinline__ void snapshot(int slot) { si_store(slot ? slot_b : slot_a, env, lane, s); }
+    __device__ __forceinline__ bool keep()                     // both buffer slots of this env aside, for the observation kernel (mode 2)
+    {
+        SiRegs t;
+        si_load(slot_a, env, lane, t); si_store(keep_a, env, lane, t);
+        si_load(slot_b, env, lane, t); si_store(keep_b, env, lane, t);
+        return true;
+    }
     __device__ __forceinline__ void step(uint32_t buttons) { si_step(c, lane, buttons, s); }
     __device__ __forceinline__ void new_game() { si_new_game(c, lane, sim, s); }
     __device__ __forceinline__ int lives() const { return wave_uniform(s.f[F_LIVES]); }
     __device__ __forceinline__ int score() const { return wave_uniform(s.f[F_SCORE]); }
 };
 
-__global__ __launch_bounds__(TBX_BLOCK) void si_agent_reset_kernel(SiDev d, SiDev slot_a, SiDev slot_b, SiCfg c, AgentResetArgs r)
+__global__ __launch_bounds__(TBX_BLOCK) void si_agent_reset_kernel(SiDev d, SiDev slot_a, SiDev slot_b, SiDev keep_a, SiDev keep_b, SiCfg c, AgentResetArgs r)
 {
     const int lane = threadIdx.x & 63;
     // a persistent grid walks the compact list of flagged envs (or every env when there is no list)
@@ -874,7 +883,7 @@ __global__ __launch_bounds__(TBX_BLOCK) void si_agent_reset_kernel(SiDev d, SiDe
         Rng sim;
         sim.s0 = d.sim_rng[env]; sim.s1 = d.sim_rng[N + env];
         AgentMonitor m = agent_monitor_load(r, env);
-        SiAgentEnv ops{c, lane, s, sim, slot_a, slot_b, env};
+        SiAgentEnv ops{c, lane, s, sim, slot_a, slot_b, env, keep_a, keep_b};
         AgentResetProc<SiAgentEnv> proc{ops, r, m, r.env_offset + (uint64_t)env, wave_uniform(d.prev_score[env]),
                                         (uint32_t)wave_uniform((int)r.buf_valid[env]), r.noop_override ? wave_uniform(r.noop_override[env]) : 0, false};
         proc.run();
@@ -882,7 +891,7 @@ __global__ __launch_bounds__(TBX_BLOCK) void si_agent_reset_kernel(SiDev d, SiDe
         if (lane == 0) {
             d.sim_rng[env] = sim.s0; d.sim_rng[N + env] = sim.s1;
             d.prev_score[env] = proc.prev;
-            agent_monitor_store(r, env, m, proc.valid, proc.obs_raw);
+            agent_monitor_store(r, env, m, proc.valid, proc.obs_raw, proc.obs_keep);
         }
     }
 }
@@ -1657,7 +1666,7 @@ __global__ __launch_bounds__(64 * TBX_SERVE_WAVES) void si_serve_kernel(SiDev d,
 // (three waves per SIMD: the two painters sit at 168-170 VGPRs, one register either side of the step from three waves to two,
 // and the kernel is issue-bound -- 2.98 ms per agent step with three, 4.07 with two)
 template <int S>
-__global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(3))) void si_agent_warp_kernel(SiDev dLive, SiDev dA, SiDev dB, AgentWarpArgs a, int n)
+__global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(3))) void si_agent_warp_kernel(SiDev dLive, SiDev dA, SiDev dB, SiDev dKA, SiDev dKB, AgentWarpArgs a, int n)
 {
     __shared__ AgentFusedLds<SiGrayPainter> lds[TBX_WAVES_PER_BLOCK];
     __shared__ uint32_t spr_lds[SPR_WORDS];
@@ -1668,7 +1677,9 @@ __global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(3))) 
     if (env >= a.end) return;
     SiGrayPainter pa, pb;
     pa.spr_lds = spr_lds; pb.spr_lds = spr_lds;
-    agent_fused_wave<S, SiGrayPainter>(pa, pb, dLive, dA, dB, a, env, lane, lds[wave]);
+    // (mode 2: the buffer as FireResetEnv.reset's step(2) left it, kept aside before a no-op step rewrote slots A / B)
+    const bool kept = (__builtin_amdgcn_readfirstlane((int)a.mode[env]) & 2) != 0;
+    agent_fused_wave<S, SiGrayPainter>(pa, pb, dLive, kept ? dKA : dA, kept ? dKB : dB, a, env, lane, lds[wave]);
 }
 
 // ------------------------------------------------------------------ state pack / unpack, scalars
@@ -1866,6 +1877,8 @@ struct SiOps : GameOps {
         hipFree(d.sc); hipFree(d.enemies); hipFree(d.shields); hipFree(d.lasers);
         hipFree(dA.sc); hipFree(dA.enemies); hipFree(dA.shields); hipFree(dA.lasers);
         hipFree(dB.sc); hipFree(dB.enemies); hipFree(dB.shields); hipFree(dB.lasers);
+        hipFree(dKA.sc); hipFree(dKA.enemies); hipFree(dKA.shields); hipFree(dKA.lasers);
+        hipFree(dKB.sc); hipFree(dKB.enemies); hipFree(dKB.shields); hipFree(dKB.lasers);
     }
 
     int get_config(tbx_engine*, void* pod) override { memcpy(pod, &cfg, sizeof cfg); return TBX_OK; }
@@ -1955,6 +1968,7 @@ struct SiOps : GameOps {
 
     // ---- agent layer: MaxAndSkipEnv's two-frame buffer is two snapshots of the dynamic SoA state per env
     SiDev dA{}, dB{};
+    SiDev dKA{}, dKB{};      // copies of the two slots for the observation of one agent step (AgentResetProc::run, mode 2)
     bool agent_fused() const override { return true; }
     bool multi_frame_step() const override { return true; }
     bool agent_reset_supported() const override { return true; }
@@ -1975,19 +1989,21 @@ struct SiOps : GameOps {
     int agent_prepare(tbx_engine* e) override
     {
         int rc = alloc_slot(e, dA);
-        if (rc) return rc;
-        return alloc_slot(e, dB);
+        if (!rc) rc = alloc_slot(e, dB);
+        if (!rc) rc = alloc_slot(e, dKA);
+        if (!rc) rc = alloc_slot(e, dKB);
+        return rc;
     }
 
     int agent_warp(tbx_engine* e, const AgentWarpArgs& a, hipStream_t s) override
     {
         const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
         switch (a.obs ? a.stack : 0) {
-        case 0: hipLaunchKernelGGL(si_agent_warp_kernel<0>, grid, block, 0, s, d, dA, dB, a, e->n); break;      // the plane ring (new_plane = 2), any depth
-        case 1: hipLaunchKernelGGL(si_agent_warp_kernel<1>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        case 2: hipLaunchKernelGGL(si_agent_warp_kernel<2>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        case 3: hipLaunchKernelGGL(si_agent_warp_kernel<3>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        default: hipLaunchKernelGGL(si_agent_warp_kernel<4>, grid, block, 0, s, d, dA, dB, a, e->n); break;
+        case 0: hipLaunchKernelGGL(si_agent_warp_kernel<0>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;      // the plane ring (new_plane = 2), any depth
+        case 1: hipLaunchKernelGGL(si_agent_warp_kernel<1>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
+        case 2: hipLaunchKernelGGL(si_agent_warp_kernel<2>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
+        case 3: hipLaunchKernelGGL(si_agent_warp_kernel<3>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
+        default: hipLaunchKernelGGL(si_agent_warp_kernel<4>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
         }
         TBX_HIP(hipGetLastError());
         return TBX_OK;
@@ -1996,7 +2012,7 @@ struct SiOps : GameOps {
     int agent_reset_envs(tbx_engine* e, const AgentResetArgs& r, hipStream_t s) override
     {
         const dim3 grid = r.list ? dim3(std::min<unsigned>(grid_for(e->n).x, 512u)) : grid_for(e->n);
-        hipLaunchKernelGGL(si_agent_reset_kernel, grid, dim3(TBX_BLOCK), 0, s, d, dA, dB, c, r);
+        hipLaunchKernelGGL(si_agent_reset_kernel, grid, dim3(TBX_BLOCK), 0, s, d, dA, dB, dKA, dKB, c, r);
         TBX_HIP(hipGetLastError());
         recs_valid = false;
         return TBX_OK;
@@ -2179,8 +2195,8 @@ struct SiOps : GameOps {
     // env is canonical)
     void copy_envs(tbx_engine*, TbxForkPlan& plan) override
     {
-        const SiDev* const all[3] = {&d, &dA, &dB};
-        for (int k = 0; k < 3; k++) {
+        const SiDev* const all[5] = {&d, &dA, &dB, &dKA, &dKB};   // (the kept copies too: mode 2 travels with the env)
+        for (int k = 0; k < 5; k++) {
             const SiDev& x = *all[k];
             plan.rows(x.sc, HEAD_WORDS * sizeof(int32_t), 1, k == 0 ? HEAD_RNG * sizeof(int32_t) : 0, k == 0 ? 2 : 0);
             plan.rows(x.enemies, NEF * 64 * sizeof(int32_t));
