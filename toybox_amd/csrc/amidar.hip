@@ -2174,13 +2174,9 @@ struct AmiOps : GameOps {
     {
         dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
-        switch (a.obs ? a.stack : 0) {
-        case 0: hipLaunchKernelGGL(ami_agent_warp_kernel<0>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;      // the plane ring (new_plane = 2), any depth
-        case 1: hipLaunchKernelGGL(ami_agent_warp_kernel<1>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
-        case 2: hipLaunchKernelGGL(ami_agent_warp_kernel<2>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
-        case 3: hipLaunchKernelGGL(ami_agent_warp_kernel<3>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
-        default: hipLaunchKernelGGL(ami_agent_warp_kernel<4>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
-        }
+        tbx_dispatch<0, 1, 2, 3, 4>(tbx_stack_arm(a.obs, a.stack), [&](auto depth) {
+            hipLaunchKernelGGL(ami_agent_warp_kernel<decltype(depth)::value>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n);
+        });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2227,7 +2223,7 @@ struct AmiOps : GameOps {
 
     int pack_state(tbx_engine* e, int env, int count, hipStream_t s) override
     {
-        hipLaunchKernelGGL(ami_pack_kernel, dim3(count), dim3(64), 0, s, d, env, (tbx_amidar_state_t*)e->staging);
+        hipLaunchKernelGGL(ami_pack_kernel, dim3(count), dim3(64), 0, s, d, env, (tbx_amidar_state_t*)e->staging.p);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2240,8 +2236,8 @@ struct AmiOps : GameOps {
             if (st.n_enemies < 0 || st.n_enemies > TBX_AMI_MAX_ENEMIES) return e->fail(TBX_E_UNSUPPORTED, "amidar: the device engine holds at most 8 enemies per env");
             if (st.n_boxes < 0 || st.n_boxes > TBX_AMI_MAX_BOXES) return e->fail(TBX_E_UNSUPPORTED, "amidar: the device engine holds at most 64 boxes per env");
         }
-        TBX_HIP(hipMemcpyAsync(e->staging, pod_host, sizeof(tbx_amidar_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(ami_unpack_kernel, dim3(count), dim3(64), 0, s, d, env, (const tbx_amidar_state_t*)e->staging);
+        TBX_HIP(hipMemcpyAsync(e->staging.p, pod_host, sizeof(tbx_amidar_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(ami_unpack_kernel, dim3(count), dim3(64), 0, s, d, env, (const tbx_amidar_state_t*)e->staging.p);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

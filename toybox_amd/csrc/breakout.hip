@@ -577,7 +577,7 @@ __device__ __forceinline__ void t_new_game(const BrkCfg& c, Rng& sim, BrkT& s)
     t_start_ball(c, s);
 }
 
-// COH = the step half of an OVERLAPPED fused launch (engine.hip, fused_overlapped): the launch before it may still be running on
+// COH = the step half of an OVERLAPPED fused launch (pipeline.hip, fused_overlapped): the launch before it may still be running on
 // the other stream, on other XCDs with L2s of their own, and the launch after it starts before this one ends.  Every load of
 // step-written memory and every store then carries agent scope (global_load / global_store ... sc1: past the XCD's L2 to the
 // memory side), so that publishing a block's results needs no L2 write-back and reading the previous step's needs no L2
@@ -1328,7 +1328,7 @@ __global__ __launch_bounds__(TBX_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5)
         brk_render_body<C, false, false>(recs, nullptr, pal, out, 0, count, split | (1 << 16), nullptr, nullptr, (int)blockIdx.x - step_blocks);
         return;
     }
-    // arrive != nullptr: an overlapped launch (engine.hip, fused_overlapped).  The launch before this one may still be painting on
+    // arrive != nullptr: an overlapped launch (pipeline.hip, fused_overlapped).  The launch before this one may still be painting on
     // the other lane; what it STEPPED (state, the records read below) was fenced out before its step blocks bumped the counter
     // the engine's wait kernel saw.  The step blocks' waves start by dropping what their caches hold from before that (one
     // invalidate per wave of a few hundred waves; as the first instruction of EVERY wave of the launch it made the launch four times
@@ -1856,14 +1856,8 @@ struct BreakoutOps : GameOps {
     BrkCfg c{};
     tbx_breakout_config_t cfg{};
     bool custom = false;
-    BrkRenderRec* recs = nullptr;   // [N] rasteriser input records (the CURRENT of two buffers)
-    BrkRenderRec* recs_other = nullptr;   // the other one: a step that runs ahead of the previous frame's rasteriser writes
-    int recs_par = 0;               // here and the two swap (GameOps::step_ahead)
-    BrkRenderRec* recs_third = nullptr;   // fused launches rotate through three (render_step): a launch overlapped on the other lane must not
-                                          // rewrite what this launch's rasteriser blocks still read
-    BrkRenderRec* recs_chunk[2] = {nullptr, nullptr};   // [k][N] records of a rollout chunk of parity q (tbx_rollout_synthetic), made on first use
-    int recs_chunk_k[2] = {0, 0};
-    bool recs_valid = false;        // records reflect the current state of every env
+    TbxRecordSet<BrkRenderRec> recs;   // fused launches rotate through three (render_step): a launch overlapped on the other lane must not
+                                       // rewrite what this launch's rasteriser blocks still read
     BrkCfg* cfg_dev = nullptr;      // device copy of `c` for kernels that index the tables per thread
 
     static void default_config(tbx_breakout_config_t* k);
@@ -1925,9 +1919,7 @@ struct BreakoutOps : GameOps {
         TBX_HIP(dalloc(&d.balls, 16 * N));
         TBX_HIP(dalloc(&d.n_bricks, N));
         TBX_HIP(dalloc(&d.alive, 4 * N));
-        TBX_HIP(dalloc(&recs, N));
-        TBX_HIP(dalloc(&recs_other, N));
-        TBX_HIP(dalloc(&recs_third, N));
+        TBX_HIP(recs.alloc(N, 3));
         d.custom = nullptr;
         return TBX_OK;
     }
@@ -1937,10 +1929,7 @@ struct BreakoutOps : GameOps {
         hipFree(d.rng); hipFree(d.score); hipFree(d.lives); hipFree(d.level); hipFree(d.flags);
         hipFree(d.paddle); hipFree(d.n_balls); hipFree(d.balls); hipFree(d.n_bricks); hipFree(d.alive);
         if (d.custom) hipFree(d.custom);
-        hipFree(recs);
-        hipFree(recs_other);
-        hipFree(recs_third);
-        hipFree(recs_chunk[0]); hipFree(recs_chunk[1]);
+        recs.release();
         hipFree(recsA);
         hipFree(keepA);
         hipFree(keepB);
@@ -1963,7 +1952,7 @@ struct BreakoutOps : GameOps {
         if (custom) hipLaunchKernelGGL(brk_new_game_kernel<true>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, mask_dev);
         else hipLaunchKernelGGL(brk_new_game_kernel<false>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, mask_dev);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 
@@ -1972,11 +1961,11 @@ struct BreakoutOps : GameOps {
         if (!custom && src.single_env < 0 && use_tpe) {
             if (src.acc_reward || src.buf_valid || src.exec_flag || src.frames > 1) {    // an agent step's frames (never auto-reset)
                 if (flags & TBX_STEP_AUTO_RESET) return e->fail(TBX_E_INVALID, "an agent step cannot auto-reset");
-                hipLaunchKernelGGL(brk_step_tpe_kernel<true>, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, recs, recsA, recsB);
+                hipLaunchKernelGGL(brk_step_tpe_kernel<true>, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, recs.cur, recsA, recsB);
             } else
-                TBX_LAUNCH_STEP(e, s, (brk_step_tpe_kernel<false>), dim3((e->n + 127) / 128), dim3(128), d, cfg_dev, src, flags, recs, recsA, recsB);
+                TBX_LAUNCH_STEP(e, s, (brk_step_tpe_kernel<false>), dim3((e->n + 127) / 128), dim3(128), d, cfg_dev, src, flags, recs.cur, recsA, recsB);
             TBX_HIP(hipGetLastError());
-            recs_valid = true;
+            recs.valid = true;
             return TBX_OK;
         }
         int first = 0, count = e->n;
@@ -1984,13 +1973,13 @@ struct BreakoutOps : GameOps {
         if (custom) hipLaunchKernelGGL(brk_step_kernel<true>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count);
         else hipLaunchKernelGGL(brk_step_kernel<false>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 
     // the rasteriser reads nothing but the records, and there are two buffers of them: a batch step of the canonical wall
-    // can run while the previous frame is still being painted (engine.hip, pipelined mode)
-    bool pipeline_ok() const override { return !custom && use_tpe && recs_other != nullptr; }
+    // can run while the previous frame is still being painted (pipeline.hip, pipelined mode)
+    bool pipeline_ok() const override { return !custom && use_tpe && recs.other != nullptr; }
     // scripts/pipeline_sweep.py, stream order against value 3, ms per step without a gather: 1 024 envs 0.0315 / 0.038, 2 048
     // 0.0491 / 0.0507, 4 096 0.0985 / 0.0868, 8 192 0.168 / 0.164, 12 288 0.243 / 0.240; with one at 8 192: 0.175 / 0.230
     int pipeline_auto(int n, bool gather) const override { return (!gather && n >= 4096 && n < 16384) ? 3 : 0; }
@@ -2003,15 +1992,13 @@ struct BreakoutOps : GameOps {
         use_tpe = e->opt[TBX_OPT_STEP_FORM] != 2;     // thread per env unless the wave-per-env kernel is asked for
         split_opt = e->opt[TBX_OPT_RENDER_SPLIT];
     }
-    int records_parity() const override { return recs_par; }
-    bool records_valid() const override { return recs_valid; }
+    int records_parity() const override { return recs.par; }
+    bool records_valid() const override { return recs.valid; }
     int step_ahead(tbx_engine* e, const ActionSource& src, uint32_t flags, hipStream_t s) override
     {
-        hipLaunchKernelGGL(brk_step_tpe_kernel<false>, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, recs_other, recsA, recsB);
+        hipLaunchKernelGGL(brk_step_tpe_kernel<false>, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, recs.other, recsA, recsB);
         TBX_HIP(hipGetLastError());
-        std::swap(recs, recs_other);
-        recs_par ^= 1;
-        recs_valid = true;
+        recs.stepped_ahead();
         return TBX_OK;
     }
 
@@ -2035,10 +2022,10 @@ struct BreakoutOps : GameOps {
     static constexpr int FUSED_LEAD_BLOCKS = 1 << 20;
     int render_step(tbx_engine* e, uint8_t* out_dev, int channels, const ActionSource& src, uint32_t flags, hipStream_t s, TbxOverlapLaunch* ov) override
     {
-        if (!recs_valid) {                                     // the painter reads records: bring them up to the state first
-            hipLaunchKernelGGL(brk_render_prep_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, d, recs, 0, e->n);
+        if (!recs.valid) {                                     // the painter reads records: bring them up to the state first
+            hipLaunchKernelGGL(brk_render_prep_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, d, recs.cur, 0, e->n);
             TBX_HIP(hipGetLastError());
-            recs_valid = true;
+            recs.valid = true;
         }
         const BrkPalette pal = palette();
         const int split = split_opt > 0 ? split_opt : channels == 3 ? 10 : e->n <= 8192 ? 4 : e->n <= 32768 ? 2 : 1;
@@ -2052,29 +2039,20 @@ struct BreakoutOps : GameOps {
             const int lead = ov->lead > 0 ? ov->lead : FUSED_LEAD_BLOCKS;
             const int release_block = std::max(step_blocks, (int)grid.x - lead);
             hipEvent_t done = OVL_DIAG(ov->diag, 128) ? nullptr : ov->done;
-            switch (channels) {
-            case 3: hipExtLaunchKernelGGL((brk_render_step_kernel_w5<3, true>), grid, block, 0, s, nullptr, done, 0, recs, pal, out_dev, e->n, split, d, cfg_dev, src, flags, recs_other, step_blocks, ov->arrive, release_block, ov->diag); break;
-            case 4: hipExtLaunchKernelGGL((brk_render_step_kernel_w5<4, true>), grid, block, 0, s, nullptr, done, 0, recs, pal, out_dev, e->n, split, d, cfg_dev, src, flags, recs_other, step_blocks, ov->arrive, release_block, ov->diag); break;
-            default: return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
-            }
-        } else
-            switch (channels) {
-            case 3: TBX_LAUNCH_STEP(e, s, (brk_render_step_kernel_w5<3, false>), grid, block, recs, pal, out_dev, e->n, split, d, cfg_dev, src, flags, recs_other, step_blocks, no_counter, 0, 0); break;
-            case 4: TBX_LAUNCH_STEP(e, s, (brk_render_step_kernel_w5<4, false>), grid, block, recs, pal, out_dev, e->n, split, d, cfg_dev, src, flags, recs_other, step_blocks, no_counter, 0, 0); break;
-            default: return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
-            }
+            if (!tbx_dispatch<3, 4>(channels, [&](auto ch) {
+                    hipExtLaunchKernelGGL((brk_render_step_kernel_w5<decltype(ch)::value, true>), grid, block, 0, s, nullptr, done, 0, recs.cur, pal, out_dev, e->n, split, d, cfg_dev, src, flags, recs.other, step_blocks, ov->arrive, release_block, ov->diag);
+                }))
+                return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
+        } else if (!tbx_dispatch<3, 4>(channels, [&](auto ch) {
+                       TBX_LAUNCH_STEP(e, s, (brk_render_step_kernel_w5<decltype(ch)::value, false>), grid, block, recs.cur, pal, out_dev, e->n, split, d, cfg_dev, src, flags, recs.other, step_blocks, no_counter, 0, 0);
+                   }))
+            return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
-        // THREE buffers in rotation: the launch after this one reads what this one's step wrote and writes the third, so that a
-        // launch on the other lane never rewrites records this launch's rasteriser blocks may still be reading
-        BrkRenderRec* const was_read = recs;
-        recs = recs_other;
-        recs_other = recs_third;
-        recs_third = was_read;
-        recs_par ^= 1;
+        recs.rotate3();
         return TBX_OK;
     }
 
-    // ---- rollout chunks (engine.hip, rollout_chunked)
+    // ---- rollout chunks (pipeline.hip, rollout_chunked)
     bool rollout_ok(int channels) const override { return pipeline_ok() && channels >= 3; }
     // same-box A/B against the loop of single calls in stream order (scripts/rollout_ab.py, k = 4, ms per step, with the K = 4 record
     // ring | without a gather; profiles/r06_experiments.txt): 4 096 envs 0.0854 -> 0.0747 | 0.0833 -> 0.0748 (0.79 of 8 TB/s); 8 192:
@@ -2096,22 +2074,15 @@ struct BreakoutOps : GameOps {
     bool rollout_auto(int n, int gather_kind) const override { return n <= 32768 && (gather_kind == 0 || n >= 2048); }
     int rollout_step(tbx_engine* e, const ActionSource& src, uint32_t flags, int k, int q, uint64_t* packed, size_t stride, hipStream_t s) override
     {
-        if (recs_chunk_k[q] < k) {                             // (the caller has made sure nothing reads the old buffer any more)
-            TBX_HIP(hipStreamSynchronize(s));
-            hipFree(recs_chunk[q]);
-            recs_chunk[q] = nullptr;
-            recs_chunk_k[q] = 0;
-            TBX_HIP(hipMalloc((void**)&recs_chunk[q], sizeof(BrkRenderRec) * (size_t)k * (size_t)e->n));
-            recs_chunk_k[q] = k;
-        }
-        hipLaunchKernelGGL(brk_rollout_step_kernel, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, k, recs_chunk[q], packed, stride);
+        TBX_HIP(recs.chunk_reserve(q, k, (size_t)e->n, s));   // (the caller has made sure nothing reads the old buffer any more)
+        hipLaunchKernelGGL(brk_rollout_step_kernel, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, k, recs.chunk[q].p, packed, stride);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;                                    // the single-frame records no longer show the state
+        recs.valid = false;                                    // the single-frame records no longer show the state
         return TBX_OK;
     }
     int rollout_render(tbx_engine* e, uint8_t* out, int channels, int q, int j, hipStream_t s) override
     {
-        const BrkRenderRec* rr = recs_chunk[q] + (size_t)j * (size_t)e->n;
+        const BrkRenderRec* rr = recs.chunk[q].p + (size_t)j * (size_t)e->n;
         if (channels == 3) launch_render<3>(out, 0, e->n, s, rr);
         else launch_render<4>(out, 0, e->n, s, rr);
         TBX_HIP(hipGetLastError());
@@ -2128,7 +2099,7 @@ struct BreakoutOps : GameOps {
         // behind another rasteriser launch: one part, no staggered first waves (what those two are for -- first waves that start
         // together into an idle memory system -- does not happen there); 8 192 envs x 4 frames 0.1533-0.1536 ms per step against
         // 0.1553 with the two-part launch, 4 096: 0.0792 / 0.0813, 16 384: 0.3022 / 0.3035 (three processes each, r06_experiments item 6)
-        const BrkRenderRec* rr = recs_chunk[q] + (size_t)j0 * (size_t)e->n;
+        const BrkRenderRec* rr = recs.chunk[q].p + (size_t)j0 * (size_t)e->n;
         if (channels == 3) launch_render<3>(out, 0, count * e->n, s, rr, nullptr, nullptr, behind_rasteriser);
         else launch_render<4>(out, 0, count * e->n, s, rr, nullptr, nullptr, behind_rasteriser);
         TBX_HIP(hipGetLastError());
@@ -2147,11 +2118,11 @@ struct BreakoutOps : GameOps {
     int serve(tbx_engine* e, TbxServeCtl* ctl_dev, hipStream_t s) override
     {
         const BrkPalette pal = palette();
-        if (custom) hipLaunchKernelGGL(brk_serve_kernel<true>, dim3(1), dim3(64 * TBX_SERVE_WAVES), 0, s, d, c, recs, pal, ctl_dev);
-        else if (use_tpe) hipLaunchKernelGGL(brk_serve_tpe_kernel, dim3(1), dim3(64 * TBX_SERVE_WAVES), 0, s, d, cfg_dev, recs, pal, ctl_dev);
-        else hipLaunchKernelGGL(brk_serve_kernel<false>, dim3(1), dim3(64 * TBX_SERVE_WAVES), 0, s, d, c, recs, pal, ctl_dev);
+        if (custom) hipLaunchKernelGGL(brk_serve_kernel<true>, dim3(1), dim3(64 * TBX_SERVE_WAVES), 0, s, d, c, recs.cur, pal, ctl_dev);
+        else if (use_tpe) hipLaunchKernelGGL(brk_serve_tpe_kernel, dim3(1), dim3(64 * TBX_SERVE_WAVES), 0, s, d, cfg_dev, recs.cur, pal, ctl_dev);
+        else hipLaunchKernelGGL(brk_serve_kernel<false>, dim3(1), dim3(64 * TBX_SERVE_WAVES), 0, s, d, c, recs.cur, pal, ctl_dev);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;         // (the thread-per-env form keeps env 0's record current, but nothing here relies on it)
+        recs.valid = false;         // (the thread-per-env form keeps env 0's record current, but nothing here relies on it)
         return TBX_OK;
     }
 
@@ -2163,11 +2134,11 @@ struct BreakoutOps : GameOps {
                        const BrkRenderRec* alt = nullptr, const uint8_t* pick_alt = nullptr, bool overlapped = false)
     {
         const BrkPalette pal = palette();
-        if (!recs_valid && (!src_recs || alt)) {           // the live records are read
-            hipLaunchKernelGGL(brk_render_prep_kernel, dim3((count + 255) / 256), dim3(256), 0, s, d, recs, first, count);
-            if (first == 0 && count == d.n) recs_valid = true;
+        if (!recs.valid && (!src_recs || alt)) {           // the live records are read
+            hipLaunchKernelGGL(brk_render_prep_kernel, dim3((count + 255) / 256), dim3(256), 0, s, d, recs.cur, first, count);
+            if (first == 0 && count == d.n) recs.valid = true;
         }
-        const BrkRenderRec* rr = src_recs ? src_recs : recs;
+        const BrkRenderRec* rr = src_recs ? src_recs : recs.cur;
         // ten waves per frame, each doing unit p and unit p + 10 (one from the busy upper half of the screen, one from the
         // lower): measured 6.05-6.25 TB/s against 5.4-5.7 for one wave per frame and for every other split from 1 to 20
         // except 9..12 (scripts/ab_render.py over TBX_OPT_RENDER_SPLIT); also what keeps small batches from under-filling the chip
@@ -2211,12 +2182,8 @@ struct BreakoutOps : GameOps {
 
     int render(tbx_engine* e, uint8_t* out_dev, int channels, int first_env, int n_envs, hipStream_t s) override
     {
-        switch (channels) {
-        case 1: launch_render<1>(out_dev, first_env, n_envs, s); break;
-        case 3: launch_render<3>(out_dev, first_env, n_envs, s); break;
-        case 4: launch_render<4>(out_dev, first_env, n_envs, s); break;
-        default: return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
-        }
+        if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) { launch_render<decltype(ch)::value>(out_dev, first_env, n_envs, s); }))
+            return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2255,13 +2222,9 @@ struct BreakoutOps : GameOps {
     int render_from(tbx_engine* e, int source, const uint8_t* pick_live, uint8_t* out_dev, int channels, hipStream_t s) override
     {
         const BrkRenderRec* src_recs = source == 1 ? recsA : source == 2 ? recsB : nullptr;
-        const BrkRenderRec* alt = (src_recs && pick_live) ? recs : nullptr;
-        switch (channels) {
-        case 1: launch_render<1>(out_dev, 0, e->n, s, src_recs, alt, alt ? pick_live : nullptr); break;
-        case 3: launch_render<3>(out_dev, 0, e->n, s, src_recs, alt, alt ? pick_live : nullptr); break;
-        case 4: launch_render<4>(out_dev, 0, e->n, s, src_recs, alt, alt ? pick_live : nullptr); break;
-        default: return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
-        }
+        const BrkRenderRec* alt = (src_recs && pick_live) ? recs.cur : nullptr;
+        if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) { launch_render<decltype(ch)::value>(out_dev, 0, e->n, s, src_recs, alt, alt ? pick_live : nullptr); }))
+            return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2269,7 +2232,7 @@ struct BreakoutOps : GameOps {
     int agent_reset_envs(tbx_engine* e, const AgentResetArgs& r, hipStream_t s) override
     {
         if (custom) return e->fail(TBX_E_UNSUPPORTED, "breakout: episodic-life / fire-reset / no-op-reset need the canonical brick wall");
-        hipLaunchKernelGGL(brk_agent_reset_kernel, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, r, recs, recsA, recsB, keepA, keepB);
+        hipLaunchKernelGGL(brk_agent_reset_kernel, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, r, recs.cur, recsA, recsB, keepA, keepB);
         TBX_HIP(hipGetLastError());
         // every other env's live record is still current if it was; the flagged envs' records were just rewritten
         return TBX_OK;
@@ -2293,26 +2256,22 @@ struct BreakoutOps : GameOps {
         for (int y = 2; y <= 12; y += 2) mark(y);           // HUD glyph rows are 2 px tall, HUD ends at 12
         mark(TBX_BRK_WALL_Y0); mark(TBX_BRK_WALL_Y0 + 12);  // top bar
         for (int r = 0; r <= c.n_rows; r++) mark(43 + 4 * r); // each brick row and the line after the wall
-        if (!recs_valid) {                                   // envs whose observation is the raw live frame read `recs`
-            hipLaunchKernelGGL(brk_render_prep_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, d, recs, 0, e->n);
+        if (!recs.valid) {                                   // envs whose observation is the raw live frame read `recs.cur`
+            hipLaunchKernelGGL(brk_render_prep_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, d, recs.cur, 0, e->n);
             TBX_HIP(hipGetLastError());
-            recs_valid = true;
+            recs.valid = true;
         }
         const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
-        switch (a.obs ? a.stack : 0) {
-        case 0: hipLaunchKernelGGL(brk_agent_warp_kernel<0>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;      // the plane ring (new_plane = 2), any depth
-        case 1: hipLaunchKernelGGL(brk_agent_warp_kernel<1>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;
-        case 2: hipLaunchKernelGGL(brk_agent_warp_kernel<2>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;
-        case 3: hipLaunchKernelGGL(brk_agent_warp_kernel<3>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;
-        default: hipLaunchKernelGGL(brk_agent_warp_kernel<4>, grid, block, 0, s, recs, recsA, recsB, keepA, keepB, pal, a, e->n); break;
-        }
+        tbx_dispatch<0, 1, 2, 3, 4>(tbx_stack_arm(a.obs, a.stack), [&](auto depth) {
+            hipLaunchKernelGGL(brk_agent_warp_kernel<decltype(depth)::value>, grid, block, 0, s, recs.cur, recsA, recsB, keepA, keepB, pal, a, e->n);
+        });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
 
     int pack_state(tbx_engine* e, int env, int count, hipStream_t s) override
     {
-        auto* out = (tbx_breakout_state_t*)e->staging;
+        auto* out = (tbx_breakout_state_t*)e->staging.p;
         if (custom) hipLaunchKernelGGL(brk_pack_kernel<true>, dim3(count), dim3(64), 0, s, d, c, env, out);
         else hipLaunchKernelGGL(brk_pack_kernel<false>, dim3(count), dim3(64), 0, s, d, c, env, out);
         TBX_HIP(hipGetLastError());
@@ -2360,12 +2319,12 @@ struct BreakoutOps : GameOps {
             int rc = enable_custom(e, s);
             if (rc) return rc;
         }
-        TBX_HIP(hipMemcpyAsync(e->staging, pod_host, sizeof(tbx_breakout_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
-        auto* in = (const tbx_breakout_state_t*)e->staging;
+        TBX_HIP(hipMemcpyAsync(e->staging.p, pod_host, sizeof(tbx_breakout_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
+        auto* in = (const tbx_breakout_state_t*)e->staging.p;
         if (custom) hipLaunchKernelGGL(brk_unpack_kernel<true>, dim3(count), dim3(64), 0, s, d, env, in);
         else hipLaunchKernelGGL(brk_unpack_kernel<false>, dim3(count), dim3(64), 0, s, d, env, in);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 
@@ -2380,7 +2339,7 @@ struct BreakoutOps : GameOps {
         if (custom) hipLaunchKernelGGL(brk_edit_kernel<true>, grid, block, 0, s, d, c.n_rows, op, a, mask_dev);
         else hipLaunchKernelGGL(brk_edit_kernel<false>, grid, block, 0, s, d, c.n_rows, op, a, mask_dev);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 
@@ -2400,7 +2359,7 @@ struct BreakoutOps : GameOps {
         plan.rows(recsB, sizeof(BrkRenderRec));
         plan.rows(keepA, sizeof(BrkRenderRec));        // (an env copied while its observation is the kept buffer's: mode 2 travels too)
         plan.rows(keepB, sizeof(BrkRenderRec));
-        recs_valid = false;
+        recs.valid = false;
     }
 
     int reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s) override

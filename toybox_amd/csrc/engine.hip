@@ -1,7 +1,8 @@
 // engine.hip -- the C-ABI of include/toybox_amd.h over the per-game gfx950 kernels.
 // No CPU fallback: every entry point that computes needs a visible gfx950 device.
 
-#include "tbx_common.hpp"
+#include "engine_host.hpp"
+#include "pipeline.hpp"
 #include <emmintrin.h>   // host side only: tbx_host_stack_push
 
 #include <sched.h>
@@ -19,9 +20,6 @@ int tbx_agent_buffer(tbx_engine* e, int which, void** out_ptr, size_t* out_bytes
 namespace {
 
 thread_local std::string g_create_error;
-
-#define CHECK_ENGINE(e) \
-    if (!(e)) return TBX_E_INVALID
 
 }  // namespace
 
@@ -51,18 +49,23 @@ hipError_t tbx_packed_leaves_chunk(tbx_engine* e, hipStream_t s)
     return hipSuccess;
 }
 
-namespace {
-
-int hip_fail(tbx_engine* e, const char* what, hipError_t err)
+int ensure_frame(tbx_engine* e, size_t bytes)
 {
-    return e->fail(TBX_E_NO_DEVICE, std::string(what) + ": " + hipGetErrorString(err));
+    EHIP(e->frame_own.reserve(bytes));
+    e->frame = e->frame_own.p;
+    e->frame_bytes = bytes;                                    // TBX_BUF_FRAME: the size of the frame it names, not of the allocation
+    return TBX_OK;
 }
 
-#define EHIP(call)                                        \
-    do {                                                  \
-        hipError_t _e = (call);                           \
-        if (_e != hipSuccess) return hip_fail(e, #call, _e); \
-    } while (0)
+// the buffers of chunk parity q of tbx_rollout_synthetic: k frames and, unless a ring of the gather takes them, k rows of step records
+int chunk_buffers(tbx_engine* e, int q, int k, size_t frame_bytes, bool want_packed, hipStream_t sync_a, hipStream_t sync_b)
+{
+    EHIP(e->rollout.frames[q].reserve((size_t)k * frame_bytes, sync_a, sync_b));
+    if (want_packed) EHIP(e->rollout.packed[q].reserve(sizeof(uint64_t) * (size_t)k * (size_t)e->n, sync_a, sync_b));
+    return TBX_OK;
+}
+
+namespace {
 
 void breakout_default_config(tbx_breakout_config_t* c)
 {
@@ -213,20 +216,6 @@ __global__ void fill_rng_kernel(uint64_t* sim_rng, int n, uint64_t s0, uint64_t 
     sim_rng[(size_t)n + i] = s1;
 }
 
-int ensure_frame(tbx_engine* e, size_t bytes)
-{
-    if (e->frame_own_bytes < bytes) {
-        if (e->frame_own) hipFree(e->frame_own);
-        e->frame_own = nullptr;
-        e->frame_own_bytes = 0;
-        EHIP(hipMalloc((void**)&e->frame_own, bytes));
-        e->frame_own_bytes = bytes;
-    }
-    e->frame = e->frame_own;
-    e->frame_bytes = bytes;                                    // TBX_BUF_FRAME: the size of the frame it names, not of the allocation
-    return TBX_OK;
-}
-
 int check_err_flag(tbx_engine* e)
 {
     uint32_t f = 0;
@@ -308,38 +297,22 @@ int tbx_destroy(tbx_engine* e)
     if (e->serve_ctl) hipHostFree(e->serve_ctl);
     if (e->serve_frame) hipHostFree(e->serve_frame);
     if (e->stream) hipStreamSynchronize(e->stream);
-    TbxPipe& pp = e->pipe;
-    for (int k = 0; k < 2; k++)
-        if (pp.lane[k] && pp.lane[k] != e->stream) hipStreamSynchronize(pp.lane[k]);
-    if (pp.step_lane) hipStreamSynchronize(pp.step_lane);
+    pipe_drain(e);
     tbx_gather_free(e);
     tbx_agent_free(e);
     if (e->ops) { e->ops->destroy(e); delete e->ops; }
     hipFree(e->sim_rng); hipFree(e->prev_score);
     for (int k = 0; k < 2; k++) {
         hipFree(e->outs[k].reward); hipFree(e->outs[k].done); hipFree(e->outs[k].lives); hipFree(e->outs[k].score); hipFree(e->outs[k].packed);
-        hipFree(pp.frame[k]);
-        if (pp.render_ev[k]) hipEventDestroy(pp.render_ev[k]);
-        if (pp.user_step_ev[k]) hipEventDestroy(pp.user_step_ev[k]);
-        if (pp.user_frame_ev[k]) hipEventDestroy(pp.user_frame_ev[k]);
-        if (pp.launch_ev[k]) hipEventDestroy(pp.launch_ev[k]);
-        if (pp.lane[k] && pp.lane[k] != e->stream) hipStreamDestroy(pp.lane[k]);
+        e->rollout.frames[k].release(); e->rollout.packed[k].release();
     }
-    hipFree(pp.arrive);
-    if (pp.step_lane) { hipStreamSynchronize(pp.step_lane); hipStreamDestroy(pp.step_lane); }
-    for (int q = 0; q < 2; q++) {
-        hipFree(pp.chunk_frames[q]); hipFree(pp.chunk_packed[q]);
-        if (pp.chunk_step_ev[q]) hipEventDestroy(pp.chunk_step_ev[q]);
-        for (int l = 0; l < 2; l++)
-            if (pp.chunk_raster_ev[q][l]) hipEventDestroy(pp.chunk_raster_ev[q][l]);
-    }
+    pipe_free(e);
     hipFree(e->actions);
-    hipFree(e->edit_args); hipFree(e->reduce_out); hipFree(e->fork_scratch);
-    hipFree(e->mask); hipFree(e->err_flag); hipFree(e->frame_own); hipFree(e->staging); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
+    e->edit_args.release(); e->reduce_out.release(); e->fork_scratch.release(); e->frame_own.release(); e->staging.release();
+    hipFree(e->mask); hipFree(e->err_flag); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
     if (e->io_host) hipHostFree(e->io_host);
     if (e->scal_host) hipHostFree(e->scal_host);
     if (e->order_ev) hipEventDestroy(e->order_ev);
-    if (pp.step_ev) hipEventDestroy(pp.step_ev);
     if (e->stream) hipStreamDestroy(e->stream);
     delete e;
     return TBX_OK;
@@ -422,8 +395,7 @@ int tbx_create(int game, int n_envs, int device, const void* config_pod, size_t 
     CHIP(hipMemsetAsync(e->reward, 0, N * sizeof(int32_t), e->stream));
     CHIP(hipMemsetAsync(e->done, 0, N, e->stream));
     CHIP(hipMemsetAsync(e->packed, 0, N * sizeof(uint64_t), e->stream));
-    e->staging_bytes = e->ops->state_size();
-    CHIP(hipMalloc(&e->staging, e->staging_bytes));
+    CHIP(e->staging.reserve(e->ops->state_size()));
 
     // config: NULL -> game defaults
     std::vector<uint8_t> cfg(e->ops->config_size());
@@ -539,492 +511,6 @@ int tbx_step_device(tbx_engine* e, const int32_t* actions_dev, uint32_t flags, v
     src.actions = actions_dev;
     src.single_env = -1;
     return e->ops->step(e, src, flags, (hipStream_t)stream);
-}
-
-// ---- pipelined mode (TBX_OPT_PIPELINE; contract in include/toybox_amd.h)
-//
-// A step with in-kernel actions depends on nothing the previous frame's rasteriser produces, and for games whose rasteriser
-// reads step-written records (GameOps::pipeline_ok) it disturbs nothing that rasteriser reads once there are two buffers of
-// records and of step outputs: it runs on the engine's step stream BESIDE the render queued before it.  Measured on MI355X
-// (scripts/interleave_probe.py): a 10 us step kernel serialised between two 1.19 ms Breakout render launches costs
-// 0.04-0.22 ms depending on the box, run beside the render it costs 0.01-0.04 ms.  With value 3 consecutive renders into the
-// engine-owned frame buffer alternate between two internal streams and two buffers as well, so that launch N+1 ramps up in
-// the ramp-down of launch N.
-//
-// Streams.  Value 2: one internal step stream; renders stay on the caller's stream U.  Value 3: two internal streams S[0],
-// S[1]; step N and the overlapped render N both go to S[p], p = the parity of the buffers step N writes -- so render N is
-// behind its step, behind render N-2 (same frame buffer) and behind step N-2 / render N-2's reads of records p by stream order
-// alone, and runs beside render N-1 on the other stream.  (Few streams on purpose: the runtime multiplexes streams onto a
-// handful of hardware queues -- GPU_MAX_HW_QUEUES, 4 by default -- and two streams that share one queue do not overlap.)
-//
-// Who waits for whom beyond stream order (U = the stream the caller names):
-//   step N   (writes records / outputs p)   <- step N-1 (the state; other stream in value 3), a render of records p that ran
-//                                              elsewhere, U's readers of outputs p (fence recorded on U at step N-1's call),
-//                                              the gather that read outputs p
-//   render N on U (value 2, or out_dev given) <- nothing: U waits for every step
-//   render N on S[p] (value 3)              <- U's readers of frame buffer p (fence recorded on U at render N-1's call)
-//   U                                        <- every step and every overlapped render (so whatever the caller queues next
-//                                              sees them, and U is the tail that calls of any other kind join)
-static int pipe_mode(const tbx_engine* e)
-{
-    const int v = e->opt[TBX_OPT_PIPELINE];
-    if (v == 0 || e->gather_ring || !e->ops->pipeline_ok()) return 0;      // (the K-step record ring moves the one record pointer)
-    if (v == 1) return e->ops->pipeline_auto(e->n, e->gather != nullptr);
-    return v;
-}
-
-static int pipe_prepare(tbx_engine* e)
-{
-    TbxPipe& p = e->pipe;
-    if (p.prepared) return TBX_OK;
-    // every resource is made only while it is still missing, so that a call that failed half way can be repeated without
-    // leaking what the first attempt got; `prepared` is set last
-    const size_t N = (size_t)e->n;
-    TbxStepOut& o = e->outs[1];
-    if (!o.reward) { EHIP(hipMalloc((void**)&o.reward, N * sizeof(int32_t))); EHIP(hipMemset(o.reward, 0, N * sizeof(int32_t))); }
-    if (!o.done) { EHIP(hipMalloc((void**)&o.done, N)); EHIP(hipMemset(o.done, 0, N)); }
-    if (!o.lives) { EHIP(hipMalloc((void**)&o.lives, N * sizeof(int32_t))); EHIP(hipMemset(o.lives, 0, N * sizeof(int32_t))); }
-    if (!o.score) { EHIP(hipMalloc((void**)&o.score, N * sizeof(int32_t))); EHIP(hipMemset(o.score, 0, N * sizeof(int32_t))); }
-    if (!o.packed) { EHIP(hipMalloc((void**)&o.packed, N * sizeof(uint64_t))); EHIP(hipMemset(o.packed, 0, N * sizeof(uint64_t))); }
-    if (!p.step_ev) EHIP(hipEventCreateWithFlags(&p.step_ev, hipEventDisableTiming));
-    for (int k = 0; k < 2; k++) {
-        if (!p.render_ev[k]) EHIP(hipEventCreateWithFlags(&p.render_ev[k], hipEventDisableTiming));
-        if (!p.user_step_ev[k]) EHIP(hipEventCreateWithFlags(&p.user_step_ev[k], hipEventDisableTiming));
-        if (!p.user_frame_ev[k]) EHIP(hipEventCreateWithFlags(&p.user_frame_ev[k], hipEventDisableTiming));
-        if (!p.launch_ev[k]) EHIP(hipEventCreateWithFlags(&p.launch_ev[k], hipEventDisableTiming));
-    }
-    for (int q = 0; q < 2; q++) {
-        if (!p.chunk_step_ev[q]) EHIP(hipEventCreateWithFlags(&p.chunk_step_ev[q], hipEventDisableTiming));
-        for (int l = 0; l < 2; l++)
-            if (!p.chunk_raster_ev[q][l]) EHIP(hipEventCreateWithFlags(&p.chunk_raster_ev[q][l], hipEventDisableTiming));
-    }
-    if (!p.arrive) {
-        EHIP(hipMalloc((void**)&p.arrive, 2 * sizeof(unsigned long long)));
-        EHIP(hipMemset(p.arrive, 0, 2 * sizeof(unsigned long long)));
-        p.arrive_want = p.release_want = 0;
-    }
-    // The two internal streams are created with the highest priority.  Not for the priority's sake: the runtime multiplexes the
-    // streams of a process onto a few hardware queues PER PRIORITY LEVEL (GPU_MAX_HW_QUEUES, 4 by default), two streams that
-    // land on one queue do not overlap, and which streams share depends on the creation history of the whole process.  The
-    // high-priority pool is the lanes' own (measured: with ordinary streams the overlapped modes were faster or slower than
-    // the serial loop from one process to the next; scripts/pipeline_sweep.py).
-    int lo = 0, hi = 0;
-    EHIP(hipDeviceGetStreamPriorityRange(&lo, &hi));     // numerically hi <= lo
-#ifdef TBX_DIAG
-    if (getenv("TBX_LANE_PRIORITY")) hi = atoi(getenv("TBX_LANE_PRIORITY")) ? lo : hi;      // measurement builds: ordinary streams
-#endif
-    for (int k = 0; k < 2; k++)
-        if (!p.lane[k]) EHIP(hipStreamCreateWithPriority(&p.lane[k], hipStreamNonBlocking, hi));
-    if (!p.step_lane) EHIP(hipStreamCreateWithPriority(&p.step_lane, hipStreamNonBlocking, hi));   // (three of the priority level's four hardware queues)
-    p.prepared = true;
-    return TBX_OK;
-}
-
-// the first pipelined call after a call of any other kind: every internal stream behind all that came before
-enum { PIPE_STEPS_AND_RENDERS = 0, PIPE_FUSED_OVERLAP = 1, PIPE_ROLLOUT_CHUNKS = 2 };
-
-static int pipe_enter(tbx_engine* e, int kind = PIPE_STEPS_AND_RENDERS)
-{
-    TbxPipe& p = e->pipe;
-    const bool fused = kind == PIPE_FUSED_OVERLAP, rollout = kind == PIPE_ROLLOUT_CHUNKS;
-    if (e->pending_kind) EHIP(tbx_finish_pending(e));           // (a host-delivery step between its begin and end calls)
-    // pipelined steps / renders, overlapped fused launches and rollout chunks keep different books on the same lanes: a change of
-    // kind joins first (tbx_use_stream makes the stream of the last call wait for every internal launch; the lanes re-enter behind it)
-    if (p.active && (p.fused != fused || p.rollout != rollout)) EHIP(tbx_use_stream(e, e->last_stream));
-    if (p.active) return TBX_OK;
-    if (e->serve_running) EHIP(tbx_serve_stop(e));
-    int rc = pipe_prepare(e);
-    if (rc) return rc;
-    EHIP(tbx_wait_tail(e, p.lane[0]));
-    EHIP(tbx_wait_tail(e, p.lane[1]));
-    if (rollout) EHIP(tbx_wait_tail(e, p.step_lane));
-    for (int k = 0; k < 2; k++) { p.render_pending[k] = p.user_step_rec[k] = p.user_frame_rec[k] = false; p.render_on[k] = nullptr; }
-    p.step_outstanding = false;
-    p.step_on = nullptr;
-    p.step_user = nullptr;
-    p.frame_par = -1;
-    p.live_reader = -1;
-    p.fused = fused;
-    p.rollout = rollout;
-    p.prev_overlapped = false;
-    p.launch_rec[0] = p.launch_rec[1] = false;
-    p.user_waits[0] = p.user_waits[1] = false;
-    p.reader_seen = false;
-    for (int q = 0; q < 2; q++) { p.chunk_step_rec[q] = p.chunk_raster_rec[q][0] = p.chunk_raster_rec[q][1] = p.chunk_user_waits[q] = false; }
-    p.active = true;
-    return TBX_OK;
-}
-
-static int pipe_step(tbx_engine* e, const ActionSource& src, uint32_t flags, hipStream_t user, int mode)
-{
-    int rc = pipe_enter(e);
-    if (rc) return rc;
-    TbxPipe& p = e->pipe;
-    const int cur = e->out_par, wp = cur ^ 1;                  // this step writes output set wp ...
-    const int rw = e->ops->records_parity() ^ 1;               // ... and records buffer rw
-    hipStream_t ss = mode == 3 ? p.lane[wp] : p.lane[0];
-    if (p.step_outstanding && p.step_on != ss) EHIP(hipStreamWaitEvent(ss, p.step_ev, 0));          // the state step N-1 left
-    if (p.render_pending[rw]) {                                                                      // the reader of records rw
-        if (p.render_on[rw] != ss) EHIP(hipStreamWaitEvent(ss, p.render_ev[rw], 0));
-        p.render_pending[rw] = false;
-    }
-    if (p.user_step_rec[wp]) { EHIP(hipStreamWaitEvent(ss, p.user_step_ev[wp], 0)); p.user_step_rec[wp] = false; }
-    // A render issued while the records did not reflect the state (after new_game / set_state / a single-env step) read LIVE
-    // state -- the prep kernel that rebuilds the records, or a state-reading rasteriser -- on its own stream: this step, which
-    // rewrites that state, goes behind it (it only waited for the reader of the OTHER records buffer).
-    if (p.live_reader >= 0) {
-        if (p.render_on[p.live_reader] != ss) EHIP(hipStreamWaitEvent(ss, p.render_ev[p.live_reader], 0));
-        p.live_reader = -1;
-    }
-    // whatever the caller has queued so far may read the current outputs: the step after this one waits for it
-    EHIP(hipEventRecord(p.user_step_ev[cur], user));
-    p.user_step_rec[cur] = true;
-    tbx_set_out_parity(e, wp);
-    hipError_t ge = tbx_gather_before_step(e, ss);
-    rc = ge == hipSuccess ? e->ops->step_ahead(e, src, flags, ss) : hip_fail(e, "tbx_gather_before_step", ge);
-    if (rc) {                                                  // nothing was launched: TBX_BUF_* keep naming the set that holds results
-        tbx_set_out_parity(e, cur);
-        return rc;
-    }
-    EHIP(hipEventRecord(p.step_ev, ss));
-    EHIP(hipStreamWaitEvent(user, p.step_ev, 0));
-    p.step_outstanding = true;
-    p.step_on = ss;
-    p.step_user = user;
-    e->last_stream = user;
-    e->has_last = true;
-    return TBX_OK;
-}
-
-static int pipe_render(tbx_engine* e, uint8_t* out_dev, int channels, hipStream_t user, int mode)
-{
-    int rc = pipe_enter(e);
-    if (rc) return rc;
-    TbxPipe& p = e->pipe;
-    const int rp = e->ops->records_parity();
-    const bool overlap = mode == 3 && out_dev == nullptr;
-    const size_t bytes = (size_t)e->n * e->ops->height() * e->ops->width() * channels;
-    hipStream_t rs = user;
-    if (overlap) {
-        const int fp = rp;                                     // frame buffer and stream follow the records' parity
-        rs = p.lane[fp];
-        if (p.frame_bytes[fp] < bytes) {
-            EHIP(hipStreamSynchronize(rs));
-            if (p.frame[fp]) hipFree(p.frame[fp]);
-            p.frame[fp] = nullptr;
-            p.frame_bytes[fp] = 0;
-            EHIP(hipMalloc((void**)&p.frame[fp], bytes));
-            p.frame_bytes[fp] = bytes;
-        }
-        if (p.step_outstanding && p.step_on != rs) EHIP(hipStreamWaitEvent(rs, p.step_ev, 0));
-        // Readers of a frame are queued on U before the next render call.  Fence what is there now; the render into the OTHER
-        // buffer waits for the fence of the call before (readers of what that buffer held), a second render into the SAME
-        // buffer for the one just recorded.
-        const int prev = p.frame_par < 0 ? fp ^ 1 : p.frame_par;
-        EHIP(hipEventRecord(p.user_frame_ev[prev], user));
-        p.user_frame_rec[prev] = true;
-        if (p.user_frame_rec[fp]) { EHIP(hipStreamWaitEvent(rs, p.user_frame_ev[fp], 0)); p.user_frame_rec[fp] = false; }
-        out_dev = p.frame[fp];
-    } else {
-        // on the caller's stream: it waits for the step unless it is the stream the step call named (pipe_step made that one wait)
-        if (p.step_outstanding && p.step_user != user) EHIP(hipStreamWaitEvent(rs, p.step_ev, 0));
-        if (!out_dev) {
-            rc = ensure_frame(e, bytes);
-            if (rc) return rc;
-            out_dev = e->frame_own;
-        }
-    }
-    if (((uintptr_t)out_dev & 15u) != 0) return e->fail(TBX_E_INVALID, "frame buffer must be 16-byte aligned");
-    if (p.render_pending[rp] && p.render_on[rp] != rs) EHIP(hipStreamWaitEvent(rs, p.render_ev[rp], 0));   // (another render of these records)
-    const bool reads_live = !e->ops->records_valid();          // the launch below starts from live state (pipe_step waits for it)
-    rc = e->ops->render(e, out_dev, channels, 0, e->n, rs);
-    if (rc) return rc;
-    EHIP(hipEventRecord(p.render_ev[rp], rs));
-    p.render_pending[rp] = true;
-    p.render_on[rp] = rs;
-    if (reads_live) p.live_reader = rp;
-    if (overlap) {
-        EHIP(hipStreamWaitEvent(user, p.render_ev[rp], 0));
-        p.frame_par = rp;
-        e->frame = p.frame[rp];
-        e->frame_bytes = bytes;
-    } else if (out_dev == e->frame_own) {
-        e->frame = e->frame_own;
-        e->frame_bytes = bytes;
-    }
-    e->last_stream = user;
-    e->has_last = true;
-    return TBX_OK;
-}
-
-// ---- overlapped fused launches (TBX_OPT_FUSED_OVERLAP; contract in include/toybox_amd.h)
-//
-// Launch N of a loop of tbx_render_step_synthetic calls = [step blocks: state t -> t+1, records R[b], outputs O[wp]] +
-// [rasteriser blocks: R[a] -> frame F[wp]].  Launch N+1 needs the step blocks of launch N and nothing else of it, so it goes to
-// the OTHER lane (a stream per parity, like value 3 of the pipelined mode) behind a one-wave kernel that waits until the device
-// counter `arrive` says those blocks are through (they fence and bump it last).  The launch itself never waits: a grid that
-// spins could fill the chip before the launch it waits for has been dispatched.  Hazards and who orders them:
-//   state, O[wp] written by step N, read / rewritten by step N+1     the counter (+ an acquire fence at the head of every wave)
-//   R[b] written by step N, read by rasteriser N+1                   the counter
-//   R[a] read by rasteriser N, rewritten by step N+2 (three buffers) stream order: N and N+2 share a lane
-//   F[wp], O[wp] written by N, rewritten by N+2                       stream order; their READERS on the caller's stream U by the
-//                                                                    fence recorded on U at call N+1 (user_step_ev), awaited by N+2
-//   the collective that reads O[wp] / a ring                          tbx_gather waits for both lanes' completion events;
-//                                                                    tbx_gather_before_step makes the rewriting launch wait for it
-//   U                                                                 waits for every launch's completion event (what the caller
-//                                                                    queues next sees the results; calls of other kinds join through U)
-// Measured (scripts/ubench/overlap_ticket.hip, a stand-in launch, ms per launch serial / completion-event dependency / this /
-// hipStreamWaitValue64 on the counter): 4 096 envs 0.0920 / 0.0982 / 0.0887 / 0.0886, 8 192: 0.1854 / 0.1917 / 0.1794 / 0.1791,
-// 65 536: 1.555 / 1.560 / 1.477 / 1.483 -- the wait kernel costs nothing against the command processor's own (beta) wait.
-__global__ void tbx_ticket_wait_kernel(const unsigned long long* arrive, unsigned long long want_steps, unsigned long long want_releases, uint32_t* err_flag)
-{
-    if (threadIdx.x != 0) return;
-    const unsigned long long t0 = wall_clock64();
-    // (relaxed: what has to be seen behind the counter is read with agent-scope loads by the launch that follows)
-    while (__hip_atomic_load(arrive + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want_releases ||
-           __hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want_steps) {
-        __builtin_amdgcn_s_sleep(2);
-        if (wall_clock64() - t0 > 300000000ull) { atomicOr(err_flag, 4u); return; }   // 3 s of the 100 MHz clock: report, never hang
-    }
-}
-
-// the caller asks where a result of the last call lies: the stream that call named now waits for the launch that wrote it
-static int fused_reader_joins(tbx_engine* e)
-{
-    TbxPipe& p = e->pipe;
-    if (!p.active || !p.fused) return TBX_OK;
-    const int k = e->out_par;
-    if (p.launch_rec[k] && !p.user_waits[k]) {
-        EHIP(hipSetDevice(e->device));
-        EHIP(hipStreamWaitEvent(e->last_stream, p.launch_ev[k], 0));
-        p.user_waits[k] = true;
-    }
-    p.reader_seen = true;
-    return TBX_OK;
-}
-
-static bool fused_overlap_on(const tbx_engine* e, const uint8_t* out_dev, int channels)
-{
-    const int v = e->opt[TBX_OPT_FUSED_OVERLAP];
-    if (v == 2 || out_dev != nullptr || !e->ops->render_step_fused(channels)) return false;
-    return v == 1 || e->ops->fused_overlap_auto(e->n, !e->gather ? 0 : e->gather_ring ? 2 : 1);
-}
-
-static int fused_overlapped(tbx_engine* e, int channels, const ActionSource& src, uint32_t flags, hipStream_t user)
-{
-    int rc = pipe_enter(e, PIPE_FUSED_OVERLAP);
-    if (rc) return rc;
-    TbxPipe& p = e->pipe;
-    const int cur = e->out_par, wp = cur ^ 1;                  // this launch writes output set wp and frame buffer wp, on lane wp
-#ifdef TBX_DIAG
-    const int diag = getenv("TBX_OVERLAP_DIAG") ? atoi(getenv("TBX_OVERLAP_DIAG")) : 0;
-#else
-    const int diag = 0;
-#endif
-    hipStream_t ls = p.lane[OVL_DIAG(diag, 8) ? 0 : wp];
-    const int fb = OVL_DIAG(diag, 32) ? 0 : wp;
-    const size_t bytes = (size_t)e->n * e->ops->height() * e->ops->width() * channels;
-    if (p.frame_bytes[fb] < bytes) {
-        EHIP(hipStreamSynchronize(ls));
-        if (p.frame[fb]) hipFree(p.frame[fb]);
-        p.frame[fb] = nullptr;
-        p.frame_bytes[fb] = 0;
-        EHIP(hipMalloc((void**)&p.frame[fb], bytes));
-        p.frame_bytes[fb] = bytes;
-    }
-    // Readers of what call N-2 left in set / frame wp were queued on U before call N-1, which fenced them; this call fences the
-    // readers of call N-1's results for call N+1 -- if there can be any: U joined lazily (fused_reader_joins), and a caller
-    // that took no address since the last call has queued no reader.
-    if (p.user_step_rec[wp]) { EHIP(hipStreamWaitEvent(ls, p.user_step_ev[wp], 0)); p.user_step_rec[wp] = false; }
-    if (p.reader_seen || OVL_DIAG(diag, 16)) {
-        EHIP(hipEventRecord(p.user_step_ev[cur], user));
-        p.user_step_rec[cur] = true;
-        p.reader_seen = false;
-    }
-    uint64_t* const ring_slot = e->gather_ring ? e->packed : nullptr;      // (a K-step ring owns the record pointer)
-    tbx_set_out_parity(e, wp);
-    if (ring_slot) { e->packed = ring_slot; e->ops->rebind_outputs(e); }
-    auto undo = [&]() { tbx_set_out_parity(e, cur); if (ring_slot) { e->packed = ring_slot; e->ops->rebind_outputs(e); } };
-    hipError_t ge = tbx_gather_before_step(e, ls);
-    if (ge != hipSuccess) { undo(); return hip_fail(e, "tbx_gather_before_step", ge); }
-    if (p.prev_overlapped && !OVL_DIAG(diag, 64)) {
-        hipLaunchKernelGGL(tbx_ticket_wait_kernel, dim3(1), dim3(64), 0, ls, p.arrive, p.arrive_want, p.release_want, e->err_flag);
-        ge = hipGetLastError();
-        if (ge != hipSuccess) { undo(); return hip_fail(e, "tbx_ticket_wait_kernel", ge); }
-    }
-    TbxOverlapLaunch ov{p.arrive, p.launch_ev[wp], e->opt[TBX_OPT_FUSED_OVERLAP_LEAD], 0, diag};
-    rc = e->ops->render_step(e, p.frame[fb], channels, src, flags, ls, &ov);
-    if (rc) { undo(); return rc; }                             // nothing was launched: TBX_BUF_* keep naming the set that holds results
-    p.arrive_want += (unsigned long long)ov.step_blocks;
-    p.release_want += 1;
-    p.prev_overlapped = true;
-    p.launch_rec[wp] = true;
-    if (OVL_DIAG(diag, 128)) EHIP(hipEventRecord(p.launch_ev[wp], ls));
-    p.user_waits[wp] = false;
-    if (OVL_DIAG(diag, 16)) { EHIP(hipStreamWaitEvent(user, p.launch_ev[wp], 0)); p.user_waits[wp] = true; }    // (DIAG: the eager join of the first build)
-    e->frame = p.frame[fb];
-    e->frame_bytes = bytes;
-    e->step_carries_order_ev = false;
-    e->last_stream = user;
-    e->has_last = true;
-    return TBX_OK;
-}
-
-// ---- rollout chunks (tbx_rollout_synthetic; contract in include/toybox_amd.h, TbxPipe::rollout)
-//
-// Chunk c (parity q = c & 1) of k frames:
-//   step lane   T_c: ONE launch steps every env k frames with the state in registers; it writes the k render records R[q][0..k-1]
-//               (record j = the state before frame j), the k step records (straight into a ring of the gather, or an engine-owned
-//               [k][N] array) and the state.  It is ordered behind T_{c-1} by the lane, behind the rasterisers of chunk c-2 (they read
-//               R[q]), behind the collective that last read the ring, behind the caller's readers of output set q.
-//   lanes 0, 1  the rasteriser launches R[q][j] -> F[q][j]: k plain ones, launch j on lane j & 1, or ONE over the chunk's k x N frames
-//               on lane 0 (GameOps::rollout_render_span; below).  They wait for T_c and for nothing else -- and T_{c+1} has the whole
-//               length of these launches to finish beside them.  No launch ever waits for a step that is
-//               running beside a rasteriser (a Breakout step kernel that takes 10 us alone takes 100-250 us there -- what made the
-//               device-side ticket of overlapped fused launches wait for most of the launch before it).
-//   collective  (K-step ring, K = k) behind T_c alone: it runs beside the chunk's rasterisers.
-//   caller      joins lazily (tbx_device_buffer), as with overlapped fused launches.
-static bool rollout_chunks_on(const tbx_engine* e, int channels)
-{
-    const int v = e->opt[TBX_OPT_ROLLOUT_CHUNKS];
-    if (v == 2 || !e->ops->rollout_ok(channels)) return false;
-    if (e->gather && !e->gather_ring) return false;              // one collective per step: k collectives cannot ride on one launch
-    return v == 1 || v >= 3 || e->ops->rollout_auto(e->n, !e->gather ? 0 : e->gather_ring ? 2 : 1);
-}
-
-static int chunk_buffers(tbx_engine* e, int q, int k, size_t frame_bytes, bool want_packed, hipStream_t sync_a, hipStream_t sync_b)
-{
-    TbxPipe& p = e->pipe;
-    if (p.chunk_frame_bytes[q] < (size_t)k * frame_bytes) {
-        if (sync_a) EHIP(hipStreamSynchronize(sync_a));
-        if (sync_b) EHIP(hipStreamSynchronize(sync_b));
-        if (p.chunk_frames[q]) hipFree(p.chunk_frames[q]);
-        p.chunk_frames[q] = nullptr;
-        p.chunk_frame_bytes[q] = 0;
-        EHIP(hipMalloc((void**)&p.chunk_frames[q], (size_t)k * frame_bytes));
-        p.chunk_frame_bytes[q] = (size_t)k * frame_bytes;
-    }
-    const size_t pb = sizeof(uint64_t) * (size_t)k * (size_t)e->n;
-    if (want_packed && p.chunk_packed_bytes[q] < pb) {
-        if (sync_a) EHIP(hipStreamSynchronize(sync_a));
-        if (sync_b) EHIP(hipStreamSynchronize(sync_b));
-        if (p.chunk_packed[q]) hipFree(p.chunk_packed[q]);
-        p.chunk_packed[q] = nullptr;
-        p.chunk_packed_bytes[q] = 0;
-        EHIP(hipMalloc((void**)&p.chunk_packed[q], pb));
-        p.chunk_packed_bytes[q] = pb;
-    }
-    return TBX_OK;
-}
-
-static int rollout_chunked(tbx_engine* e, int channels, const ActionSource& src, uint32_t flags, int k, hipStream_t user)
-{
-    int rc = pipe_enter(e, PIPE_ROLLOUT_CHUNKS);
-    if (rc) return rc;
-    TbxPipe& p = e->pipe;
-    const int cur = e->out_par, q = cur ^ 1;                   // this chunk: output set q, record buffer q, frame chunk q
-    hipStream_t ss = p.step_lane;
-    const size_t fb = (size_t)e->n * e->ops->height() * e->ops->width() * channels;
-    rc = chunk_buffers(e, q, k, fb, !e->gather_ring, p.lane[0], p.lane[1]);
-    if (rc) return rc;
-    uint64_t* packed = p.chunk_packed[q];
-    size_t stride = (size_t)e->n;
-    if (e->gather_ring) {
-        rc = tbx_gather_ring_open(e, ss, k, &packed, &stride);
-        if (rc) return rc;
-    }
-    // T_c behind the rasterisers of chunk c - 2, which read the record buffer it rewrites
-    for (int l = 0; l < 2; l++)
-        if (p.chunk_raster_rec[q][l]) EHIP(hipStreamWaitEvent(ss, p.chunk_raster_ev[q][l], 0));
-    // ... and behind the caller's readers of what chunk c - 2 left in output set q (fenced by call c - 1); the same fence holds the
-    // rasterisers below back from the frames those readers may still read.  This call fences the readers of chunk c - 1, if the
-    // caller took an address since (lazy join: no address, no reader)
-    const bool fenced = p.user_step_rec[q];
-    if (fenced) { EHIP(hipStreamWaitEvent(ss, p.user_step_ev[q], 0)); p.user_step_rec[q] = false; }
-    if (p.reader_seen) {
-        EHIP(hipEventRecord(p.user_step_ev[cur], user));
-        p.user_step_rec[cur] = true;
-        p.reader_seen = false;
-    }
-    tbx_set_out_parity(e, q);
-    e->packed = packed + (size_t)(k - 1) * stride;              // TBX_BUF_PACKED: the record of the chunk's last step
-    e->ops->rebind_outputs(e);
-    rc = e->ops->rollout_step(e, src, flags, k, q, packed, stride, ss);
-    if (rc) { tbx_set_out_parity(e, cur); return rc; }
-    EHIP(hipEventRecord(p.chunk_step_ev[q], ss));
-    p.chunk_step_rec[q] = true;
-    bool lane_used[2] = {false, false};
-    auto lane_for = [&](int l) -> int {
-        if (!lane_used[l]) {
-            EHIP(hipStreamWaitEvent(p.lane[l], p.chunk_step_ev[q], 0));
-            if (fenced) EHIP(hipStreamWaitEvent(p.lane[l], p.user_step_ev[q], 0));
-            lane_used[l] = true;
-        }
-        return TBX_OK;
-    };
-    const int form = e->opt[TBX_OPT_ROLLOUT_CHUNKS];
-    const bool span = e->ops->rollout_span_ok() && (form == 4 || (form != 3 && e->ops->rollout_span_auto(e->n, !e->gather ? 0 : 2)));
-    if (span) {
-        // The chunk's frames in ONE rasteriser launch (k x n frames; at most 65 536 frames per launch), chunk behind chunk on ONE internal
-        // stream: rasteriser launches back to back as in a render-only loop, k times as long as a frame's, the next chunk's step launch
-        // beside them on the step lane.  Nothing runs beside a rasteriser launch but that step launch, so the rate does not depend on where
-        // the frame buffers lie (two rasteriser launches side by side: 0.151-0.164 ms per step at 8 192 envs from process to process,
-        // this form 0.1533-0.1536 in every one; profiles/r06_experiments.txt item 6).
-        const int l = 0;
-        // is the previous chunk's launch still running on that stream?  Then this one starts like a launch of a render-only loop
-        bool behind = p.chunk_raster_rec[cur][l] && hipEventQuery(p.chunk_raster_ev[cur][l]) == hipErrorNotReady;
-        (void)hipGetLastError();                                // (hipErrorNotReady is an answer, not an error to keep)
-        rc = lane_for(l);
-        if (rc) return rc;
-        const int per = std::max(1, std::min(k, 65536 / std::max(1, e->n)));
-        for (int j0 = 0; j0 < k; j0 += per) {
-            rc = e->ops->rollout_render_span(e, p.chunk_frames[q] + (size_t)j0 * fb, channels, q, j0, std::min(per, k - j0), behind, p.lane[l]);
-            if (rc) return rc;
-            behind = true;
-        }
-    } else {
-        for (int j = 0; j < k; j++) {
-            const int l = j & 1;
-            rc = lane_for(l);
-            if (rc) return rc;
-            rc = e->ops->rollout_render(e, p.chunk_frames[q] + (size_t)j * fb, channels, q, j, p.lane[l]);
-            if (rc) return rc;
-        }
-    }
-    for (int l = 0; l < 2; l++) {
-        p.chunk_raster_rec[q][l] = lane_used[l];
-        if (lane_used[l]) EHIP(hipEventRecord(p.chunk_raster_ev[q][l], p.lane[l]));
-    }
-    if (e->gather_ring) {
-        rc = tbx_gather_ring_filled(e, p.chunk_step_ev[q]);
-        if (rc) return rc;
-    }
-    p.chunk_user_waits[q] = false;
-    p.chunk_cur = q; p.chunk_k = k; p.chunk_channels = channels;
-    p.chunk_packed_base = packed; p.chunk_packed_stride = stride;
-    e->frame = p.chunk_frames[q] + (size_t)(k - 1) * fb;        // TBX_BUF_FRAME: the chunk's last frame
-    e->frame_bytes = fb;
-    e->step_carries_order_ev = false;
-    e->last_stream = user;
-    e->has_last = true;
-    return TBX_OK;
-}
-
-// the caller asks where a result of the last chunk lies: the stream that call named now waits for the chunk (its step launch and,
-// for the frames, its rasterisers)
-static int rollout_reader_joins(tbx_engine* e, bool frames)
-{
-    TbxPipe& p = e->pipe;
-    if (!p.active || !p.rollout) return TBX_OK;
-    const int q = p.chunk_cur;
-    EHIP(hipSetDevice(e->device));
-    if (p.chunk_step_rec[q] && !p.chunk_user_waits[q]) EHIP(hipStreamWaitEvent(e->last_stream, p.chunk_step_ev[q], 0));
-    if (frames)
-        for (int l = 0; l < 2; l++)
-            if (p.chunk_raster_rec[q][l]) EHIP(hipStreamWaitEvent(e->last_stream, p.chunk_raster_ev[q][l], 0));
-    p.chunk_user_waits[q] = true;
-    p.reader_seen = true;
-    return TBX_OK;
 }
 
 int tbx_step_synthetic(tbx_engine* e, uint64_t action_seed, uint64_t t, uint64_t env_offset, uint32_t flags, void* stream)
@@ -1208,9 +694,9 @@ int tbx_step_begin(tbx_engine* e, const int32_t* actions_host, uint32_t flags, c
         const size_t bytes = N * e->ops->height() * e->ops->width() * out->channels;
         rc = ensure_frame(e, bytes);
         if (rc) return rc;
-        rc = e->ops->render(e, e->frame_own, out->channels, 0, e->n, e->stream);
+        rc = e->ops->render(e, e->frame_own.p, out->channels, 0, e->n, e->stream);
         if (rc) return rc;
-        EHIP(hipMemcpyAsync(out->frame, e->frame_own, bytes, hipMemcpyDeviceToHost, e->stream));
+        EHIP(hipMemcpyAsync(out->frame, e->frame_own.p, bytes, hipMemcpyDeviceToHost, e->stream));
     }
     e->host_out = *out;
     e->host_pending = true;
@@ -1417,12 +903,7 @@ static int fork_envs(tbx_engine* e, const TbxEditArgs& a, const uint8_t* mask_de
         g.scratch_off = scratch;
         scratch += ((size_t)g.fields * N * g.row_bytes + 255) & ~(size_t)255;
     }
-    if (!direct && e->fork_scratch_bytes < scratch) {
-        EHIP(hipFree(e->fork_scratch));                        // (waits for whatever still reads it)
-        e->fork_scratch = nullptr; e->fork_scratch_bytes = 0;
-        EHIP(hipMalloc((void**)&e->fork_scratch, scratch));
-        e->fork_scratch_bytes = scratch;
-    }
+    if (!direct) EHIP(e->fork_scratch.reserve(scratch));       // (freeing the old one waits for whatever still reads it)
     const dim3 sgrid((unsigned)((N + 255) / 256)), sblock(256);
     const dim3 rgrid(std::min((unsigned)((N + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK), FORK_MAX_BLOCKS)), rblock(TBX_BLOCK);
     std::vector<ForkBatch> batches;
@@ -1435,14 +916,14 @@ static int fork_envs(tbx_engine* e, const TbxEditArgs& a, const uint8_t* mask_de
             bool sc = false, rw = false;
             for (int k = 0; k < b.n_segs; k++) (b.seg[k].row_bytes <= 8 ? sc : rw) = true;
             if (sc) {
-                if (phase == 0) hipLaunchKernelGGL(fork_scalars_kernel<0>, sgrid, sblock, 0, s, b, e->fork_scratch, a, mask_dev, e->n);
-                else if (phase == 1) hipLaunchKernelGGL(fork_scalars_kernel<1>, sgrid, sblock, 0, s, b, e->fork_scratch, a, mask_dev, e->n);
-                else hipLaunchKernelGGL(fork_scalars_kernel<2>, sgrid, sblock, 0, s, b, e->fork_scratch, a, mask_dev, e->n);
+                if (phase == 0) hipLaunchKernelGGL(fork_scalars_kernel<0>, sgrid, sblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
+                else if (phase == 1) hipLaunchKernelGGL(fork_scalars_kernel<1>, sgrid, sblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
+                else hipLaunchKernelGGL(fork_scalars_kernel<2>, sgrid, sblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
             }
             if (rw) {
-                if (phase == 0) hipLaunchKernelGGL(fork_rows_kernel<0>, rgrid, rblock, 0, s, b, e->fork_scratch, a, mask_dev, e->n);
-                else if (phase == 1) hipLaunchKernelGGL(fork_rows_kernel<1>, rgrid, rblock, 0, s, b, e->fork_scratch, a, mask_dev, e->n);
-                else hipLaunchKernelGGL(fork_rows_kernel<2>, rgrid, rblock, 0, s, b, e->fork_scratch, a, mask_dev, e->n);
+                if (phase == 0) hipLaunchKernelGGL(fork_rows_kernel<0>, rgrid, rblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
+                else if (phase == 1) hipLaunchKernelGGL(fork_rows_kernel<1>, rgrid, rblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
+                else hipLaunchKernelGGL(fork_rows_kernel<2>, rgrid, rblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
             }
         }
     };
@@ -1698,13 +1179,13 @@ int tbx_rollout_synthetic(tbx_engine* e, int channels, uint64_t action_seed, uin
     // everywhere else: the k single calls in stream order, frames into chunk buffer 0, the step records into the ring (K-step ring:
     // tbx_gather after every step, the k-th one sends it) or copied out of TBX_BUF_PACKED after every step
     EHIP(tbx_use_stream(e, s));
-    TbxPipe& p = e->pipe;
+    TbxRolloutResult& p = e->rollout;
     const size_t fb = (size_t)e->n * e->ops->height() * e->ops->width() * channels;
     int rc = chunk_buffers(e, 0, k, fb, !e->gather_ring, s, nullptr);
     if (rc) return rc;
     uint64_t* ring_base = nullptr;
     for (int j = 0; j < k; j++) {
-        rc = tbx_render_step_synthetic(e, p.chunk_frames[0] + (size_t)j * fb, channels, action_seed, t0 + (uint64_t)j, env_offset, flags, s);
+        rc = tbx_render_step_synthetic(e, p.frames[0].p + (size_t)j * fb, channels, action_seed, t0 + (uint64_t)j, env_offset, flags, s);
         if (rc) return rc;
         if (e->gather_ring) {
             if (j == 0) ring_base = e->packed;                  // slot 0 of the ring this chunk fills
@@ -1713,14 +1194,14 @@ int tbx_rollout_synthetic(tbx_engine* e, int channels, uint64_t action_seed, uin
         } else if (e->gather) {
             rc = tbx_gather(e, nullptr, s);                     // one collective per step
             if (rc) return rc;
-            EHIP(hipMemcpyAsync(p.chunk_packed[0] + (size_t)j * e->n, e->packed, sizeof(uint64_t) * (size_t)e->n, hipMemcpyDeviceToDevice, s));
+            EHIP(hipMemcpyAsync(p.packed[0].p + (size_t)j * e->n, e->packed, sizeof(uint64_t) * (size_t)e->n, hipMemcpyDeviceToDevice, s));
         } else
-            EHIP(hipMemcpyAsync(p.chunk_packed[0] + (size_t)j * e->n, e->packed, sizeof(uint64_t) * (size_t)e->n, hipMemcpyDeviceToDevice, s));
+            EHIP(hipMemcpyAsync(p.packed[0].p + (size_t)j * e->n, e->packed, sizeof(uint64_t) * (size_t)e->n, hipMemcpyDeviceToDevice, s));
     }
-    p.chunk_cur = 0; p.chunk_k = k; p.chunk_channels = channels;
-    p.chunk_packed_base = e->gather_ring ? ring_base : p.chunk_packed[0];
-    p.chunk_packed_stride = e->gather_ring ? (size_t)e->gather_ring_width : (size_t)e->n;
-    e->frame = p.chunk_frames[0] + (size_t)(k - 1) * fb;        // TBX_BUF_FRAME: the chunk's last frame, as in rollout_chunked
+    p.cur = 0; p.k = k; p.channels = channels;
+    p.packed_base = e->gather_ring ? ring_base : p.packed[0].p;
+    p.packed_stride = e->gather_ring ? (size_t)e->gather_ring_width : (size_t)e->n;
+    e->frame = p.frames[0].p + (size_t)(k - 1) * fb;        // TBX_BUF_FRAME: the chunk's last frame, as in rollout_chunked
     e->frame_bytes = fb;
     return TBX_OK;
 }
@@ -1753,18 +1234,6 @@ int tbx_render_env(tbx_engine* e, int env, uint8_t* out_host, int channels)
     return TBX_OK;
 }
 
-static int ensure_staging(tbx_engine* e, size_t bytes)
-{
-    if (e->staging_bytes >= bytes) return TBX_OK;
-    EHIP(hipStreamSynchronize(e->stream));
-    if (e->staging) hipFree(e->staging);
-    e->staging = nullptr;
-    e->staging_bytes = 0;
-    EHIP(hipMalloc(&e->staging, bytes));
-    e->staging_bytes = bytes;
-    return TBX_OK;
-}
-
 int tbx_get_states(tbx_engine* e, int first_env, int count, void* pods, size_t record_size)
 {
     CHECK_ENGINE(e);
@@ -1772,11 +1241,10 @@ int tbx_get_states(tbx_engine* e, int first_env, int count, void* pods, size_t r
     if (record_size != e->ops->state_size()) return e->fail(TBX_E_INVALID, "state record size mismatch");
     EHIP(hipSetDevice(e->device));
     EHIP(tbx_use_stream(e, e->stream));
-    int rc = ensure_staging(e, record_size * (size_t)count);
+    EHIP(e->staging.reserve(record_size * (size_t)count, e->stream));
+    int rc = e->ops->pack_state(e, first_env, count, e->stream);
     if (rc) return rc;
-    rc = e->ops->pack_state(e, first_env, count, e->stream);
-    if (rc) return rc;
-    EHIP(hipMemcpyAsync(pods, e->staging, record_size * (size_t)count, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipMemcpyAsync(pods, e->staging.p, record_size * (size_t)count, hipMemcpyDeviceToHost, e->stream));
     EHIP(hipStreamSynchronize(e->stream));
     return TBX_OK;
 }
@@ -1788,9 +1256,8 @@ int tbx_set_states(tbx_engine* e, int first_env, int count, const void* pods, si
     if (record_size != e->ops->state_size()) return e->fail(TBX_E_INVALID, "state record size mismatch");
     EHIP(hipSetDevice(e->device));
     EHIP(tbx_use_stream(e, e->stream));
-    int rc = ensure_staging(e, record_size * (size_t)count);
-    if (rc) return rc;
-    rc = e->ops->unpack_state(e, first_env, count, pods, e->stream);
+    EHIP(e->staging.reserve(record_size * (size_t)count, e->stream));
+    int rc = e->ops->unpack_state(e, first_env, count, pods, e->stream);
     if (rc) return rc;
     EHIP(hipStreamSynchronize(e->stream));
     return TBX_OK;
@@ -1879,15 +1346,9 @@ static int edit_args(tbx_engine* e, const double* args, int n_args, int per_env,
     }
     if (!args_on_host) { a.per_env = args; return TBX_OK; }
     const size_t bytes = sizeof(double) * (size_t)e->n * (size_t)n_args;
-    if (e->edit_args_bytes < bytes) {
-        EHIP(hipStreamSynchronize(e->stream));
-        hipFree(e->edit_args);
-        e->edit_args = nullptr; e->edit_args_bytes = 0;
-        EHIP(hipMalloc((void**)&e->edit_args, bytes));
-        e->edit_args_bytes = bytes;
-    }
-    EHIP(hipMemcpyAsync(e->edit_args, args, bytes, hipMemcpyHostToDevice, s));
-    a.per_env = e->edit_args;
+    EHIP(e->edit_args.reserve(bytes, e->stream));
+    EHIP(hipMemcpyAsync(e->edit_args.p, args, bytes, hipMemcpyHostToDevice, s));
+    a.per_env = e->edit_args.p;
     return TBX_OK;
 }
 
@@ -1953,16 +1414,10 @@ int tbx_reduce(tbx_engine* e, int query, const double* args, int n_args, int per
     int rc = edit_args(e, args, n_args, per_env, true, e->stream, a);
     if (rc) return rc;
     const size_t bytes = sizeof(double) * (size_t)e->n * (size_t)width;
-    if (e->reduce_out_bytes < bytes) {
-        EHIP(hipStreamSynchronize(e->stream));
-        hipFree(e->reduce_out);
-        e->reduce_out = nullptr; e->reduce_out_bytes = 0;
-        EHIP(hipMalloc((void**)&e->reduce_out, bytes));
-        e->reduce_out_bytes = bytes;
-    }
-    rc = e->ops->reduce(e, query, a, e->reduce_out, width, e->stream);
+    EHIP(e->reduce_out.reserve(bytes, e->stream));
+    rc = e->ops->reduce(e, query, a, e->reduce_out.p, width, e->stream);
     if (rc) return rc;
-    EHIP(hipMemcpyAsync(out_host, e->reduce_out, bytes, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipMemcpyAsync(out_host, e->reduce_out.p, bytes, hipMemcpyDeviceToHost, e->stream));
     EHIP(hipStreamSynchronize(e->stream));
     return TBX_OK;
 }
@@ -1990,21 +1445,20 @@ int tbx_device_buffer(tbx_engine* e, int which, void** out_ptr, size_t* out_byte
     const size_t N = (size_t)e->n;
     void* p = nullptr;
     size_t b = 0;
-    if ((which >= TBX_BUF_REWARD && which <= TBX_BUF_PACKED) || which == TBX_BUF_ROLLOUT_FRAMES || which == TBX_BUF_ROLLOUT_PACKED) {
-        int rc = fused_reader_joins(e);                                // (overlapped fused launches, rollout chunks: the caller's stream joins here)
-        if (!rc) rc = rollout_reader_joins(e, which == TBX_BUF_FRAME || which == TBX_BUF_ROLLOUT_FRAMES);
+    if (e->pipe_active && ((which >= TBX_BUF_REWARD && which <= TBX_BUF_PACKED) || which == TBX_BUF_ROLLOUT_FRAMES || which == TBX_BUF_ROLLOUT_PACKED)) {
+        const int rc = pipe_reader_joins(e, which == TBX_BUF_FRAME || which == TBX_BUF_ROLLOUT_FRAMES);   // (overlapped fused launches, rollout chunks: the caller's stream joins here)
         if (rc) return rc;
     }
     switch (which) {
     case TBX_BUF_ROLLOUT_FRAMES:
-        if (!e->pipe.chunk_k) return e->fail(TBX_E_INVALID, "tbx_rollout_synthetic has not been called");
-        p = e->pipe.chunk_frames[e->pipe.chunk_cur];
-        b = (size_t)e->pipe.chunk_k * N * e->ops->height() * e->ops->width() * e->pipe.chunk_channels;
+        if (!e->rollout.k) return e->fail(TBX_E_INVALID, "tbx_rollout_synthetic has not been called");
+        p = e->rollout.frames[e->rollout.cur].p;
+        b = (size_t)e->rollout.k * N * e->ops->height() * e->ops->width() * e->rollout.channels;
         break;
     case TBX_BUF_ROLLOUT_PACKED:
-        if (!e->pipe.chunk_k) return e->fail(TBX_E_INVALID, "tbx_rollout_synthetic has not been called");
-        p = e->pipe.chunk_packed_base;
-        b = sizeof(uint64_t) * (size_t)e->pipe.chunk_k * e->pipe.chunk_packed_stride;
+        if (!e->rollout.k) return e->fail(TBX_E_INVALID, "tbx_rollout_synthetic has not been called");
+        p = e->rollout.packed_base;
+        b = sizeof(uint64_t) * (size_t)e->rollout.k * e->rollout.packed_stride;
         break;
     case TBX_BUF_REWARD: p = e->reward; b = N * 4; break;
     case TBX_BUF_DONE: p = e->done; b = N; break;
@@ -2070,7 +1524,7 @@ int tbx_sync(tbx_engine* e)
     EHIP(tbx_finish_pending(e));
     EHIP(hipDeviceSynchronize());
     e->has_last = false;              // nothing is pending any more: the stream of the last call is no longer needed
-    e->pipe.active = false;
+    e->pipe_active = false;
     return check_err_flag(e);
 }
 

@@ -9,7 +9,7 @@
 // the next step is ordered after it, but the rasteriser the caller queues in between overlaps with it (64 KiB - 512 KiB per
 // rank, latency-bound over xGMI).
 
-#include "tbx_common.hpp"
+#include "pipeline.hpp"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -317,7 +317,7 @@ int tbx_gather_init(tbx_engine* e, int nranks, int rank, int records_per_rank, c
         // the engine must be idle while the step kernels' record pointer moves into the ring
         GHIP(hipDeviceSynchronize());
         e->has_last = false;
-        e->pipe.active = false;
+        e->pipe_active = false;
         const size_t ring_bytes = sizeof(uint64_t) * (size_t)g.every * (size_t)g.width;
         for (int k = 0; k < 2; k++) {
             GHIP(hipMalloc((void**)&g.ring[k], ring_bytes));
@@ -393,24 +393,6 @@ static int host_collective(tbx_engine* e, GatherState& g, const uint64_t* send_d
     return TBX_OK;
 }
 
-// the communication stream behind the step(s) whose records the collective reads.  Overlapped fused launches (TbxPipe::fused): the
-// completion events of both lanes -- the last launch and the one before it, which may still be painting but whose step blocks
-// the last launch waited for; pipelined mode: the step stream's event; otherwise the tail of the handle.
-static hipError_t wait_for_steps(tbx_engine* e, hipStream_t gs)
-{
-    const TbxPipe& p = e->pipe;
-    if (p.active && p.fused) {
-        for (int k = 0; k < 2; k++)
-            if (p.launch_rec[k]) {
-                hipError_t r = hipStreamWaitEvent(gs, p.launch_ev[k], 0);
-                if (r != hipSuccess) return r;
-            }
-        return hipSuccess;
-    }
-    if (p.active && p.step_outstanding) return hipStreamWaitEvent(gs, p.step_ev, 0);
-    return tbx_wait_tail(e, gs, true);
-}
-
 int tbx_gather(tbx_engine* e, uint64_t* out_dev, void* stream)
 {
     if (!e) return TBX_E_INVALID;
@@ -429,7 +411,7 @@ int tbx_gather(tbx_engine* e, uint64_t* out_dev, void* stream)
         g.advance = true;
         if (++g.fill < g.every) return TBX_OK;              // nothing is queued: K - 1 of K calls cost no stream operation at all
         const int p = g.ring_par;
-        GHIP(wait_for_steps(e, gs));
+        GHIP(pipe_wait_for_steps(e, gs));
         if (g.any && g.done_on[g.last_par] != gs) GHIP(hipStreamWaitEvent(gs, g.done[g.last_par], 0));
         if (g.host) {
             int rc = host_collective(e, g, g.ring[p], out_dev ? out_dev : g.out, gs);
@@ -445,7 +427,7 @@ int tbx_gather(tbx_engine* e, uint64_t* out_dev, void* stream)
         g.ring_par = p ^ 1;
         return TBX_OK;
     }
-    GHIP(wait_for_steps(e, gs));
+    GHIP(pipe_wait_for_steps(e, gs));
     if (g.any && g.done_on[g.last_par] != gs) GHIP(hipStreamWaitEvent(gs, g.done[g.last_par], 0));
     const uint64_t* send = e->packed;
     if (g.send) {

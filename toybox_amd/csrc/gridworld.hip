@@ -673,13 +673,9 @@ struct GridWorldOps : GameOps {
     {
         dA.cfg = dB.cfg = d.cfg;
         const dim3 grid = wave_grid(a.end - a.first), block(TBX_BLOCK);
-        switch (a.obs ? a.stack : 0) {
-        case 0: hipLaunchKernelGGL(gw_agent_warp_kernel<0>, grid, block, 0, s, d, dA, dB, a, e->n); break;      // the plane ring (new_plane = 2), any depth
-        case 1: hipLaunchKernelGGL(gw_agent_warp_kernel<1>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        case 2: hipLaunchKernelGGL(gw_agent_warp_kernel<2>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        case 3: hipLaunchKernelGGL(gw_agent_warp_kernel<3>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        default: hipLaunchKernelGGL(gw_agent_warp_kernel<4>, grid, block, 0, s, d, dA, dB, a, e->n); break;
-        }
+        tbx_dispatch<0, 1, 2, 3, 4>(tbx_stack_arm(a.obs, a.stack), [&](auto depth) {
+            hipLaunchKernelGGL(gw_agent_warp_kernel<decltype(depth)::value>, grid, block, 0, s, d, dA, dB, a, e->n);
+        });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -714,19 +710,19 @@ struct GridWorldOps : GameOps {
         // 0.845-0.86 ms -- five is 8 % faster than two and its rate no longer depends on the buffer; 16 384 envs 0.189-0.201
         // against 0.195-0.208, 32 768 equal, 4 096 envs 0.047 against 0.0456: five from 16 384 envs, two below; gray and RGBA one
         const int split = split_env > 0 ? split_env : channels == 3 ? (n_envs >= 16384 ? 5 : 2) : 1;
-        switch (channels) {
-        case 1: if (pick_alt) hipLaunchKernelGGL((gw_render_kernel<1, true>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); else hipLaunchKernelGGL((gw_render_kernel<1, false>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); break;
-        case 3: if (pick_alt) hipLaunchKernelGGL((gw_render_kernel<3, true>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); else hipLaunchKernelGGL((gw_render_kernel<3, false>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); break;
-        case 4: if (pick_alt) hipLaunchKernelGGL((gw_render_kernel<4, true>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); else hipLaunchKernelGGL((gw_render_kernel<4, false>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); break;
-        default: return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
-        }
+        if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) {
+                constexpr int C = decltype(ch)::value;
+                if (pick_alt) hipLaunchKernelGGL((gw_render_kernel<C, true>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt);
+                else hipLaunchKernelGGL((gw_render_kernel<C, false>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt);
+            }))
+            return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
 
     int pack_state(tbx_engine* e, int env, int count, hipStream_t s) override
     {
-        hipLaunchKernelGGL(gw_pack_kernel, dim3(count), dim3(64), 0, s, d, env, (tbx_gridworld_state_t*)e->staging);
+        hipLaunchKernelGGL(gw_pack_kernel, dim3(count), dim3(64), 0, s, d, env, (tbx_gridworld_state_t*)e->staging.p);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -738,8 +734,8 @@ struct GridWorldOps : GameOps {
             int rc = check_dims(e, sts[i].width, sts[i].height, sts[i].n_tiles);
             if (rc) return rc;
         }
-        TBX_HIP(hipMemcpyAsync(e->staging, pod_host, sizeof(tbx_gridworld_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(gw_unpack_kernel, dim3(count), dim3(64), 0, s, d, env, (const tbx_gridworld_state_t*)e->staging);
+        TBX_HIP(hipMemcpyAsync(e->staging.p, pod_host, sizeof(tbx_gridworld_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(gw_unpack_kernel, dim3(count), dim3(64), 0, s, d, env, (const tbx_gridworld_state_t*)e->staging.p);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

@@ -10,6 +10,7 @@
 
 #include "tbx_common.hpp"
 #include "../../include/toybox_amd_spec.h"
+#include <utility>
 
 // the frame stores are plain 16-byte stores.  Non-temporal (`global_store_dwordx4 ... nt`) stores were measured twice: in
 // render-only loops within noise of plain ones (round 2), and in the [step ; render] loops of round 4 -- where a step kernel finds
@@ -190,5 +191,43 @@ struct RowStager {
 #pragma unroll 4
         for (int i = lane; i < chunks; i += 64) tbx_store16(out + i, src[i]);
         __builtin_amdgcn_wave_barrier();
+    }
+};
+
+// ------------------------------------------------------------------ host side
+
+// The rasteriser's input records of a game whose batch step writes them (Breakout, SpaceInvaders): `cur` is what a render launched
+// now reads; a step that runs ahead of the previous frame's rasteriser writes `other`, and the two swap (GameOps::step_ahead).
+template <class Rec>
+struct TbxRecordSet {
+    Rec* cur = nullptr;             // [N] rasteriser input records (the CURRENT buffer)
+    Rec* other = nullptr;
+    Rec* third = nullptr;           // only where fused launches rotate through three (alloc(n, 3), rotate3)
+    int par = 0;                    // GameOps::records_parity
+    bool valid = false;             // records reflect the current state of every env
+    TbxDevBuf<Rec> chunk[2];        // [k][N] records of a rollout chunk of parity q (tbx_rollout_synthetic), made on first use
+    hipError_t alloc(size_t n, int buffers)
+    {
+        hipError_t r = hipMalloc((void**)&cur, n * sizeof(Rec));
+        if (r == hipSuccess) r = hipMalloc((void**)&other, n * sizeof(Rec));
+        if (r == hipSuccess && buffers == 3) r = hipMalloc((void**)&third, n * sizeof(Rec));
+        return r;
+    }
+    void stepped_ahead() { std::swap(cur, other); par ^= 1; valid = true; }
+    // THREE buffers in rotation: the launch after this one reads what this one's step wrote and writes the third, so that a
+    // launch on the other lane never rewrites records this launch's rasteriser blocks may still be reading
+    void rotate3()
+    {
+        Rec* const was_read = cur;
+        cur = other;
+        other = third;
+        third = was_read;
+        par ^= 1;
+    }
+    hipError_t chunk_reserve(int q, int k, size_t n, hipStream_t s) { return chunk[q].reserve(sizeof(Rec) * (size_t)k * n, s); }
+    void release()
+    {
+        hipFree(cur); hipFree(other); hipFree(third);
+        chunk[0].release(); chunk[1].release();
     }
 };

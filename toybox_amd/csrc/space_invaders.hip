@@ -1820,19 +1820,14 @@ struct SiOps : GameOps {
     SiDev d{};
     SiCfg c{};
     tbx_si_config_t cfg{};
-    // rasteriser input records (SiRenderRec): two buffers, `recs` the current one.  Written by the batch step kernel; anything
-    // else that touches state clears recs_valid and the next render rebuilds them (si_rec_prep_kernel).  custom: an
+    // rasteriser input records (SiRenderRec): two buffers, `recs.cur` the current one.  Written by the batch step kernel; anything
+    // else that touches state clears recs.valid and the next render rebuilds them (si_rec_prep_kernel).  custom: an
     // intervention wrote enemies off the formation grid -- records cannot describe that, the state-reading rasteriser paints.
-    SiRenderRec* recs = nullptr;
-    SiRenderRec* recs_other = nullptr;
-    int recs_par = 0;
-    bool recs_valid = false;
+    TbxRecordSet<SiRenderRec> recs;
     bool custom = false;
     bool plain = true;          // every state's ids, points and laser constants are what si_load_canonical derives (is_plain)
     bool want_recs = false;     // a batch render has been asked for since creation: steps leave records from now on (a loop that
                                 // never renders keeps the 12 us the record costs the step kernel: 61 against 50 us at 65 536 envs)
-    SiRenderRec* recs_chunk[2] = {nullptr, nullptr};   // [k][N] records of a rollout chunk of parity q (tbx_rollout_synthetic), made on first use
-    int recs_chunk_k[2] = {0, 0};
 
     int height() const override { return TBX_SI_H; }
     int width() const override { return TBX_SI_W; }
@@ -1866,14 +1861,13 @@ struct SiOps : GameOps {
         TBX_HIP(hipMalloc((void**)&d.enemies, N * NEF * 64 * sizeof(int32_t)));
         TBX_HIP(hipMalloc((void**)&d.shields, N * 64 * sizeof(uint32_t)));
         TBX_HIP(hipMalloc((void**)&d.lasers, N * NLF * 16 * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&recs, N * sizeof(SiRenderRec)));
-        TBX_HIP(hipMalloc((void**)&recs_other, N * sizeof(SiRenderRec)));
+        TBX_HIP(recs.alloc(N, 2));
         return TBX_OK;
     }
 
     void destroy(tbx_engine*) override
     {
-        hipFree(recs); hipFree(recs_other); hipFree(recs_chunk[0]); hipFree(recs_chunk[1]);
+        recs.release();
         hipFree(d.sc); hipFree(d.enemies); hipFree(d.shields); hipFree(d.lasers);
         hipFree(dA.sc); hipFree(dA.enemies); hipFree(dA.shields); hipFree(dA.lasers);
         hipFree(dB.sc); hipFree(dB.enemies); hipFree(dB.shields); hipFree(dB.lasers);
@@ -1898,7 +1892,7 @@ struct SiOps : GameOps {
     {
         hipLaunchKernelGGL(si_new_game_kernel, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, mask_dev);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 
@@ -1909,43 +1903,41 @@ struct SiOps : GameOps {
         if (src.acc_reward || src.buf_valid || src.exec_flag || src.frames > 1) {    // an agent step's frames (never auto-reset)
             if (flags & TBX_STEP_AUTO_RESET) return e->fail(TBX_E_INVALID, "an agent step cannot auto-reset");
             hipLaunchKernelGGL(si_agent_step_kernel, grid_for(count), dim3(TBX_BLOCK), 0, s, d, dA, dB, c, src, flags, first, count);
-            recs_valid = false;
+            recs.valid = false;
         } else {
             // a whole-batch step leaves the rasteriser's records behind (canonical formations only)
             const bool whole = src.single_env < 0 && !custom && want_recs;
             const bool canon = !custom && plain;               // the short load (si_load_canonical)
-            SiRenderRec* const wr = whole ? recs : nullptr;
+            SiRenderRec* const wr = whole ? recs.cur : nullptr;
             if (src.single_env < 0) {
                 if (canon) TBX_LAUNCH_STEP(e, s, si_step_kernel<true>, grid_for(count), dim3(TBX_BLOCK), d, c, src, flags, first, count, wr);
                 else TBX_LAUNCH_STEP(e, s, si_step_kernel<false>, grid_for(count), dim3(TBX_BLOCK), d, c, src, flags, first, count, wr);
             } else if (canon) hipLaunchKernelGGL(si_step_kernel<true>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count, wr);
             else hipLaunchKernelGGL(si_step_kernel<false>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count, wr);
-            recs_valid = whole;
+            recs.valid = whole;
         }
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
 
     // the rasteriser reads nothing but the records, and there are two buffers of them: a batch step can run while the previous
-    // frame is still being painted (engine.hip, pipelined mode)
-    bool pipeline_ok() const override { return !custom && recs_other != nullptr; }
+    // frame is still being painted (pipeline.hip, pipelined mode)
+    bool pipeline_ok() const override { return !custom && recs.other != nullptr; }
     // scripts/pipeline_sweep.py, stream order against value 3, ms per step without a gather: 1 024 envs 0.0546 / 0.0514, 2 048
     // 0.0926 / 0.0799, 4 096 0.162 / 0.150, 8 192 0.306 / 0.296, 12 288 0.452 / 0.447
     int pipeline_auto(int n, bool gather) const override { return (!gather && n < 16384) ? 3 : 0; }
-    int records_parity() const override { return recs_par; }
-    bool records_valid() const override { return recs_valid; }
+    int records_parity() const override { return recs.par; }
+    bool records_valid() const override { return recs.valid; }
     void rebind_outputs(tbx_engine* e) override
     {
         d.reward = e->reward; d.done = e->done; d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed;
     }
     int step_ahead(tbx_engine* e, const ActionSource& src, uint32_t flags, hipStream_t s) override
     {
-        if (plain) hipLaunchKernelGGL(si_step_kernel<true>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, src, flags, 0, e->n, recs_other);
-        else hipLaunchKernelGGL(si_step_kernel<false>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, src, flags, 0, e->n, recs_other);
+        if (plain) hipLaunchKernelGGL(si_step_kernel<true>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, src, flags, 0, e->n, recs.other);
+        else hipLaunchKernelGGL(si_step_kernel<false>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, src, flags, 0, e->n, recs.other);
         TBX_HIP(hipGetLastError());
-        std::swap(recs, recs_other);
-        recs_par ^= 1;
-        recs_valid = true;
+        recs.stepped_ahead();
         return TBX_OK;
     }
 
@@ -1960,9 +1952,9 @@ struct SiOps : GameOps {
     bool serve_paints() const override { return true; }
     int serve(tbx_engine* e, TbxServeCtl* ctl_dev, hipStream_t s) override
     {
-        hipLaunchKernelGGL(si_serve_kernel, dim3(1), dim3(64 * TBX_SERVE_WAVES), 0, s, d, c, custom ? nullptr : recs, ctl_dev);
+        hipLaunchKernelGGL(si_serve_kernel, dim3(1), dim3(64 * TBX_SERVE_WAVES), 0, s, d, c, custom ? nullptr : recs.cur, ctl_dev);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 
@@ -1998,13 +1990,9 @@ struct SiOps : GameOps {
     int agent_warp(tbx_engine* e, const AgentWarpArgs& a, hipStream_t s) override
     {
         const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
-        switch (a.obs ? a.stack : 0) {
-        case 0: hipLaunchKernelGGL(si_agent_warp_kernel<0>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;      // the plane ring (new_plane = 2), any depth
-        case 1: hipLaunchKernelGGL(si_agent_warp_kernel<1>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
-        case 2: hipLaunchKernelGGL(si_agent_warp_kernel<2>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
-        case 3: hipLaunchKernelGGL(si_agent_warp_kernel<3>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
-        default: hipLaunchKernelGGL(si_agent_warp_kernel<4>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n); break;
-        }
+        tbx_dispatch<0, 1, 2, 3, 4>(tbx_stack_arm(a.obs, a.stack), [&](auto depth) {
+            hipLaunchKernelGGL(si_agent_warp_kernel<decltype(depth)::value>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n);
+        });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2014,7 +2002,7 @@ struct SiOps : GameOps {
         const dim3 grid = r.list ? dim3(std::min<unsigned>(grid_for(e->n).x, 512u)) : grid_for(e->n);
         hipLaunchKernelGGL(si_agent_reset_kernel, grid, dim3(TBX_BLOCK), 0, s, d, dA, dB, dKA, dKB, c, r);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 
@@ -2024,9 +2012,9 @@ struct SiOps : GameOps {
         return render_impl(e, src, d, source ? pick_live : nullptr, out_dev, channels, 0, e->n, s);
     }
 
-    // ---- rollout chunks (engine.hip, rollout_chunked): the step lane runs the record of the current state and then the k single-frame
+    // ---- rollout chunks (pipeline.hip, rollout_chunked): the step lane runs the record of the current state and then the k single-frame
     // step launches of the chunk back to back, step j leaving the record of frame j + 1 in the chunk's buffer; the chunk's rasteriser
-    // launches (engine.hip: per frame on the two lanes, or one over the chunk) read them.  (No multi-frame kernel: the wave-per-env step keeps its state in HBM rows anyway.)
+    // launches (pipeline.hip: per frame on the two lanes, or one over the chunk) read them.  (No multi-frame kernel: the wave-per-env step keeps its state in HBM rows anyway.)
     bool rollout_ok(int) const override { return pipeline_ok(); }
     // scripts/rollout_ab.py (RA_GAME=space_invaders), k = 4, ms per step, single calls in stream order / the pipelined two-launch loop
     // (the engine's choice, off under a record ring) / chunks; no gather | K = 4 ring (r06_rollout_ab_si.txt): 2 048 envs 0.0918 / 0.0793 /
@@ -2036,38 +2024,31 @@ struct SiOps : GameOps {
     int rollout_step(tbx_engine* e, const ActionSource& src, uint32_t flags, int k, int q, uint64_t* packed, size_t stride, hipStream_t s) override
     {
         const size_t N = (size_t)e->n;
-        if (recs_chunk_k[q] < k) {                             // (the caller has made sure nothing reads the old buffer any more)
-            TBX_HIP(hipStreamSynchronize(s));
-            hipFree(recs_chunk[q]);
-            recs_chunk[q] = nullptr;
-            recs_chunk_k[q] = 0;
-            TBX_HIP(hipMalloc((void**)&recs_chunk[q], sizeof(SiRenderRec) * (size_t)k * N));
-            recs_chunk_k[q] = k;
-        }
-        hipLaunchKernelGGL(si_rec_prep_kernel, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, recs_chunk[q], 0, e->n);
+        TBX_HIP(recs.chunk_reserve(q, k, N, s));   // (the caller has made sure nothing reads the old buffer any more)
+        hipLaunchKernelGGL(si_rec_prep_kernel, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, recs.chunk[q].p, 0, e->n);
         for (int j = 0; j < k; j++) {
             SiDev dj = d;
             dj.packed = packed + (size_t)j * stride;
             ActionSource sj = src;
             sj.t = src.t + (uint64_t)j;
-            SiRenderRec* const wr = j + 1 < k ? recs_chunk[q] + (size_t)(j + 1) * N : nullptr;
+            SiRenderRec* const wr = j + 1 < k ? recs.chunk[q].p + (size_t)(j + 1) * N : nullptr;
             if (plain) hipLaunchKernelGGL(si_step_kernel<true>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, dj, c, sj, flags, 0, e->n, wr);
             else hipLaunchKernelGGL(si_step_kernel<false>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, dj, c, sj, flags, 0, e->n, wr);
         }
         TBX_HIP(hipGetLastError());
-        recs_valid = false;                                    // the single-frame records no longer show the state
+        recs.valid = false;                                    // the single-frame records no longer show the state
         return TBX_OK;
     }
     int rollout_render(tbx_engine* e, uint8_t* out, int channels, int q, int j, hipStream_t s) override
     {
-        return launch_rec_render(e, recs_chunk[q] + (size_t)j * (size_t)e->n, out, channels, 0, e->n, s);
+        return launch_rec_render(e, recs.chunk[q].p + (size_t)j * (size_t)e->n, out, channels, 0, e->n, s);
     }
 
     bool rollout_span_ok() const override { return true; }
     bool rollout_span_auto(int /*n*/, int /*gather_kind*/) const override { return false; }
     int rollout_render_span(tbx_engine* e, uint8_t* out, int channels, int q, int j0, int count, bool /*behind_rasteriser*/, hipStream_t s) override
     {
-        return launch_rec_render(e, recs_chunk[q] + (size_t)j0 * (size_t)e->n, out, channels, 0, count * e->n, s);
+        return launch_rec_render(e, recs.chunk[q].p + (size_t)j0 * (size_t)e->n, out, channels, 0, count * e->n, s);
     }
 
     int launch_rec_render(tbx_engine* e, const SiRenderRec* rr, uint8_t* out_dev, int channels, int first_env, int n_envs, hipStream_t s)
@@ -2077,12 +2058,10 @@ struct SiOps : GameOps {
         // 2.45 / 2.50 / 2.49 / 2.49 / 2.43 / 2.49 / 3.67 ms at 65 536 envs, 0.174 / 0.171 / 0.166 / 0.164 / 0.151 / 0.167 / 0.238 ms at 4 096)
         const int split_opt = e->opt[TBX_OPT_RENDER_SPLIT];
         const int split = split_opt > 0 ? split_opt : channels == 3 ? 12 : (channels == 4 && n_envs <= 32768) ? 5 : (channels == 1 && n_envs <= 4096) ? 4 : 1;   // (gray, small batches: 0.035 against 0.067 ms at 1 024 envs, 0.094 against 0.102 at 4 096)
-        switch (channels) {
-        case 1: hipLaunchKernelGGL(si_rec_render_kernel<1>, grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, rr, out_dev, first_env, n_envs, split); break;
-        case 3: hipLaunchKernelGGL(si_rec_render_kernel<3>, grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, rr, out_dev, first_env, n_envs, split); break;
-        case 4: hipLaunchKernelGGL(si_rec_render_kernel<4>, grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, rr, out_dev, first_env, n_envs, split); break;
-        default: return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
-        }
+        if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) {
+                hipLaunchKernelGGL(si_rec_render_kernel<decltype(ch)::value>, grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, rr, out_dev, first_env, n_envs, split);
+            }))
+            return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2091,12 +2070,12 @@ struct SiOps : GameOps {
     {
         if (custom) return render_impl(e, d, d, nullptr, out_dev, channels, first_env, n_envs, s);
         if (n_envs == e->n) want_recs = true;
-        if (!recs_valid) {
-            hipLaunchKernelGGL(si_rec_prep_kernel, grid_for(n_envs), dim3(TBX_BLOCK), 0, s, d, recs, first_env, n_envs);
+        if (!recs.valid) {
+            hipLaunchKernelGGL(si_rec_prep_kernel, grid_for(n_envs), dim3(TBX_BLOCK), 0, s, d, recs.cur, first_env, n_envs);
             TBX_HIP(hipGetLastError());
-            if (first_env == 0 && n_envs == e->n) recs_valid = true;
+            if (first_env == 0 && n_envs == e->n) recs.valid = true;
         }
-        return launch_rec_render(e, recs, out_dev, channels, first_env, n_envs, s);
+        return launch_rec_render(e, recs.cur, out_dev, channels, first_env, n_envs, s);
     }
 
     int render_impl(tbx_engine* e, const SiDev& src, const SiDev& alt, const uint8_t* pick_alt, uint8_t* out_dev, int channels, int first_env,
@@ -2117,12 +2096,12 @@ struct SiOps : GameOps {
         // two-stage form (set-up once per env into a 3.5 KB record, 9-18 light waves per frame) and a set-up shared by a
         // block's waves through LDS were built and measured this round: both slower (profiles/HISTORY.md).
         const int split = split_env > 0 ? split_env : channels == 3 ? 5 : (channels == 4 && n_envs <= 32768) ? 5 : 1;
-        switch (channels) {
-        case 1: if (pick_alt) hipLaunchKernelGGL((si_render_kernel<1, true>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt); else hipLaunchKernelGGL((si_render_kernel<1, false>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt); break;
-        case 3: if (pick_alt) hipLaunchKernelGGL((si_render_kernel<3, true>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt); else hipLaunchKernelGGL((si_render_kernel<3, false>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt); break;
-        case 4: if (pick_alt) hipLaunchKernelGGL((si_render_kernel<4, true>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt); else hipLaunchKernelGGL((si_render_kernel<4, false>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt); break;
-        default: return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
-        }
+        if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) {
+                constexpr int C = decltype(ch)::value;
+                if (pick_alt) hipLaunchKernelGGL((si_render_kernel<C, true>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt);
+                else hipLaunchKernelGGL((si_render_kernel<C, false>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt);
+            }))
+            return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2158,7 +2137,7 @@ struct SiOps : GameOps {
 
     int pack_state(tbx_engine* e, int env, int count, hipStream_t s) override
     {
-        hipLaunchKernelGGL(si_pack_kernel, dim3(count), dim3(64), 0, s, d, env, (tbx_si_state_t*)e->staging);
+        hipLaunchKernelGGL(si_pack_kernel, dim3(count), dim3(64), 0, s, d, env, (tbx_si_state_t*)e->staging.p);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2183,10 +2162,10 @@ struct SiOps : GameOps {
         if (plain)
             for (int i = 0; i < count && plain; i++)
                 if (!is_plain(sts[i])) plain = false;            // from now on the step kernel loads every row
-        TBX_HIP(hipMemcpyAsync(e->staging, pod_host, sizeof(tbx_si_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(si_unpack_kernel, dim3(count), dim3(64), 0, s, d, env, (const tbx_si_state_t*)e->staging);
+        TBX_HIP(hipMemcpyAsync(e->staging.p, pod_host, sizeof(tbx_si_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(si_unpack_kernel, dim3(count), dim3(64), 0, s, d, env, (const tbx_si_state_t*)e->staging.p);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 
@@ -2203,7 +2182,7 @@ struct SiOps : GameOps {
             plan.rows(x.shields, 64 * sizeof(uint32_t));
             plan.rows(x.lasers, NLF * 16 * sizeof(int32_t));
         }
-        recs_valid = false;
+        recs.valid = false;
     }
 
     int edit(tbx_engine* e, int op, const TbxEditArgs& a, const uint8_t* mask_dev, hipStream_t s) override
@@ -2212,7 +2191,7 @@ struct SiOps : GameOps {
             return e->fail(TBX_E_INVALID, "space_invaders: unknown edit");
         hipLaunchKernelGGL(si_edit_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, d, op, a, mask_dev);
         TBX_HIP(hipGetLastError());
-        recs_valid = false;
+        recs.valid = false;
         return TBX_OK;
     }
 

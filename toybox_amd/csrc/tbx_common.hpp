@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/toybox_amd.h"
@@ -307,6 +308,15 @@ __device__ __forceinline__ void tbx_serve_loop(TbxServeCtl* ctl, int lane, StepF
 
 // ------------------------------------------------------------------ host side
 
+// a run-time value as a template argument: f(std::integral_constant<int, V>{}) for the V that equals v; false when none does
+template <int... Vs, class F>
+bool tbx_dispatch(int v, F&& f)
+{
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// the stack depth an observation kernel is built for: 0 the plane ring (new_plane = 2), any depth; 1 .. 3; anything else runs as 4
+inline int tbx_stack_arm(bool obs, int stack) { return !obs ? 0 : stack >= 0 && stack <= 3 ? stack : 4; }
+
 struct GameOps;
 
 // the outputs of a batch step (TBX_BUF_REWARD / DONE / LIVES / SCORE / PACKED); two sets exist once the pipelined mode is on
@@ -318,67 +328,47 @@ struct TbxStepOut {
     uint64_t* packed = nullptr;
 };
 
-// Pipelined mode (TBX_OPT_PIPELINE, engine.hip): random-rollout steps and batch renders of engines whose rasteriser reads
-// step-written records run on internal streams, over double-buffered records, step outputs and frames.
-struct TbxPipe {
-    hipStream_t lane[2] = {nullptr, nullptr};        // value 2: lane[0] is the step stream; value 3: step N and render N on lane[parity]
-    hipEvent_t step_ev = nullptr;                    // behind the last pipelined step ...
-    hipStream_t step_on = nullptr;                   // ... which ran on this stream ...
-    hipStream_t step_user = nullptr;                 // ... and which this caller's stream has been made to wait for (compared, never used)
-    hipEvent_t render_ev[2] = {nullptr, nullptr};    // behind the last render that READ records buffer p ...
-    hipStream_t render_on[2] = {nullptr, nullptr};   // ... which ran on this stream
-    bool render_pending[2] = {false, false};
-    // reader fences on the caller's stream: everything the caller had queued there when the step (render) call that
-    // superseded buffer p's content was made -- the next writer of buffer p waits for it
-    hipEvent_t user_step_ev[2] = {nullptr, nullptr}, user_frame_ev[2] = {nullptr, nullptr};
-    bool user_step_rec[2] = {false, false}, user_frame_rec[2] = {false, false};
-    bool active = false;          // the last call through the handle was a pipelined step or render
-    bool prepared = false;        // every resource above exists (set last by pipe_prepare)
-    bool step_outstanding = false;
-    int live_reader = -1;         // >= 0: the render behind render_ev[live_reader] read LIVE state (records were not valid): the next step waits for it
-    int frame_par = -1;           // frame buffer the last overlapped render wrote (-1: none since the pipeline was entered)
-    uint8_t* frame[2] = {nullptr, nullptr};
-    size_t frame_bytes[2] = {0, 0};
-    // Overlapped fused launches (TBX_OPT_FUSED_OVERLAP; engine.hip, fused_overlapped): consecutive tbx_render_step_synthetic
-    // launches alternate between the two lanes, the two output sets and the two frame buffers, and launch N+1 is ordered behind
-    // the STEP BLOCKS of launch N only -- a device counter they bump when their state, records and outputs are written, waited
-    // for by a one-wave kernel in front of launch N+1 (tbx_ticket_wait_kernel) -- not behind its rasteriser blocks.
-    bool fused = false;                              // the calls since the pipeline was entered are such launches (pipe_enter joins before the kind of call changes)
-    // Rollout chunks (tbx_rollout_synthetic; engine.hip, rollout_chunked): k frames per call.  ONE step launch on the step lane
-    // writes the k render records, the k step records and the state; the rasteriser launches (k, alternating between the two lanes, or
-    // one over the chunk's k x N frames on lane 0) depend on that step launch alone -- and the step launch of chunk c+1 runs beside them, a whole chunk ahead of its own
-    // rasterisers: no launch waits for a step that runs beside a rasteriser (what kept overlapped fused launches unstable).
-    bool rollout = false;                            // the calls since the pipeline was entered are rollout chunks
-    hipStream_t step_lane = nullptr;
-    hipEvent_t chunk_step_ev[2] = {nullptr, nullptr};        // behind the step launch of the last chunk of parity q
-    hipEvent_t chunk_raster_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [q][lane]: behind that chunk's last rasteriser launch on the lane
-    bool chunk_step_rec[2] = {false, false}, chunk_raster_rec[2][2] = {{false, false}, {false, false}};
-    bool chunk_user_waits[2] = {false, false};       // the caller's stream has been made to wait for chunk q (lazy join)
-    uint8_t* chunk_frames[2] = {nullptr, nullptr};   // [k][N][H][W][C] frames of the last chunk of parity q
-    size_t chunk_frame_bytes[2] = {0, 0};
-    uint64_t* chunk_packed[2] = {nullptr, nullptr};  // [k][N] step records of that chunk when no gather ring takes them
-    size_t chunk_packed_bytes[2] = {0, 0};
-    int chunk_cur = 0, chunk_k = 0, chunk_channels = 0;      // what TBX_BUF_ROLLOUT_* name: parity, frames and channels of the last chunk
-    uint64_t* chunk_packed_base = nullptr;           // ... and where its step records lie (a ring of the gather, or chunk_packed)
-    size_t chunk_packed_stride = 0;
-    hipEvent_t launch_ev[2] = {nullptr, nullptr};    // completion event of the last fused launch on lane k (it rides on the launch)
-    bool launch_rec[2] = {false, false};
-    unsigned long long* arrive = nullptr;            // device [2]: step blocks of overlapped launches that have finished, ever; launches
-                                                     // whose RELEASE block has started (the block `lead` blocks before the end of the grid)
-    unsigned long long arrive_want = 0;              // host: what the launches issued so far add up to
-    unsigned long long release_want = 0;
-    bool prev_overlapped = false;                    // the call before this one was an overlapped launch (else stream order holds)
-    // The caller's stream joins LAZILY in this mode: it is made to wait for the launch that wrote a result when the caller asks
-    // for the result's address (tbx_device_buffer -- required after every call, the addresses alternate) or makes a call of any
-    // other kind.  A loop that only rolls queues nothing on the caller's stream: with a record gather on the device, a wait and
-    // a fence per call on that stream turned a gain of 4-25 % into a loss of 10-100 % (profiles/r06_experiments.txt).
-    bool user_waits[2] = {false, false};             // the caller's stream has been made to wait for launch_ev[k]
-    bool reader_seen = false;                        // an address was handed out since the last call: the next call fences the caller's stream
+// A device buffer that only grows.  reserve(): nothing while it is large enough; else the streams that may still use the old
+// buffer run dry first (a null stream: none), it is freed and a new one made.  After a failed hipMalloc the buffer is empty, so
+// a repeated call tries again.
+template <class T>
+struct TbxDevBuf {
+    T* p = nullptr;
+    size_t bytes = 0;
+    hipError_t reserve(size_t need, hipStream_t drain_a = nullptr, hipStream_t drain_b = nullptr)
+    {
+        if (bytes >= need) return hipSuccess;
+        hipError_t r = drain_a ? hipStreamSynchronize(drain_a) : hipSuccess;
+        if (r == hipSuccess && drain_b) r = hipStreamSynchronize(drain_b);
+        if (r == hipSuccess && p) r = hipFree(p);
+        if (r != hipSuccess) return r;
+        p = nullptr;
+        bytes = 0;
+        r = hipMalloc((void**)&p, need);
+        if (r == hipSuccess) bytes = need;
+        else p = nullptr;
+        return r;
+    }
+    void release()
+    {
+        hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+// what TBX_BUF_ROLLOUT_FRAMES / TBX_BUF_ROLLOUT_PACKED name: the last chunk of tbx_rollout_synthetic, whichever form ran it
+struct TbxRolloutResult {
+    TbxDevBuf<uint8_t> frames[2];                    // [k][N][H][W][C] frames of the last chunk of parity q
+    TbxDevBuf<uint64_t> packed[2];                   // [k][N] step records of that chunk when no gather ring takes them
+    int cur = 0, k = 0, channels = 0;                // parity, frames and channels of the last chunk
+    uint64_t* packed_base = nullptr;                 // ... and where its step records lie (a ring of the gather, or `packed`)
+    size_t packed_stride = 0;
 };
 
 // what an overlapped fused launch gets from the engine: the counter its step blocks bump, the event that rides on the launch as
 // its completion event; step_blocks comes back (how many arrivals the launch adds)
-// measurement builds only (make DIAG=1; env TBX_OVERLAP_DIAG read in engine.hip; results are WRONG or racy with any bit set): parts of
+// measurement builds only (make DIAG=1; env TBX_OVERLAP_DIAG read in pipeline.hip; results are WRONG or racy with any bit set): parts of
 // the overlapped launch switched off one at a time -- 1 the first build's step half: plain loads and stores behind a per-wave L2
 // invalidate and write-back (+ 2: no write-back) instead of agent-scope loads and stores, 4 plain record load, 8 both launches on ONE lane (the machinery without any overlap), 16 no fence / wait on the caller's
 // stream, 32 one frame buffer, 64 no wait kernel, 128 no completion event on the launch
@@ -410,7 +400,9 @@ struct tbx_engine {
     bool gather_ring = false;                  // a K-step record ring is in force (TBX_OPT_GATHER_EVERY > 1 at tbx_gather_init): no pipelined mode
     int gather_ring_every = 0, gather_ring_width = 0;   // ... its K and its row width in records (tbx_rollout_synthetic)
     bool gather_wants_step_event = false;      // the next batch step is one a collective will wait for: its launch carries the ordering event
-    TbxPipe pipe;
+    struct TbxPipe* pipe = nullptr;            // pipelined mode and the overlapped loop forms (pipeline.hip), created by the first such call
+    bool pipe_active = false;                  // the last call through the handle was one of them
+    TbxRolloutResult rollout;
     // common device buffers (SoA over envs)
     uint64_t* sim_rng = nullptr;    // [2][N] simulator RNG
     int32_t* prev_score = nullptr;  // [N]
@@ -440,19 +432,14 @@ struct tbx_engine {
     int ended_early_rc = 0;
     std::string ended_early_msg;
     tbx_step_host_out_t host_out{}; // where they go
-    uint8_t* frame_own = nullptr;   // engine-owned frame buffer (lazy)
-    size_t frame_own_bytes = 0;
+    TbxDevBuf<uint8_t> frame_own;   // engine-owned frame buffer (lazy)
     uint8_t* frame = nullptr;       // what TBX_BUF_FRAME reports: frame_own, in the overlapped forms the buffer the last launch wrote,
                                     // after tbx_rollout_synthetic the last frame of the chunk's frames (include/toybox_amd.h)
     size_t frame_bytes = 0;         // ... and the size of that frame, N * H * W * channels of the call that produced it
-    double* edit_args = nullptr;    // [N][n_args] per-env arguments of tbx_edit / tbx_reduce (host-pointer forms)
-    size_t edit_args_bytes = 0;
-    double* reduce_out = nullptr;   // [N][width] result staging of tbx_reduce
-    size_t reduce_out_bytes = 0;
-    void* staging = nullptr;        // device POD staging for get/set state
-    size_t staging_bytes = 0;
-    uint8_t* fork_scratch = nullptr;   // TBX_EDIT_COPY_ENV: the gathered rows between the two passes of a fork (engine.hip, fork_envs)
-    size_t fork_scratch_bytes = 0;
+    TbxDevBuf<double> edit_args;    // [N][n_args] per-env arguments of tbx_edit / tbx_reduce (host-pointer forms)
+    TbxDevBuf<double> reduce_out;   // [N][width] result staging of tbx_reduce
+    TbxDevBuf<void> staging;        // device POD staging for get/set state
+    TbxDevBuf<uint8_t> fork_scratch;   // TBX_EDIT_COPY_ENV: the gathered rows between the two passes of a fork (engine.hip, fork_envs)
     GameOps* ops = nullptr;
     struct AgentState* agent = nullptr;   // fused agent-side preprocessing (agent.hip), lazily created
     struct GatherState* gather = nullptr; // multi-GPU record gather over RCCL (gather.hip), created by tbx_gather_init
@@ -517,6 +504,7 @@ inline hipEvent_t tbx_step_order_event(tbx_engine* e)
     } while (0)
 
 hipError_t tbx_packed_leaves_chunk(tbx_engine* e, hipStream_t s);   // engine.hip: TBX_BUF_PACKED out of a chunk's record array
+hipError_t pipe_leave(tbx_engine* e, hipStream_t s);                // pipeline.hip: the joins that leave a pipelined form
 
 // Every entry point that queues work names the stream it is about to use.  When that differs from the stream the previous
 // entry point used (the "_device" forms run on the caller's stream -- including the NULL stream, which does not order itself
@@ -535,35 +523,9 @@ inline hipError_t tbx_use_stream(tbx_engine* e, hipStream_t s)
     }
     hipError_t r = tbx_wait_tail(e, s);
     if (r != hipSuccess) return r;
-    if (e->pipe.active) {
-        // leaving the pipelined mode: a render that ran on another caller stream than the one the last pipelined call named
-        // (mode 2, or out_dev given: render on U1, then a step naming U2) is not behind last_stream -- join it here
-        TbxPipe& p = e->pipe;
-        for (int k = 0; k < 2; k++)
-            if (p.render_pending[k] && p.render_on[k] && p.render_on[k] != s) {
-                r = hipStreamWaitEvent(s, p.render_ev[k], 0);
-                if (r != hipSuccess) return r;
-            }
-        // ... and overlapped fused launches, which the caller's stream joins lazily (TbxPipe::user_waits): both lanes
-        if (p.fused)
-            for (int k = 0; k < 2; k++)
-                if (p.launch_rec[k] && p.lane[k] != s) {
-                    r = hipStreamWaitEvent(s, p.launch_ev[k], 0);
-                    if (r != hipSuccess) return r;
-                }
-        // ... and rollout chunks: the step lane and the rasterisers of both parities
-        if (p.rollout)
-            for (int q = 0; q < 2; q++) {
-                if (p.chunk_step_rec[q]) {
-                    r = hipStreamWaitEvent(s, p.chunk_step_ev[q], 0);
-                    if (r != hipSuccess) return r;
-                }
-                for (int l = 0; l < 2; l++)
-                    if (p.chunk_raster_rec[q][l]) {
-                        r = hipStreamWaitEvent(s, p.chunk_raster_ev[q][l], 0);
-                        if (r != hipSuccess) return r;
-                    }
-            }
+    if (e->pipe_active) {
+        r = pipe_leave(e, s);
+        if (r != hipSuccess) return r;
     }
     // after a rollout chunk without a record ring TBX_BUF_PACKED names the LAST ROW of the chunk's records: a step of any other
     // form would write its records there, so the row moves into the engine's own array first (behind the joins above)
@@ -572,7 +534,7 @@ inline hipError_t tbx_use_stream(tbx_engine* e, hipStream_t s)
         if (r != hipSuccess) return r;
     }
     e->step_carries_order_ev = false;          // whatever this call queues moves the tail
-    e->pipe.active = false;
+    e->pipe_active = false;
     e->last_stream = s;
     e->has_last = true;
     return hipSuccess;
@@ -669,14 +631,14 @@ struct GameOps {
     // tbx_render_step_synthetic: the rasteriser of the current frame and the batch step to the next one as ONE launch on s
     // (engines whose rasteriser reads step-written records); render_step_fused() false: the engine runs render(), then step()
     virtual bool render_step_fused(int /*channels*/) const { return false; }
-    // ov != nullptr: an overlapped launch (TbxPipe::fused) -- its step blocks bump ov->arrive when their stores are visible
+    // ov != nullptr: an overlapped launch (pipeline.hip, fused_overlapped) -- its step blocks bump ov->arrive when their stores are visible
     // device-wide, ov->done rides on the launch as its completion event, ov->step_blocks is filled in
     virtual int render_step(tbx_engine*, uint8_t* /*out_dev*/, int /*channels*/, const ActionSource&, uint32_t /*flags*/, hipStream_t,
                             TbxOverlapLaunch* /*ov*/ = nullptr) { return TBX_E_UNSUPPORTED; }
     // TBX_OPT_FUSED_OVERLAP = 0, the engine's choice: overlap consecutive fused launches for a batch of n envs?
     // (gather_kind: 0 no record gather, 1 one collective per step, 2 a K-step ring)
     virtual bool fused_overlap_auto(int /*n*/, int /*gather_kind*/) const { return false; }
-    // tbx_rollout_synthetic as chunks (TbxPipe::rollout).  rollout_ok(): this engine can right now (canonical state layout, RGB /
+    // tbx_rollout_synthetic as chunks (pipeline.hip, rollout_chunked).  rollout_ok(): this engine can right now (canonical state layout, RGB /
     // RGBA); rollout_auto(): the engine's choice for n envs; rollout_step(): frames t .. t + k - 1 of every env in ONE launch on s --
     // render record j (the state BEFORE frame j) into the chunk's record buffer of parity q, step record j into packed + j * stride,
     // the last frame's outputs into tbx_engine::reward / ...; rollout_render(): the rasteriser of record j of parity q into out.
