@@ -291,11 +291,11 @@ void orc_si_step(const tbx_si_config_t* c, tbx_si_state_t* s, uint32_t buttons)
         if (s->ufo_x >= TBX_SI_W) { s->ufo_x = TBX_SI_UFO_X0; s->ufo_appearance_counter = TBX_SI_UFO_PERIOD; }
     }
 
-    /* K. wave cleared */
+    /* K. wave cleared (SPEC.md: no enemy alive or exploding -- an empty formation, n_enemies == 0, is cleared every frame) */
     {
         int busy = 0;
         for (int i = 0; i < s->n_enemies; i++) busy |= s->enemies[i].alive || s->enemies[i].death_counter >= 0;
-        if (!busy && s->n_enemies > 0) { s->level += 1; reset_formation(s); }
+        if (!busy) { s->level += 1; reset_formation(s); }
     }
 }
 

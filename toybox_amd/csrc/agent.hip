@@ -325,6 +325,18 @@ AgentResetArgs reset_args(tbx_engine* e)
     return r;
 }
 
+// The generic path's two full-resolution gray frames.  tbx_agent_init allocates them where the engine starts on that path; an
+// engine that LEAVES its fused path later (Breakout on the first non-canonical brick written into it, which agent_fused()
+// answers anew at every step) gets them here, the first time the generic path is taken.  Every byte is painted before it is read.
+int generic_buffers(tbx_engine* e)
+{
+    AgentState& a = *e->agent;
+    const size_t bytes = (size_t)e->n * a.H * a.W;
+    if (!a.gray_a) AHIP(hipMalloc((void**)&a.gray_a, bytes));
+    if (!a.gray_b) AHIP(hipMalloc((void**)&a.gray_b, bytes));
+    return TBX_OK;
+}
+
 // the fused observation kernels can be launched for a range of envs (observe_chunk); the generic path cannot
 bool observe_in_chunks(tbx_engine* e) { return e->ops->agent_fused() && !e->agent->force_generic; }
 
@@ -341,7 +353,9 @@ int observe(tbx_engine* e, int reset_mode, hipStream_t s)
     AgentState& a = *e->agent;
     if (e->ops->agent_fused() && !a.force_generic) return e->ops->agent_warp(e, warp_args(e, reset_mode), s);
     // generic path: the two buffer slots (and the live frame where a reset returned one) as full-resolution gray frames
-    int rc = e->ops->render_from(e, 1, nullptr, a.gray_a, 1, s);
+    int rc = generic_buffers(e);
+    if (rc) return rc;
+    rc = e->ops->render_from(e, 1, nullptr, a.gray_a, 1, s);
     if (rc) return rc;
     rc = e->ops->render_from(e, 2, a.mode, a.gray_b, 1, s);
     if (rc) return rc;
@@ -444,8 +458,8 @@ void tbx_agent_copy_envs(tbx_engine* e, TbxForkPlan& plan)
     const size_t px = (size_t)a.cfg.out_h * a.cfg.out_w;
     plan.soa(a.ep_ret, 1); plan.soa(a.ep_len, 1); plan.soa(a.ep_index, 1); plan.soa(a.prev_lives, 1);
     plan.soa(a.needs_reset, 1); plan.soa(a.was_real_done, 1); plan.soa(a.buf_valid, 1); plan.soa(a.mode, 1);
-    plan.rows(a.gray_a, (size_t)a.H * a.W);
-    plan.rows(a.gray_b, (size_t)a.H * a.W);
+    plan.rows(a.gray_a, (size_t)a.H * a.W);          // (absent while the fused path has never been left, like obs / plane / ring under
+    plan.rows(a.gray_b, (size_t)a.H * a.W);          //  the other new_plane values: TbxForkPlan::rows skips a null base)
     plan.rows(a.obs, px * a.cfg.stack);
     plan.rows(a.plane, px);
     plan.rows(a.ring, px, a.cfg.stack);
@@ -506,8 +520,8 @@ int tbx_agent_init(tbx_engine* e, const tbx_agent_config_t* cfg)
     a->force_generic = e->opt[TBX_OPT_AGENT_GENERIC] != 0;
     const size_t N = (size_t)e->n;
     if (a->force_generic || !e->ops->agent_fused()) {
-        AHIP(hipMalloc((void**)&a->gray_a, N * H * W));
-        AHIP(hipMalloc((void**)&a->gray_b, N * H * W));
+        int rc = generic_buffers(e);
+        if (rc) return rc;
     }
     AHIP(hipMalloc((void**)&a->was_real_done, N));
     AHIP(hipMalloc((void**)&a->needs_reset, N));

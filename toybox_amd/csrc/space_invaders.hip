@@ -608,10 +608,10 @@ __device__ __forceinline__ void si_step(const SiCfg& c, int lane, uint32_t butto
         if (f[F_UFO_X] >= TBX_SI_W) { f[F_UFO_X] = TBX_SI_UFO_X0; f[F_UFO_APP] = TBX_SI_UFO_PERIOD; }
     }
 
-    // K. wave cleared
+    // K. wave cleared (SPEC.md: no enemy alive or exploding -- an empty formation, n_enemies == 0, is cleared every frame)
     {
         const bool busy = lane < ne && (e_alive(s) || e_dc(s) >= 0);
-        if (!__ballot(busy) && ne > 0) { f[F_LEVEL] += 1; si_reset_formation(s, lane); }
+        if (!__ballot(busy)) { f[F_LEVEL] += 1; si_reset_formation(s, lane); }
     }
 }
 
