@@ -674,7 +674,9 @@ typedef struct tbx_agent_config {
 } tbx_agent_config_t;
 
 int tbx_agent_init(tbx_engine* engine, const tbx_agent_config_t* cfg);
-/* tbx_agent_init constructs the stack (zero frame buffers, EpisodicLifeEnv.was_real_done = True, Monitor idle). */
+/* tbx_agent_init constructs the stack (zero frame buffers, EpisodicLifeEnv.was_real_done = True, Monitor idle).  A call that fails
+ * once it has begun to replace the stack leaves the engine WITHOUT an agent layer: later agent calls answer "tbx_agent_init has
+ * not been called" until one succeeds. */
 /* NoopResetEnv.override_num_noops (atari_wrappers.py:115-123) per env: counts_host[i] > 0 replaces the drawn count in env i,
  * 0 keeps the default rule; NULL removes the override. */
 int tbx_agent_set_noops(tbx_engine* engine, const int32_t* counts_host);

@@ -325,17 +325,75 @@ AgentResetArgs reset_args(tbx_engine* e)
     return r;
 }
 
+// The device arrays of AgentState, declared here ONCE: tbx_agent_init, tbx_agent_free, tbx_agent_copy_envs and generic_buffers run
+// over this table.  (Not in it: the pinned host blocks and io_dev, sized at first use; noop_override, tbx_agent_set_noops' own.)
+struct AgentArray {
+    void** p;
+    size_t row_bytes, rows;       // [fields][rows][row_bytes]; rows is N, or an absolute count (reset_count, ty, tx)
+    int fields;
+    int fill;                     // the byte tbx_agent_init fills it with, NO_FILL: every byte is written before it is read
+    bool made;                    // exists under this config
+    bool in_env;                  // part of an env: travels with TBX_EDIT_COPY_ENV
+    size_t bytes() const { return (size_t)fields * rows * row_bytes; }
+};
+constexpr int NO_FILL = -1;
+
+// generic: the engine is on (or has been on) the generic path, which needs the two full-resolution gray frames
+template <class F>
+void agent_arrays(tbx_engine* e, bool generic, F&& f)
+{
+    AgentState& a = *e->agent;
+    const size_t N = (size_t)e->n, px = (size_t)a.cfg.out_h * a.cfg.out_w, frame = (size_t)a.H * a.W;
+    const bool ring = a.cfg.new_plane == 2;
+    auto per_env = [&](auto*& p, size_t elems, int fill, bool in_env = false, bool made = true, int fields = 1) {
+        f(AgentArray{reinterpret_cast<void**>(&p), elems * sizeof(*p), N, fields, fill, made, in_env});
+    };
+    auto fixed = [&](auto*& p, size_t count, int fill) { f(AgentArray{reinterpret_cast<void**>(&p), sizeof(*p), count, 1, fill, true, false}); };
+    // the wrapper stack's per-env state (the two buffer slots themselves live with the game: GameOps::copy_envs) ...
+    per_env(a.ep_ret, 1, 0, true); per_env(a.ep_len, 1, 0, true); per_env(a.ep_index, 1, 0, true); per_env(a.prev_lives, 1, 0, true);
+    per_env(a.needs_reset, 1, 0, true);
+    per_env(a.was_real_done, 1, 1, true);                  // EpisodicLifeEnv.__init__: was_real_done = True
+    per_env(a.buf_valid, 1, 0, true);                      // MaxAndSkipEnv.__init__: _obs_buffer = np.zeros
+    per_env(a.mode, 1, 0, true);
+    per_env(a.gray_a, frame, NO_FILL, true, generic); per_env(a.gray_b, frame, NO_FILL, true, generic);
+    // ... and the observation: the env's rolled stack, its newest plane, its row in EVERY slot of the plane ring (the head is
+    // batch-wide and stays)
+    per_env(a.obs, px * a.cfg.stack, 0, true, !ring);
+    per_env(a.plane, px, 0, true, a.cfg.new_plane == 1);
+    per_env(a.ring, px, 0, true, ring, a.cfg.stack);
+    // the outputs of the last step and the per-step scratch: not part of an env
+    per_env(a.exec_flag, 1, 0); per_env(a.fin, 1, 0); per_env(a.done_out, 1, 0); per_env(a.racc, 1, 0); per_env(a.reward_out, 1, 0);
+    per_env(a.kind, 1, 0); per_env(a.ep_done, 1, 0); per_env(a.ep_len_out, 1, 0); per_env(a.ep_ret_out, 1, 0);
+    per_env(a.reset_list, 1, NO_FILL);
+    fixed(a.reset_count, 2, 0);
+    fixed(a.ty, (size_t)a.cfg.out_h, NO_FILL); fixed(a.tx, (size_t)a.cfg.out_w, NO_FILL);
+}
+
+int upload_taps(tbx_engine* e)
+{
+    AgentState& a = *e->agent;
+    const std::vector<AgentTaps> ty = make_taps(a.H, a.cfg.out_h), tx = make_taps(a.W, a.cfg.out_w);
+    AHIP(hipMemcpy(a.ty, ty.data(), ty.size() * sizeof(AgentTaps), hipMemcpyHostToDevice));
+    AHIP(hipMemcpy(a.tx, tx.data(), tx.size() * sizeof(AgentTaps), hipMemcpyHostToDevice));
+    return TBX_OK;
+}
+
+// allocate and fill what the table says exists and is not there yet
+int make_arrays(tbx_engine* e, bool generic)
+{
+    hipError_t r = hipSuccess;
+    agent_arrays(e, generic, [&](AgentArray x) {
+        if (r != hipSuccess || !x.made || *x.p) return;
+        if ((r = hipMalloc(x.p, x.bytes())) != hipSuccess) *x.p = nullptr;
+        else if (x.fill != NO_FILL) r = hipMemset(*x.p, x.fill, x.bytes());
+    });
+    return r == hipSuccess ? TBX_OK : agent_fail(e, "agent: hipMalloc / hipMemset of a device array", r);
+}
+
 // The generic path's two full-resolution gray frames.  tbx_agent_init allocates them where the engine starts on that path; an
 // engine that LEAVES its fused path later (Breakout on the first non-canonical brick written into it, which agent_fused()
 // answers anew at every step) gets them here, the first time the generic path is taken.  Every byte is painted before it is read.
-int generic_buffers(tbx_engine* e)
-{
-    AgentState& a = *e->agent;
-    const size_t bytes = (size_t)e->n * a.H * a.W;
-    if (!a.gray_a) AHIP(hipMalloc((void**)&a.gray_a, bytes));
-    if (!a.gray_b) AHIP(hipMalloc((void**)&a.gray_b, bytes));
-    return TBX_OK;
-}
+int generic_buffers(tbx_engine* e) { return e->agent->gray_b ? TBX_OK : make_arrays(e, true); }
 
 // the fused observation kernels can be launched for a range of envs (observe_chunk); the generic path cannot
 bool observe_in_chunks(tbx_engine* e) { return e->ops->agent_fused() && !e->agent->force_generic; }
@@ -434,35 +492,22 @@ void tbx_agent_free(tbx_engine* e)
         hipStreamSynchronize(e->stream);
         if (e->pending_kind == 2) e->pending_kind = 0;
     }
-    hipFree(a->plane); hipFree(a->ring); hipHostFree(a->host_actions); hipFree(a->io_dev); hipHostFree(a->io_host);
+    hipHostFree(a->host_actions); hipFree(a->io_dev); hipHostFree(a->io_host);
     if (a->copy_stream) { hipStreamSynchronize(a->copy_stream); hipStreamDestroy(a->copy_stream); }
     for (hipEvent_t ev : a->chunk_ev) if (ev) hipEventDestroy(ev);
     if (a->copies_done) hipEventDestroy(a->copies_done);
-    hipFree(a->gray_a); hipFree(a->gray_b); hipFree(a->obs); hipFree(a->fin); hipFree(a->done_out);
-    hipFree(a->racc); hipFree(a->reward_out); hipFree(a->ty); hipFree(a->tx);
-    hipFree(a->was_real_done); hipFree(a->needs_reset); hipFree(a->mode); hipFree(a->buf_valid); hipFree(a->exec_flag);
+    agent_arrays(e, true, [](AgentArray x) { hipFree(*x.p); });
     hipFree(a->noop_override);
-    hipFree(a->kind); hipFree(a->ep_done); hipFree(a->ep_ret); hipFree(a->ep_len); hipFree(a->ep_index);
-    hipFree(a->prev_lives); hipFree(a->ep_len_out); hipFree(a->ep_ret_out); hipFree(a->reset_list); hipFree(a->reset_count);
     delete a;
     e->agent = nullptr;
 }
 
-// TBX_EDIT_COPY_ENV: the wrapper stack's per-env state (the two buffer slots themselves live with the game: GameOps::copy_envs)
-// and the observation -- the env's rolled stack, its newest plane, its row in EVERY slot of the plane ring (the head is
-// batch-wide and stays).  The outputs of the last step, the no-op overrides and the per-step scratch are not part of an env.
+// TBX_EDIT_COPY_ENV: the arrays the table marks as part of an env (those that exist: TbxForkPlan::rows skips a null base).  The
+// outputs of the last step, the no-op overrides and the per-step scratch are not.
 void tbx_agent_copy_envs(tbx_engine* e, TbxForkPlan& plan)
 {
     if (!e->agent) return;
-    AgentState& a = *e->agent;
-    const size_t px = (size_t)a.cfg.out_h * a.cfg.out_w;
-    plan.soa(a.ep_ret, 1); plan.soa(a.ep_len, 1); plan.soa(a.ep_index, 1); plan.soa(a.prev_lives, 1);
-    plan.soa(a.needs_reset, 1); plan.soa(a.was_real_done, 1); plan.soa(a.buf_valid, 1); plan.soa(a.mode, 1);
-    plan.rows(a.gray_a, (size_t)a.H * a.W);          // (absent while the fused path has never been left, like obs / plane / ring under
-    plan.rows(a.gray_b, (size_t)a.H * a.W);          //  the other new_plane values: TbxForkPlan::rows skips a null base)
-    plan.rows(a.obs, px * a.cfg.stack);
-    plan.rows(a.plane, px);
-    plan.rows(a.ring, px, a.cfg.stack);
+    agent_arrays(e, true, [&](AgentArray x) { if (x.in_env) plan.rows(*x.p, x.row_bytes, x.fields); });
 }
 
 int tbx_agent_buffer(tbx_engine* e, int which, void** out_ptr, size_t* out_bytes)
@@ -518,69 +563,13 @@ int tbx_agent_init(tbx_engine* e, const tbx_agent_config_t* cfg)
     a->cfg = *cfg;
     a->H = H; a->W = W;
     a->force_generic = e->opt[TBX_OPT_AGENT_GENERIC] != 0;
-    const size_t N = (size_t)e->n;
-    if (a->force_generic || !e->ops->agent_fused()) {
-        int rc = generic_buffers(e);
-        if (rc) return rc;
-    }
-    AHIP(hipMalloc((void**)&a->was_real_done, N));
-    AHIP(hipMalloc((void**)&a->needs_reset, N));
-    AHIP(hipMalloc((void**)&a->mode, N));
-    AHIP(hipMalloc((void**)&a->buf_valid, N));
-    AHIP(hipMalloc((void**)&a->exec_flag, N));
-    AHIP(hipMemset(a->was_real_done, 1, N));         // EpisodicLifeEnv.__init__: was_real_done = True
-    AHIP(hipMemset(a->needs_reset, 0, N));
-    AHIP(hipMemset(a->mode, 0, N));
-    AHIP(hipMemset(a->buf_valid, 0, N));             // MaxAndSkipEnv.__init__: _obs_buffer = np.zeros
-    AHIP(hipMemset(a->exec_flag, 0, N));
-    {
-        int rc = e->ops->agent_prepare(e);
-        if (rc) return rc;
-    }
-    if (cfg->new_plane == 2) {
-        AHIP(hipMalloc((void**)&a->ring, N * cfg->out_h * cfg->out_w * cfg->stack));
-        AHIP(hipMemset(a->ring, 0, N * cfg->out_h * cfg->out_w * cfg->stack));
-    } else {
-        AHIP(hipMalloc((void**)&a->obs, N * cfg->out_h * cfg->out_w * cfg->stack));
-        AHIP(hipMemset(a->obs, 0, N * cfg->out_h * cfg->out_w * cfg->stack));
-    }
-    if (cfg->new_plane == 1) {
-        AHIP(hipMalloc((void**)&a->plane, N * cfg->out_h * cfg->out_w));
-        AHIP(hipMemset(a->plane, 0, N * cfg->out_h * cfg->out_w));
-    }
-    AHIP(hipMalloc((void**)&a->fin, N));
-    AHIP(hipMalloc((void**)&a->done_out, N));
-    AHIP(hipMalloc((void**)&a->racc, N * sizeof(int32_t)));
-    AHIP(hipMalloc((void**)&a->reward_out, N * sizeof(float)));
-    AHIP(hipMalloc((void**)&a->kind, N));
-    AHIP(hipMalloc((void**)&a->ep_done, N));
-    AHIP(hipMalloc((void**)&a->ep_ret, N * sizeof(int32_t)));
-    AHIP(hipMalloc((void**)&a->ep_len, N * sizeof(int32_t)));
-    AHIP(hipMalloc((void**)&a->ep_index, N * sizeof(int32_t)));
-    AHIP(hipMalloc((void**)&a->prev_lives, N * sizeof(int32_t)));
-    AHIP(hipMalloc((void**)&a->ep_len_out, N * sizeof(int32_t)));
-    AHIP(hipMalloc((void**)&a->ep_ret_out, N * sizeof(float)));
-    AHIP(hipMalloc((void**)&a->reset_list, N * sizeof(int32_t)));
-    AHIP(hipMalloc((void**)&a->reset_count, 2 * sizeof(int32_t)));
-    AHIP(hipMemset(a->reset_count, 0, 2 * sizeof(int32_t)));
-    const std::vector<AgentTaps> ty = make_taps(H, cfg->out_h), tx = make_taps(W, cfg->out_w);
-    AHIP(hipMalloc((void**)&a->ty, ty.size() * sizeof(AgentTaps)));
-    AHIP(hipMalloc((void**)&a->tx, tx.size() * sizeof(AgentTaps)));
-    AHIP(hipMemcpy(a->ty, ty.data(), ty.size() * sizeof(AgentTaps), hipMemcpyHostToDevice));
-    AHIP(hipMemcpy(a->tx, tx.data(), tx.size() * sizeof(AgentTaps), hipMemcpyHostToDevice));
-    AHIP(hipMemset(a->fin, 0, N));
-    AHIP(hipMemset(a->done_out, 0, N));
-    AHIP(hipMemset(a->racc, 0, N * sizeof(int32_t)));
-    AHIP(hipMemset(a->reward_out, 0, N * sizeof(float)));
-    AHIP(hipMemset(a->kind, 0, N));
-    AHIP(hipMemset(a->ep_done, 0, N));
-    AHIP(hipMemset(a->ep_ret, 0, N * sizeof(int32_t)));
-    AHIP(hipMemset(a->ep_len, 0, N * sizeof(int32_t)));
-    AHIP(hipMemset(a->ep_index, 0, N * sizeof(int32_t)));
-    AHIP(hipMemset(a->prev_lives, 0, N * sizeof(int32_t)));
-    AHIP(hipMemset(a->ep_len_out, 0, N * sizeof(int32_t)));
-    AHIP(hipMemset(a->ep_ret_out, 0, N * sizeof(float)));
-    return TBX_OK;
+    // from here on a failure leaves NO agent layer behind (a half-made one would meet the next agent call with null arrays);
+    // the code and the text are the failing call's
+    int rc = make_arrays(e, a->force_generic || !e->ops->agent_fused());
+    if (!rc) rc = e->ops->agent_prepare(e);
+    if (!rc) rc = upload_taps(e);
+    if (rc) tbx_agent_free(e);
+    return rc;
 }
 
 int tbx_agent_set_noops(tbx_engine* e, const int32_t* counts_host)

@@ -56,6 +56,13 @@ struct AmiTables {
     uint32_t bg, player, unpainted, painted, enemy, inner;
 };
 
+// the movers' per-frame ("hot") fields and their row in AmiDev::mh; -1 for the fields that stay in the env-major table
+constexpr int NMH = 6, MSLOTS = TBX_AMI_MAX_ENEMIES + 1;
+__host__ __device__ constexpr int ami_hot_row(int field)
+{
+    return field == M_X ? 0 : field == M_Y ? 1 : field == M_SPEED ? 2 : field == M_STEP_TX ? 3 : field == M_STEP_TY ? 4 : field == M_CAUGHT ? 5 : -1;
+}
+
 struct AmiDev {
     int n;
     uint64_t* sim_rng; int32_t* prev_score; int32_t* reward; uint8_t* done; int32_t* lives_out; int32_t* score_out;
@@ -69,14 +76,19 @@ struct AmiDev {
                          // struct-of-arrays over envs: the thread-per-env step reads them coalesced from here; every writer
                          // (ami_store, the thread form's ms) updates both copies, wave-per-env kernels read the table
     const AmiTables* tab;
+    // the per-env arrays, declared here ONCE (tbx_common.hpp, TbxLayout): allocation, release and the fork plan follow this list
+    template <class F>
+    constexpr void arrays(F&& f)
+    {
+        f(rng, tbx_soa(2, 1));
+        f(sc, tbx_soa(ANF));
+        f(tiles, tbx_rows(32 * sizeof(uint64_t)));
+        f(boxes, tbx_rows(128 * sizeof(uint32_t)));
+        f(movers, tbx_rows(NMF * 16 * sizeof(int32_t)));
+        f(mh, tbx_soa(NMH * MSLOTS));
+    }
 };
-
-// the movers' per-frame ("hot") fields and their row in AmiDev::mh; -1 for the fields that stay in the env-major table
-constexpr int NMH = 6, MSLOTS = TBX_AMI_MAX_ENEMIES + 1;
-__host__ __device__ constexpr int ami_hot_row(int field)
-{
-    return field == M_X ? 0 : field == M_Y ? 1 : field == M_SPEED ? 2 : field == M_STEP_TX ? 3 : field == M_STEP_TY ? 4 : field == M_CAUGHT ? 5 : -1;
-}
+static_assert(sizeof(AmiDev) == sizeof(void*) * (1 + 8 + tbx_array_count<AmiDev>() + 1), "AmiDev: n, the engine's eight buffers, the arrays of arrays(), tab");
 
 __constant__ int AMI_ROUTES[TBX_AMI_N_ROUTES][TBX_AMI_ROUTE_LEN] = TBX_AMI_ROUTES;
 
@@ -2031,16 +2043,8 @@ struct AmiOps : GameOps {
         memcpy(&k, cfg_pod, sizeof k);
         int rc = build_tables(e, k);
         if (rc) return rc;
-        const size_t N = (size_t)e->n;
-        d.n = e->n;
-        d.sim_rng = e->sim_rng; d.prev_score = e->prev_score; d.reward = e->reward; d.done = e->done;
-        d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed; d.err_flag = e->err_flag;
-        TBX_HIP(hipMalloc((void**)&d.rng, 2 * N * sizeof(uint64_t)));
-        TBX_HIP(hipMalloc((void**)&d.sc, (size_t)ANF * N * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&d.tiles, N * 32 * sizeof(uint64_t)));
-        TBX_HIP(hipMalloc((void**)&d.boxes, N * 128 * sizeof(uint32_t)));
-        TBX_HIP(hipMalloc((void**)&d.movers, N * NMF * 16 * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&d.mh, N * NMH * MSLOTS * sizeof(int32_t)));
+        tbx_bind_engine(d, e);
+        TBX_HIP(tbx_alloc_arrays(d, (size_t)e->n));
         TBX_HIP(hipMalloc((void**)&tab_dev, sizeof(AmiTables)));
         d.tab = tab_dev;
         return upload(e);
@@ -2048,11 +2052,8 @@ struct AmiOps : GameOps {
 
     void destroy(tbx_engine*) override
     {
-        hipFree(d.rng); hipFree(d.sc); hipFree(d.tiles); hipFree(d.boxes); hipFree(d.movers); hipFree(d.mh); hipFree(tab_dev);
-        hipFree(dA.rng); hipFree(dA.sc); hipFree(dA.tiles); hipFree(dA.boxes); hipFree(dA.movers); hipFree(dA.mh);
-        hipFree(dB.rng); hipFree(dB.sc); hipFree(dB.tiles); hipFree(dB.boxes); hipFree(dB.movers); hipFree(dB.mh);
-        hipFree(dKA.rng); hipFree(dKA.sc); hipFree(dKA.tiles); hipFree(dKA.boxes); hipFree(dKA.movers); hipFree(dKA.mh);
-        hipFree(dKB.rng); hipFree(dKB.sc); hipFree(dKB.tiles); hipFree(dKB.boxes); hipFree(dKB.movers); hipFree(dKB.mh);
+        for (AmiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_free_arrays(*x);
+        hipFree(tab_dev);
     }
 
     int get_config(tbx_engine*, void* pod) override { memcpy(pod, &cfg, sizeof cfg); return TBX_OK; }
@@ -2064,8 +2065,6 @@ struct AmiOps : GameOps {
         if (rc) return rc;
         return upload(e);
     }
-
-    static dim3 grid_for(int count) { return dim3((count + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK); }
 
     int new_game(tbx_engine* e, const uint8_t* mask_dev, hipStream_t s) override
     {
@@ -2093,16 +2092,12 @@ struct AmiOps : GameOps {
     // 0.200 / 0.212 / 0.2085 at 8 192, 0.3886 / 0.4324 / 0.4055 at 16 384 -- slower everywhere (the kill criterion was a gain of
     // 3 % at 4 096): beside a kernel that saturates the memory system with stores the step's loads and its full-state write-back
     // queue, and the rasteriser loses the slots the step's waves hold.  Removed; Amidar's step stays in stream order.
-    void rebind_outputs(tbx_engine* e) override
-    {
-        d.reward = e->reward; d.done = e->done; d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed;
-    }
+    void rebind_outputs(tbx_engine* e) override { tbx_bind_outputs(d, e); }
 
     int step(tbx_engine* e, const ActionSource& src, uint32_t flags, hipStream_t s) override
     {
         int first = 0, count = e->n;
         if (src.single_env >= 0) { first = src.single_env; count = 1; }
-        dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         // TBX_OPT_STEP_FORM: 2 = never, 1 = always, 0 = by batch size.  The thread form is one wave per 64 envs with a long
         // serial path per thread (~45 us whatever the batch), the wave form scales with the batch.  Measured in the step + render
         // loop (scripts/pipeline_sweep.py amidar, PS_STEP_FORM=1|2, one box): ms per step thread / wave form 0.246 / 0.215 at
@@ -2146,33 +2141,18 @@ struct AmiOps : GameOps {
     bool multi_frame_step() const override { return true; }
     bool agent_reset_supported() const override { return true; }
 
-    int alloc_slot(tbx_engine* e, AmiDev& x)
-    {
-        if (x.sc) { x.tab = d.tab; return TBX_OK; }
-        const size_t N = (size_t)e->n;
-        x = d;
-        x.sc = nullptr; x.tiles = nullptr; x.boxes = nullptr; x.movers = nullptr; x.rng = nullptr; x.mh = nullptr;
-        TBX_HIP(hipMalloc((void**)&x.rng, 2 * N * sizeof(uint64_t)));
-        TBX_HIP(hipMalloc((void**)&x.sc, (size_t)ANF * N * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&x.tiles, N * 32 * sizeof(uint64_t)));
-        TBX_HIP(hipMalloc((void**)&x.boxes, N * 128 * sizeof(uint32_t)));
-        TBX_HIP(hipMalloc((void**)&x.movers, N * NMF * 16 * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&x.mh, N * NMH * MSLOTS * sizeof(int32_t)));
-        return TBX_OK;
-    }
-
     int agent_prepare(tbx_engine* e) override
     {
-        int rc = alloc_slot(e, dA);
-        if (!rc) rc = alloc_slot(e, dB);
-        if (!rc) rc = alloc_slot(e, dKA);
-        if (!rc) rc = alloc_slot(e, dKB);
-        return rc;
+        for (AmiDev* x : {&dA, &dB, &dKA, &dKB}) {
+            if (x->sc) continue;                       // made by an earlier tbx_agent_init (whole: tbx_alloc_arrays)
+            *x = d;                                    // n, the engine's buffers, the tables
+            TBX_HIP(tbx_alloc_arrays(*x, (size_t)e->n));
+        }
+        return TBX_OK;
     }
 
     int agent_warp(tbx_engine* e, const AgentWarpArgs& a, hipStream_t s) override
     {
-        dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
         tbx_dispatch<0, 1, 2, 3, 4>(tbx_stack_arm(a.obs, a.stack), [&](auto depth) {
             hipLaunchKernelGGL(ami_agent_warp_kernel<decltype(depth)::value>, grid, block, 0, s, d, dA, dB, dKA, dKB, a, e->n);
@@ -2183,7 +2163,6 @@ struct AmiOps : GameOps {
 
     int agent_reset_envs(tbx_engine* e, const AgentResetArgs& r, hipStream_t s) override
     {
-        dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         const dim3 grid = r.list ? dim3(std::min<unsigned>(grid_for(e->n).x, 512u)) : grid_for(e->n);
         hipLaunchKernelGGL(ami_agent_reset_kernel, grid, dim3(TBX_BLOCK), 0, s, d, dA, dB, dKA, dKB, r);
         TBX_HIP(hipGetLastError());
@@ -2192,7 +2171,6 @@ struct AmiOps : GameOps {
 
     int render_from(tbx_engine* e, int source, const uint8_t* pick_live, uint8_t* out_dev, int channels, hipStream_t s) override
     {
-        dA.tab = dB.tab = dKA.tab = dKB.tab = d.tab;
         const AmiDev& src = source == 1 ? dA : source == 2 ? dB : d;
         return render_impl(e, src, d, source ? pick_live : nullptr, out_dev, channels, 0, e->n, s);
     }
@@ -2211,12 +2189,15 @@ struct AmiOps : GameOps {
         // (gray: one wave per frame under-fills the chip at small batches -- four per frame up to 4 096 envs: 0.026 against 0.047 ms
         // at 1 024, 0.064 against 0.066 at 4 096; at 16 384 it is the slower form, 0.196 against 0.187, and so it is for RGBA at 4 096)
         const int split = split_env > 0 ? split_env : channels == 3 ? 9 : (channels == 1 && n_envs <= 4096) ? 4 : 1;
-        switch (channels) {
-        case 1: if (pick_alt) hipLaunchKernelGGL((ami_render_kernel<1, true>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); else hipLaunchKernelGGL((ami_render_kernel<1, false>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); break;
-        case 3: if (pick_alt) hipLaunchKernelGGL((ami_render_kernel_w6<3, true>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); else hipLaunchKernelGGL((ami_render_kernel_w6<3, false>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); break;
-        case 4: if (pick_alt) hipLaunchKernelGGL((ami_render_kernel<4, true>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); else hipLaunchKernelGGL((ami_render_kernel<4, false>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt); break;
-        default: return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
-        }
+        if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) {
+                tbx_dispatch<0, 1>(pick_alt != nullptr, [&](auto with_alt) {
+                    constexpr int C = decltype(ch)::value;
+                    constexpr bool ALT = decltype(with_alt)::value != 0;
+                    if constexpr (C == 3) hipLaunchKernelGGL((ami_render_kernel_w6<C, ALT>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt);
+                    else hipLaunchKernelGGL((ami_render_kernel<C, ALT>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt);
+                });
+            }))
+            return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2246,16 +2227,7 @@ struct AmiOps : GameOps {
     // mirror, of the live state and of the agent layer's two slots
     void copy_envs(tbx_engine*, TbxForkPlan& plan) override
     {
-        const AmiDev* const all[5] = {&d, &dA, &dB, &dKA, &dKB};   // (the kept copies too: mode 2 travels with the env)
-        for (int k = 0; k < 5; k++) {
-            const AmiDev& x = *all[k];
-            plan.soa(x.rng, 2, k == 0 ? 1 : 0);
-            plan.soa(x.sc, ANF);
-            plan.rows(x.tiles, 32 * sizeof(uint64_t));
-            plan.rows(x.boxes, 128 * sizeof(uint32_t));
-            plan.rows(x.movers, NMF * 16 * sizeof(int32_t));
-            plan.soa(x.mh, NMH * MSLOTS);
-        }
+        for (AmiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_fork_arrays(plan, *x, x == &d);   // (the kept copies too: mode 2 travels with the env)
     }
 
     int edit(tbx_engine* e, int op, const TbxEditArgs& a, const uint8_t* mask_dev, hipStream_t s) override

@@ -63,7 +63,21 @@ struct BrkDev {
     int32_t* n_bricks;
     uint64_t* alive;        // [4][N]
     BrkCustom* custom;      // [N] or nullptr
+    // the per-env arrays, declared here ONCE (tbx_common.hpp, TbxLayout): allocation, release and the fork plan follow this list
+    template <class F>
+    constexpr void arrays(F&& f)
+    {
+        f(rng, tbx_soa(2, 1));
+        f(score, tbx_soa(1)); f(lives, tbx_soa(1)); f(level, tbx_soa(1)); f(flags, tbx_soa(1));
+        f(paddle, tbx_soa(7));
+        f(n_balls, tbx_soa(1));
+        f(balls, tbx_soa(16));
+        f(n_bricks, tbx_soa(1));
+        f(alive, tbx_soa(4));
+        f(custom, tbx_lazy(tbx_rows(sizeof(BrkCustom))));
+    }
 };
+static_assert(sizeof(BrkDev) == sizeof(void*) * (1 + 8 + tbx_array_count<BrkDev>()), "BrkDev: n, the engine's eight buffers, the arrays of arrays()");
 
 // config as the kernels see it (kernel argument, scalar loads)
 struct BrkCfg {
@@ -1851,6 +1865,19 @@ __global__ void brk_scalars_kernel(BrkDev d, int32_t* score, int32_t* lives, int
 
 // ------------------------------------------------------------------ host ops
 
+// agent layer: MaxAndSkipEnv's two-frame buffer is two 64-byte render records per env
+struct BrkSlots {
+    BrkRenderRec *recsA, *recsB;
+    BrkRenderRec *keepA, *keepB;   // copies of slots A / B for the observation of one agent step (AgentResetProc::run, mode 2)
+    template <class F>
+    constexpr void arrays(F&& f)
+    {
+        f(recsA, tbx_rows(sizeof(BrkRenderRec))); f(recsB, tbx_rows(sizeof(BrkRenderRec)));
+        f(keepA, tbx_rows(sizeof(BrkRenderRec))); f(keepB, tbx_rows(sizeof(BrkRenderRec)));
+    }
+};
+static_assert(sizeof(BrkSlots) == sizeof(void*) * tbx_array_count<BrkSlots>(), "BrkSlots: the arrays of arrays()");
+
 struct BreakoutOps : GameOps {
     BrkDev d{};
     BrkCfg c{};
@@ -1890,9 +1917,6 @@ struct BreakoutOps : GameOps {
         return TBX_OK;
     }
 
-    template <typename T>
-    static hipError_t dalloc(T** p, size_t count) { return hipMalloc((void**)p, count * sizeof(T)); }
-
     int init(tbx_engine* e, const void* cfg_pod, size_t cfg_size) override
     {
         tbx_breakout_config_t k;
@@ -1904,36 +1928,18 @@ struct BreakoutOps : GameOps {
         }
         int rc = load_cfg(e, k);
         if (rc) return rc;
-        const size_t N = (size_t)e->n;
         options_changed(e);
-        d.n = e->n;
-        d.sim_rng = e->sim_rng; d.prev_score = e->prev_score; d.reward = e->reward; d.done = e->done;
-        d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed; d.err_flag = e->err_flag;
-        TBX_HIP(dalloc(&d.rng, 2 * N));
-        TBX_HIP(dalloc(&d.score, N));
-        TBX_HIP(dalloc(&d.lives, N));
-        TBX_HIP(dalloc(&d.level, N));
-        TBX_HIP(dalloc(&d.flags, N));
-        TBX_HIP(dalloc(&d.paddle, 7 * N));
-        TBX_HIP(dalloc(&d.n_balls, N));
-        TBX_HIP(dalloc(&d.balls, 16 * N));
-        TBX_HIP(dalloc(&d.n_bricks, N));
-        TBX_HIP(dalloc(&d.alive, 4 * N));
-        TBX_HIP(recs.alloc(N, 3));
-        d.custom = nullptr;
+        tbx_bind_engine(d, e);
+        TBX_HIP(tbx_alloc_arrays(d, (size_t)e->n));
+        TBX_HIP(recs.alloc((size_t)e->n, 3));
         return TBX_OK;
     }
 
     void destroy(tbx_engine*) override
     {
-        hipFree(d.rng); hipFree(d.score); hipFree(d.lives); hipFree(d.level); hipFree(d.flags);
-        hipFree(d.paddle); hipFree(d.n_balls); hipFree(d.balls); hipFree(d.n_bricks); hipFree(d.alive);
-        if (d.custom) hipFree(d.custom);
+        tbx_free_arrays(d);
+        tbx_free_arrays(slots);
         recs.release();
-        hipFree(recsA);
-        hipFree(keepA);
-        hipFree(keepB);
-        hipFree(recsB);
         hipFree(cfg_dev);
     }
 
@@ -1945,12 +1951,9 @@ struct BreakoutOps : GameOps {
         return load_cfg(e, k);
     }
 
-    static dim3 grid_for(int count) { return dim3((count + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK); }
-
     int new_game(tbx_engine* e, const uint8_t* mask_dev, hipStream_t s) override
     {
-        if (custom) hipLaunchKernelGGL(brk_new_game_kernel<true>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, mask_dev);
-        else hipLaunchKernelGGL(brk_new_game_kernel<false>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, mask_dev);
+        tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_new_game_kernel<decltype(cu)::value != 0>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, mask_dev); });
         TBX_HIP(hipGetLastError());
         recs.valid = false;
         return TBX_OK;
@@ -1961,17 +1964,16 @@ struct BreakoutOps : GameOps {
         if (!custom && src.single_env < 0 && use_tpe) {
             if (src.acc_reward || src.buf_valid || src.exec_flag || src.frames > 1) {    // an agent step's frames (never auto-reset)
                 if (flags & TBX_STEP_AUTO_RESET) return e->fail(TBX_E_INVALID, "an agent step cannot auto-reset");
-                hipLaunchKernelGGL(brk_step_tpe_kernel<true>, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, recs.cur, recsA, recsB);
+                hipLaunchKernelGGL(brk_step_tpe_kernel<true>, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, recs.cur, slots.recsA, slots.recsB);
             } else
-                TBX_LAUNCH_STEP(e, s, (brk_step_tpe_kernel<false>), dim3((e->n + 127) / 128), dim3(128), d, cfg_dev, src, flags, recs.cur, recsA, recsB);
+                TBX_LAUNCH_STEP(e, s, (brk_step_tpe_kernel<false>), dim3((e->n + 127) / 128), dim3(128), d, cfg_dev, src, flags, recs.cur, slots.recsA, slots.recsB);
             TBX_HIP(hipGetLastError());
             recs.valid = true;
             return TBX_OK;
         }
         int first = 0, count = e->n;
         if (src.single_env >= 0) { first = src.single_env; count = 1; }
-        if (custom) hipLaunchKernelGGL(brk_step_kernel<true>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count);
-        else hipLaunchKernelGGL(brk_step_kernel<false>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count);
+        tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_step_kernel<decltype(cu)::value != 0>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count); });
         TBX_HIP(hipGetLastError());
         recs.valid = false;
         return TBX_OK;
@@ -1983,10 +1985,7 @@ struct BreakoutOps : GameOps {
     // scripts/pipeline_sweep.py, stream order against value 3, ms per step without a gather: 1 024 envs 0.0315 / 0.038, 2 048
     // 0.0491 / 0.0507, 4 096 0.0985 / 0.0868, 8 192 0.168 / 0.164, 12 288 0.243 / 0.240; with one at 8 192: 0.175 / 0.230
     int pipeline_auto(int n, bool gather) const override { return (!gather && n >= 4096 && n < 16384) ? 3 : 0; }
-    void rebind_outputs(tbx_engine* e) override
-    {
-        d.reward = e->reward; d.done = e->done; d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed;
-    }
+    void rebind_outputs(tbx_engine* e) override { tbx_bind_outputs(d, e); }
     void options_changed(tbx_engine* e) override
     {
         use_tpe = e->opt[TBX_OPT_STEP_FORM] != 2;     // thread per env unless the wave-per-env kernel is asked for
@@ -1996,7 +1995,7 @@ struct BreakoutOps : GameOps {
     bool records_valid() const override { return recs.valid; }
     int step_ahead(tbx_engine* e, const ActionSource& src, uint32_t flags, hipStream_t s) override
     {
-        hipLaunchKernelGGL(brk_step_tpe_kernel<false>, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, recs.other, recsA, recsB);
+        hipLaunchKernelGGL(brk_step_tpe_kernel<false>, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, src, flags, recs.other, slots.recsA, slots.recsB);
         TBX_HIP(hipGetLastError());
         recs.stepped_ahead();
         return TBX_OK;
@@ -2165,14 +2164,13 @@ struct BreakoutOps : GameOps {
         auto launch_part = [&](int f0, int n) {                           // envs first + f0 .. first + f0 + n - 1 into their frames
             uint8_t* o = out + (size_t)f0 * TBX_BRK_H * TBX_BRK_W * C;
             const dim3 grid = grid_for(n * split), block(TBX_BLOCK);
-#define BRK_LAUNCH(KERNEL, CUSTOM_, ALT_) hipLaunchKernelGGL((KERNEL<C, CUSTOM_, ALT_>), grid, block, 0, s, rr, d.custom, pal, o, first + f0, n, split_arg, alt, pick_alt)
-            if (C >= 3) {          // (pick_alt: the agent layer's generic path, per-env choice between two record arrays)
-                if (pick_alt) { if (custom) BRK_LAUNCH(brk_render_kernel_w5, true, true); else BRK_LAUNCH(brk_render_kernel_w5, false, true); }
-                else { if (custom) BRK_LAUNCH(brk_render_kernel_w5, true, false); else BRK_LAUNCH(brk_render_kernel_w5, false, false); }
-            } else {
-                if (pick_alt) { if (custom) BRK_LAUNCH(brk_render_kernel, true, true); else BRK_LAUNCH(brk_render_kernel, false, true); }
-                else { if (custom) BRK_LAUNCH(brk_render_kernel, true, false); else BRK_LAUNCH(brk_render_kernel, false, false); }
-            }
+#define BRK_LAUNCH(KERNEL) hipLaunchKernelGGL((KERNEL<C, decltype(cu)::value != 0, decltype(al)::value != 0>), grid, block, 0, s, rr, d.custom, pal, o, first + f0, n, split_arg, alt, pick_alt)
+            tbx_dispatch<0, 1>(custom, [&](auto cu) {
+                tbx_dispatch<0, 1>(pick_alt != nullptr, [&](auto al) {   // (pick_alt: the agent layer's generic path, per-env choice between two record arrays)
+                    if (C >= 3) BRK_LAUNCH(brk_render_kernel_w5);
+                    else BRK_LAUNCH(brk_render_kernel);
+                });
+            });
 #undef BRK_LAUNCH
         };
         constexpr int HEAD_ENVS = 1024;
@@ -2188,11 +2186,8 @@ struct BreakoutOps : GameOps {
         return TBX_OK;
     }
 
-    // ---- agent layer: MaxAndSkipEnv's two-frame buffer is two 64-byte render records per env
-    BrkRenderRec* recsA = nullptr;
-    BrkRenderRec* recsB = nullptr;
-    BrkRenderRec* keepA = nullptr;   // copies of slots A / B for the observation of one agent step (AgentResetProc::run, mode 2)
-    BrkRenderRec* keepB = nullptr;
+    // ---- agent layer
+    BrkSlots slots{};
 
     bool agent_fused() const override { return !custom; }
     bool multi_frame_step() const override { return !custom && use_tpe; }
@@ -2200,20 +2195,14 @@ struct BreakoutOps : GameOps {
 
     int agent_prepare(tbx_engine* e) override
     {
-        if (!recsA) TBX_HIP(hipMalloc((void**)&recsA, sizeof(BrkRenderRec) * (size_t)e->n));
-        if (!recsB) TBX_HIP(hipMalloc((void**)&recsB, sizeof(BrkRenderRec) * (size_t)e->n));
-        if (!keepA) TBX_HIP(hipMalloc((void**)&keepA, sizeof(BrkRenderRec) * (size_t)e->n));
-        if (!keepB) TBX_HIP(hipMalloc((void**)&keepB, sizeof(BrkRenderRec) * (size_t)e->n));
-        TBX_HIP(hipMemset(keepA, 0, sizeof(BrkRenderRec) * (size_t)e->n));
-        TBX_HIP(hipMemset(keepB, 0, sizeof(BrkRenderRec) * (size_t)e->n));
-        TBX_HIP(hipMemset(recsA, 0, sizeof(BrkRenderRec) * (size_t)e->n));
-        TBX_HIP(hipMemset(recsB, 0, sizeof(BrkRenderRec) * (size_t)e->n));
+        if (!slots.recsA) TBX_HIP(tbx_alloc_arrays(slots, (size_t)e->n));
+        TBX_HIP(tbx_zero_arrays(slots, (size_t)e->n));          // on every tbx_agent_init: np.zeros of MaxAndSkipEnv's buffer
         return TBX_OK;
     }
 
     int agent_snapshot(tbx_engine* e, int slot, const uint8_t* exec_flag, uint8_t* buf_valid, hipStream_t s) override
     {
-        hipLaunchKernelGGL(brk_render_prep_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, d, slot ? recsB : recsA, 0, e->n, exec_flag,
+        hipLaunchKernelGGL(brk_render_prep_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, d, slot ? slots.recsB : slots.recsA, 0, e->n, exec_flag,
                            buf_valid, slot ? 2 : 1);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
@@ -2221,7 +2210,7 @@ struct BreakoutOps : GameOps {
 
     int render_from(tbx_engine* e, int source, const uint8_t* pick_live, uint8_t* out_dev, int channels, hipStream_t s) override
     {
-        const BrkRenderRec* src_recs = source == 1 ? recsA : source == 2 ? recsB : nullptr;
+        const BrkRenderRec* src_recs = source == 1 ? slots.recsA : source == 2 ? slots.recsB : nullptr;
         const BrkRenderRec* alt = (src_recs && pick_live) ? recs.cur : nullptr;
         if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) { launch_render<decltype(ch)::value>(out_dev, 0, e->n, s, src_recs, alt, alt ? pick_live : nullptr); }))
             return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
@@ -2232,7 +2221,7 @@ struct BreakoutOps : GameOps {
     int agent_reset_envs(tbx_engine* e, const AgentResetArgs& r, hipStream_t s) override
     {
         if (custom) return e->fail(TBX_E_UNSUPPORTED, "breakout: episodic-life / fire-reset / no-op-reset need the canonical brick wall");
-        hipLaunchKernelGGL(brk_agent_reset_kernel, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, r, recs.cur, recsA, recsB, keepA, keepB);
+        hipLaunchKernelGGL(brk_agent_reset_kernel, dim3((e->n + 127) / 128), dim3(128), 0, s, d, cfg_dev, r, recs.cur, slots.recsA, slots.recsB, slots.keepA, slots.keepB);
         TBX_HIP(hipGetLastError());
         // every other env's live record is still current if it was; the flagged envs' records were just rewritten
         return TBX_OK;
@@ -2263,7 +2252,7 @@ struct BreakoutOps : GameOps {
         }
         const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
         tbx_dispatch<0, 1, 2, 3, 4>(tbx_stack_arm(a.obs, a.stack), [&](auto depth) {
-            hipLaunchKernelGGL(brk_agent_warp_kernel<decltype(depth)::value>, grid, block, 0, s, recs.cur, recsA, recsB, keepA, keepB, pal, a, e->n);
+            hipLaunchKernelGGL(brk_agent_warp_kernel<decltype(depth)::value>, grid, block, 0, s, recs.cur, slots.recsA, slots.recsB, slots.keepA, slots.keepB, pal, a, e->n);
         });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
@@ -2272,8 +2261,7 @@ struct BreakoutOps : GameOps {
     int pack_state(tbx_engine* e, int env, int count, hipStream_t s) override
     {
         auto* out = (tbx_breakout_state_t*)e->staging.p;
-        if (custom) hipLaunchKernelGGL(brk_pack_kernel<true>, dim3(count), dim3(64), 0, s, d, c, env, out);
-        else hipLaunchKernelGGL(brk_pack_kernel<false>, dim3(count), dim3(64), 0, s, d, c, env, out);
+        tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_pack_kernel<decltype(cu)::value != 0>, dim3(count), dim3(64), 0, s, d, c, env, out); });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -2296,7 +2284,7 @@ struct BreakoutOps : GameOps {
     int enable_custom(tbx_engine* e, hipStream_t s)
     {
         if (custom) return TBX_OK;
-        TBX_HIP(hipMalloc((void**)&d.custom, sizeof(BrkCustom) * (size_t)e->n));
+        TBX_HIP(tbx_alloc_arrays(d, (size_t)e->n, true));      // d.custom
         hipLaunchKernelGGL(brk_fill_custom_kernel, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c);
         TBX_HIP(hipGetLastError());
         custom = true;
@@ -2321,8 +2309,7 @@ struct BreakoutOps : GameOps {
         }
         TBX_HIP(hipMemcpyAsync(e->staging.p, pod_host, sizeof(tbx_breakout_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
         auto* in = (const tbx_breakout_state_t*)e->staging.p;
-        if (custom) hipLaunchKernelGGL(brk_unpack_kernel<true>, dim3(count), dim3(64), 0, s, d, env, in);
-        else hipLaunchKernelGGL(brk_unpack_kernel<false>, dim3(count), dim3(64), 0, s, d, env, in);
+        tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_unpack_kernel<decltype(cu)::value != 0>, dim3(count), dim3(64), 0, s, d, env, in); });
         TBX_HIP(hipGetLastError());
         recs.valid = false;
         return TBX_OK;
@@ -2336,8 +2323,7 @@ struct BreakoutOps : GameOps {
         default: return e->fail(TBX_E_INVALID, "breakout: unknown edit");
         }
         const dim3 grid((e->n + 255) / 256), block(256);
-        if (custom) hipLaunchKernelGGL(brk_edit_kernel<true>, grid, block, 0, s, d, c.n_rows, op, a, mask_dev);
-        else hipLaunchKernelGGL(brk_edit_kernel<false>, grid, block, 0, s, d, c.n_rows, op, a, mask_dev);
+        tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_edit_kernel<decltype(cu)::value != 0>, grid, block, 0, s, d, c.n_rows, op, a, mask_dev); });
         TBX_HIP(hipGetLastError());
         recs.valid = false;
         return TBX_OK;
@@ -2347,26 +2333,15 @@ struct BreakoutOps : GameOps {
     // agent layer (a copy of a canonical env is canonical: `custom` stays as it is)
     void copy_envs(tbx_engine*, TbxForkPlan& plan) override
     {
-        plan.soa(d.rng, 2, 1);
-        plan.soa(d.score, 1); plan.soa(d.lives, 1); plan.soa(d.level, 1); plan.soa(d.flags, 1);
-        plan.soa(d.paddle, 7);
-        plan.soa(d.n_balls, 1);
-        plan.soa(d.balls, 16);
-        plan.soa(d.n_bricks, 1);
-        plan.soa(d.alive, 4);
-        plan.rows(d.custom, sizeof(BrkCustom));
-        plan.rows(recsA, sizeof(BrkRenderRec));
-        plan.rows(recsB, sizeof(BrkRenderRec));
-        plan.rows(keepA, sizeof(BrkRenderRec));        // (an env copied while its observation is the kept buffer's: mode 2 travels too)
-        plan.rows(keepB, sizeof(BrkRenderRec));
+        tbx_fork_arrays(plan, d, true);
+        tbx_fork_arrays(plan, slots, false);           // (the kept copies too: an env copied while its observation is the kept buffer's)
         recs.valid = false;
     }
 
     int reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s) override
     {
         const dim3 grid((e->n + 255) / 256), block(256);
-        if (custom) hipLaunchKernelGGL(brk_reduce_kernel<true>, grid, block, 0, s, d, c.n_rows, query, a, out_dev, width);
-        else hipLaunchKernelGGL(brk_reduce_kernel<false>, grid, block, 0, s, d, c.n_rows, query, a, out_dev, width);
+        tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_reduce_kernel<decltype(cu)::value != 0>, grid, block, 0, s, d, c.n_rows, query, a, out_dev, width); });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

@@ -31,7 +31,16 @@ struct GwDev {
     uint8_t* done;
     uint64_t* packed;
     uint32_t* err_flag;
+    // the per-env arrays, declared here ONCE (tbx_common.hpp, TbxLayout): allocation, release and the fork plan follow this list
+    template <class F>
+    constexpr void arrays(F&& f)
+    {
+        f(sc, tbx_soa(GF));
+        f(tiles, tbx_rows(GT * 3 * sizeof(uint32_t)));
+        f(grid, tbx_rows(CELLS));
+    }
 };
+static_assert(sizeof(GwDev) == sizeof(void*) * (1 + tbx_array_count<GwDev>() + 1 + 8), "GwDev: n, the arrays of arrays(), cfg, the engine's eight buffers");
 
 struct GwT { int32_t score, over, px, py, becomes, w, h, nt; };
 
@@ -574,32 +583,23 @@ struct GridWorldOps : GameOps {
     int init(tbx_engine* e, const void* cfg_pod, size_t cfg_size) override
     {
         if (!cfg_pod || cfg_size != sizeof(tbx_gridworld_config_t)) return e->fail(TBX_E_INVALID, "gridworld: config size mismatch");
-        const size_t N = (size_t)e->n;
         TBX_HIP(hipMalloc((void**)&cfg_dev, sizeof(tbx_gridworld_config_t)));
         tbx_gridworld_config_t k;
         memcpy(&k, cfg_pod, sizeof k);
         int rc = load_cfg(e, k);
         if (rc) return rc;
-        d.n = e->n;
         d.cfg = cfg_dev;
-        d.sim_rng = e->sim_rng; d.prev_score = e->prev_score; d.reward = e->reward; d.done = e->done;
-        d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed; d.err_flag = e->err_flag;
-        TBX_HIP(hipMalloc((void**)&d.sc, (size_t)GF * N * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&d.tiles, N * GT * 3 * sizeof(uint32_t)));
-        TBX_HIP(hipMalloc((void**)&d.grid, N * CELLS));
+        tbx_bind_engine(d, e);
+        TBX_HIP(tbx_alloc_arrays(d, (size_t)e->n));
         return TBX_OK;
     }
 
-    void rebind_outputs(tbx_engine* e) override
-    {
-        d.reward = e->reward; d.done = e->done; d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed;
-    }
+    void rebind_outputs(tbx_engine* e) override { tbx_bind_outputs(d, e); }
 
     void destroy(tbx_engine*) override
     {
-        hipFree(d.sc); hipFree(d.tiles); hipFree(d.grid); hipFree(cfg_dev);
-        hipFree(dA.sc); hipFree(dA.tiles); hipFree(dA.grid);
-        hipFree(dB.sc); hipFree(dB.tiles); hipFree(dB.grid);
+        for (GwDev* x : {&d, &dA, &dB}) tbx_free_arrays(*x);
+        hipFree(cfg_dev);
     }
 
     int get_config(tbx_engine*, void* pod) override { memcpy(pod, &cfg, sizeof cfg); return TBX_OK; }
@@ -611,11 +611,9 @@ struct GridWorldOps : GameOps {
         return load_cfg(e, k);
     }
 
-    static dim3 wave_grid(int count) { return dim3((count + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK); }
-
     int new_game(tbx_engine* e, const uint8_t* mask_dev, hipStream_t s) override
     {
-        hipLaunchKernelGGL(gw_new_game_kernel, wave_grid(e->n), dim3(TBX_BLOCK), 0, s, d, mask_dev);
+        hipLaunchKernelGGL(gw_new_game_kernel, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, mask_dev);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
@@ -642,37 +640,26 @@ struct GridWorldOps : GameOps {
     bool agent_fused() const override { return true; }
     bool agent_reset_supported() const override { return true; }
 
-    int alloc_slot(tbx_engine* e, GwDev& x)
-    {
-        if (x.sc) { x.cfg = d.cfg; return TBX_OK; }
-        const size_t N = (size_t)e->n;
-        x = d;
-        x.sc = nullptr; x.tiles = nullptr; x.grid = nullptr;
-        TBX_HIP(hipMalloc((void**)&x.sc, (size_t)GF * N * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&x.tiles, N * GT * 3 * sizeof(uint32_t)));
-        TBX_HIP(hipMalloc((void**)&x.grid, N * CELLS));
-        return TBX_OK;
-    }
-
     int agent_prepare(tbx_engine* e) override
     {
-        int rc = alloc_slot(e, dA);
-        if (rc) return rc;
-        return alloc_slot(e, dB);
+        for (GwDev* x : {&dA, &dB}) {
+            if (x->sc) continue;                       // made by an earlier tbx_agent_init (whole: tbx_alloc_arrays)
+            *x = d;                                    // n, the engine's buffers, the config
+            TBX_HIP(tbx_alloc_arrays(*x, (size_t)e->n));
+        }
+        return TBX_OK;
     }
 
     int agent_snapshot(tbx_engine* e, int slot, const uint8_t* exec_flag, uint8_t* buf_valid, hipStream_t s) override
     {
-        dA.cfg = dB.cfg = d.cfg;
-        hipLaunchKernelGGL(gw_snapshot_kernel, wave_grid(e->n), dim3(TBX_BLOCK), 0, s, slot ? dB : dA, d, exec_flag, buf_valid, slot ? 2 : 1);
+        hipLaunchKernelGGL(gw_snapshot_kernel, grid_for(e->n), dim3(TBX_BLOCK), 0, s, slot ? dB : dA, d, exec_flag, buf_valid, slot ? 2 : 1);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
 
     int agent_warp(tbx_engine* e, const AgentWarpArgs& a, hipStream_t s) override
     {
-        dA.cfg = dB.cfg = d.cfg;
-        const dim3 grid = wave_grid(a.end - a.first), block(TBX_BLOCK);
+        const dim3 grid = grid_for(a.end - a.first), block(TBX_BLOCK);
         tbx_dispatch<0, 1, 2, 3, 4>(tbx_stack_arm(a.obs, a.stack), [&](auto depth) {
             hipLaunchKernelGGL(gw_agent_warp_kernel<decltype(depth)::value>, grid, block, 0, s, d, dA, dB, a, e->n);
         });
@@ -682,7 +669,6 @@ struct GridWorldOps : GameOps {
 
     int agent_reset_envs(tbx_engine* e, const AgentResetArgs& r, hipStream_t s) override
     {
-        dA.cfg = dB.cfg = d.cfg;
         const unsigned blocks = (unsigned)((e->n + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK);
         hipLaunchKernelGGL(gw_agent_reset_kernel, dim3(r.list ? std::min(blocks, 1024u) : blocks), dim3(TBX_BLOCK), 0, s, d, dA, dB, r);
         TBX_HIP(hipGetLastError());
@@ -691,7 +677,6 @@ struct GridWorldOps : GameOps {
 
     int render_from(tbx_engine* e, int source, const uint8_t* pick_live, uint8_t* out_dev, int channels, hipStream_t s) override
     {
-        dA.cfg = dB.cfg = d.cfg;
         const GwDev& src = source == 1 ? dA : source == 2 ? dB : d;
         return render_impl(e, src, d, source ? pick_live : nullptr, out_dev, channels, 0, e->n, s);
     }
@@ -711,9 +696,9 @@ struct GridWorldOps : GameOps {
         // against 0.195-0.208, 32 768 equal, 4 096 envs 0.047 against 0.0456: five from 16 384 envs, two below; gray and RGBA one
         const int split = split_env > 0 ? split_env : channels == 3 ? (n_envs >= 16384 ? 5 : 2) : 1;
         if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) {
-                constexpr int C = decltype(ch)::value;
-                if (pick_alt) hipLaunchKernelGGL((gw_render_kernel<C, true>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt);
-                else hipLaunchKernelGGL((gw_render_kernel<C, false>), wave_grid(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt);
+                tbx_dispatch<0, 1>(pick_alt != nullptr, [&](auto with_alt) {
+                    hipLaunchKernelGGL((gw_render_kernel<decltype(ch)::value, decltype(with_alt)::value != 0>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, split, alt, pick_alt);
+                });
             }))
             return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
@@ -744,13 +729,7 @@ struct GridWorldOps : GameOps {
     // layer's two slots (GridWorld has no RNG of its own)
     void copy_envs(tbx_engine*, TbxForkPlan& plan) override
     {
-        const GwDev* const all[3] = {&d, &dA, &dB};
-        for (int k = 0; k < 3; k++) {
-            const GwDev& x = *all[k];
-            plan.soa(x.sc, GF);
-            plan.rows(x.tiles, GT * 3 * sizeof(uint32_t));
-            plan.rows(x.grid, CELLS);
-        }
+        for (GwDev* x : {&d, &dA, &dB}) tbx_fork_arrays(plan, *x, x == &d);
     }
 
     int scalars(tbx_engine* e, int32_t* score_dev, int32_t* lives_dev, int32_t* level_dev, hipStream_t s) override

@@ -57,7 +57,17 @@ struct SiDev {
     int32_t* enemies;     // [N][NEF][64]
     uint32_t* shields;    // [N][64]
     int32_t* lasers;      // [N][NLF][16]
+    // the per-env arrays, declared here ONCE (tbx_common.hpp, TbxLayout): allocation, release and the fork plan follow this list
+    template <class F>
+    constexpr void arrays(F&& f)
+    {
+        f(sc, tbx_rows(HEAD_WORDS * sizeof(int32_t), 1, HEAD_RNG * sizeof(int32_t), 2));
+        f(enemies, tbx_rows(NEF * 64 * sizeof(int32_t)));
+        f(shields, tbx_rows(64 * sizeof(uint32_t)));
+        f(lasers, tbx_rows(NLF * 16 * sizeof(int32_t)));
+    }
 };
+static_assert(sizeof(SiDev) == sizeof(void*) * (1 + 8 + tbx_array_count<SiDev>()), "SiDev: n, the engine's eight buffers, the arrays of arrays()");
 
 struct SiCfg {
     double jitter;
@@ -1853,26 +1863,16 @@ struct SiOps : GameOps {
         memcpy(&k, cfg_pod, sizeof k);
         int rc = load_cfg(e, k);
         if (rc) return rc;
-        const size_t N = (size_t)e->n;
-        d.n = e->n;
-        d.sim_rng = e->sim_rng; d.prev_score = e->prev_score; d.reward = e->reward; d.done = e->done;
-        d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed; d.err_flag = e->err_flag;
-        TBX_HIP(hipMalloc((void**)&d.sc, N * HEAD_WORDS * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&d.enemies, N * NEF * 64 * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&d.shields, N * 64 * sizeof(uint32_t)));
-        TBX_HIP(hipMalloc((void**)&d.lasers, N * NLF * 16 * sizeof(int32_t)));
-        TBX_HIP(recs.alloc(N, 2));
+        tbx_bind_engine(d, e);
+        TBX_HIP(tbx_alloc_arrays(d, (size_t)e->n));
+        TBX_HIP(recs.alloc((size_t)e->n, 2));
         return TBX_OK;
     }
 
     void destroy(tbx_engine*) override
     {
         recs.release();
-        hipFree(d.sc); hipFree(d.enemies); hipFree(d.shields); hipFree(d.lasers);
-        hipFree(dA.sc); hipFree(dA.enemies); hipFree(dA.shields); hipFree(dA.lasers);
-        hipFree(dB.sc); hipFree(dB.enemies); hipFree(dB.shields); hipFree(dB.lasers);
-        hipFree(dKA.sc); hipFree(dKA.enemies); hipFree(dKA.shields); hipFree(dKA.lasers);
-        hipFree(dKB.sc); hipFree(dKB.enemies); hipFree(dKB.shields); hipFree(dKB.lasers);
+        for (SiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_free_arrays(*x);
     }
 
     int get_config(tbx_engine*, void* pod) override { memcpy(pod, &cfg, sizeof cfg); return TBX_OK; }
@@ -1885,8 +1885,6 @@ struct SiOps : GameOps {
         if (k.n_rows != cfg.n_rows || memcmp(k.row_scores, cfg.row_scores, sizeof k.row_scores) != 0) plain = false;
         return load_cfg(e, k);
     }
-
-    static dim3 grid_for(int count) { return dim3((count + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK); }
 
     int new_game(tbx_engine* e, const uint8_t* mask_dev, hipStream_t s) override
     {
@@ -1909,11 +1907,10 @@ struct SiOps : GameOps {
             const bool whole = src.single_env < 0 && !custom && want_recs;
             const bool canon = !custom && plain;               // the short load (si_load_canonical)
             SiRenderRec* const wr = whole ? recs.cur : nullptr;
-            if (src.single_env < 0) {
-                if (canon) TBX_LAUNCH_STEP(e, s, si_step_kernel<true>, grid_for(count), dim3(TBX_BLOCK), d, c, src, flags, first, count, wr);
-                else TBX_LAUNCH_STEP(e, s, si_step_kernel<false>, grid_for(count), dim3(TBX_BLOCK), d, c, src, flags, first, count, wr);
-            } else if (canon) hipLaunchKernelGGL(si_step_kernel<true>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count, wr);
-            else hipLaunchKernelGGL(si_step_kernel<false>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count, wr);
+            tbx_dispatch<0, 1>(canon, [&](auto cn) {
+                if (src.single_env < 0) TBX_LAUNCH_STEP(e, s, si_step_kernel<decltype(cn)::value != 0>, grid_for(count), dim3(TBX_BLOCK), d, c, src, flags, first, count, wr);
+                else hipLaunchKernelGGL(si_step_kernel<decltype(cn)::value != 0>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, src, flags, first, count, wr);
+            });
             recs.valid = whole;
         }
         TBX_HIP(hipGetLastError());
@@ -1928,14 +1925,10 @@ struct SiOps : GameOps {
     int pipeline_auto(int n, bool gather) const override { return (!gather && n < 16384) ? 3 : 0; }
     int records_parity() const override { return recs.par; }
     bool records_valid() const override { return recs.valid; }
-    void rebind_outputs(tbx_engine* e) override
-    {
-        d.reward = e->reward; d.done = e->done; d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed;
-    }
+    void rebind_outputs(tbx_engine* e) override { tbx_bind_outputs(d, e); }
     int step_ahead(tbx_engine* e, const ActionSource& src, uint32_t flags, hipStream_t s) override
     {
-        if (plain) hipLaunchKernelGGL(si_step_kernel<true>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, src, flags, 0, e->n, recs.other);
-        else hipLaunchKernelGGL(si_step_kernel<false>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, src, flags, 0, e->n, recs.other);
+        tbx_dispatch<0, 1>(plain, [&](auto pl) { hipLaunchKernelGGL(si_step_kernel<decltype(pl)::value != 0>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, src, flags, 0, e->n, recs.other); });
         TBX_HIP(hipGetLastError());
         recs.stepped_ahead();
         return TBX_OK;
@@ -1965,26 +1958,14 @@ struct SiOps : GameOps {
     bool multi_frame_step() const override { return true; }
     bool agent_reset_supported() const override { return true; }
 
-    int alloc_slot(tbx_engine* e, SiDev& x)
-    {
-        if (x.sc) return TBX_OK;
-        const size_t N = (size_t)e->n;
-        x = d;
-        x.sc = nullptr; x.enemies = nullptr; x.shields = nullptr; x.lasers = nullptr;
-        TBX_HIP(hipMalloc((void**)&x.sc, N * HEAD_WORDS * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&x.enemies, N * NEF * 64 * sizeof(int32_t)));
-        TBX_HIP(hipMalloc((void**)&x.shields, N * 64 * sizeof(uint32_t)));
-        TBX_HIP(hipMalloc((void**)&x.lasers, N * NLF * 16 * sizeof(int32_t)));
-        return TBX_OK;
-    }
-
     int agent_prepare(tbx_engine* e) override
     {
-        int rc = alloc_slot(e, dA);
-        if (!rc) rc = alloc_slot(e, dB);
-        if (!rc) rc = alloc_slot(e, dKA);
-        if (!rc) rc = alloc_slot(e, dKB);
-        return rc;
+        for (SiDev* x : {&dA, &dB, &dKA, &dKB}) {
+            if (x->sc) continue;                       // made by an earlier tbx_agent_init (whole: tbx_alloc_arrays)
+            *x = d;                                    // n, the engine's buffers
+            TBX_HIP(tbx_alloc_arrays(*x, (size_t)e->n));
+        }
+        return TBX_OK;
     }
 
     int agent_warp(tbx_engine* e, const AgentWarpArgs& a, hipStream_t s) override
@@ -2032,8 +2013,7 @@ struct SiOps : GameOps {
             ActionSource sj = src;
             sj.t = src.t + (uint64_t)j;
             SiRenderRec* const wr = j + 1 < k ? recs.chunk[q].p + (size_t)(j + 1) * N : nullptr;
-            if (plain) hipLaunchKernelGGL(si_step_kernel<true>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, dj, c, sj, flags, 0, e->n, wr);
-            else hipLaunchKernelGGL(si_step_kernel<false>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, dj, c, sj, flags, 0, e->n, wr);
+            tbx_dispatch<0, 1>(plain, [&](auto pl) { hipLaunchKernelGGL(si_step_kernel<decltype(pl)::value != 0>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, dj, c, sj, flags, 0, e->n, wr); });
         }
         TBX_HIP(hipGetLastError());
         recs.valid = false;                                    // the single-frame records no longer show the state
@@ -2097,9 +2077,9 @@ struct SiOps : GameOps {
         // block's waves through LDS were built and measured this round: both slower (profiles/HISTORY.md).
         const int split = split_env > 0 ? split_env : channels == 3 ? 5 : (channels == 4 && n_envs <= 32768) ? 5 : 1;
         if (!tbx_dispatch<1, 3, 4>(channels, [&](auto ch) {
-                constexpr int C = decltype(ch)::value;
-                if (pick_alt) hipLaunchKernelGGL((si_render_kernel<C, true>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt);
-                else hipLaunchKernelGGL((si_render_kernel<C, false>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt);
+                tbx_dispatch<0, 1>(pick_alt != nullptr, [&](auto with_alt) {
+                    hipLaunchKernelGGL((si_render_kernel<decltype(ch)::value, decltype(with_alt)::value != 0>), grid_for(n_envs * split), dim3(TBX_BLOCK), 0, s, src, out_dev, first_env, n_envs, skip_blank, split, alt, pick_alt);
+                });
             }))
             return e->fail(TBX_E_INVALID, "channels must be 1, 3 or 4");
         TBX_HIP(hipGetLastError());
@@ -2174,14 +2154,7 @@ struct SiOps : GameOps {
     // env is canonical)
     void copy_envs(tbx_engine*, TbxForkPlan& plan) override
     {
-        const SiDev* const all[5] = {&d, &dA, &dB, &dKA, &dKB};   // (the kept copies too: mode 2 travels with the env)
-        for (int k = 0; k < 5; k++) {
-            const SiDev& x = *all[k];
-            plan.rows(x.sc, HEAD_WORDS * sizeof(int32_t), 1, k == 0 ? HEAD_RNG * sizeof(int32_t) : 0, k == 0 ? 2 : 0);
-            plan.rows(x.enemies, NEF * 64 * sizeof(int32_t));
-            plan.rows(x.shields, 64 * sizeof(uint32_t));
-            plan.rows(x.lasers, NLF * 16 * sizeof(int32_t));
-        }
+        for (SiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_fork_arrays(plan, *x, x == &d);   // (the kept copies too: mode 2 travels with the env)
         recs.valid = false;
     }
 

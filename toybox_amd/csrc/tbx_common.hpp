@@ -583,6 +583,85 @@ struct TbxForkPlan {
     }
 };
 
+// How one per-env device array of a state struct (AmiDev, SiDev, GwDev, BrkDev, ...) lies in memory, in the two forms the fork
+// plan takes.  Every such struct lists its arrays ONCE, in a constexpr member template `arrays(f)` that calls f(member, TbxLayout)
+// per array; allocation, release and the fork plan of an instance are derived from that list by the helpers below, and a
+// static_assert next to the list compares tbx_array_count with the struct's size, so a pointer member without an entry does not build.
+struct TbxLayout {
+    uint32_t fields, row_bytes, rng_off, rng_words;   // row_bytes 0: the element's size
+    bool lazy;                                        // made on demand by a call of its own, not with the instance (BrkDev::custom)
+};
+constexpr TbxLayout tbx_soa(int fields, int rng_words = 0) { return TbxLayout{(uint32_t)fields, 0u, 0u, (uint32_t)rng_words, false}; }   // [fields][N] elements
+constexpr TbxLayout tbx_rows(size_t row_bytes, int fields = 1, size_t rng_off = 0, int rng_words = 0)                            // [fields][N][row_bytes]
+{
+    return TbxLayout{(uint32_t)fields, (uint32_t)row_bytes, (uint32_t)rng_off, (uint32_t)rng_words, false};
+}
+constexpr TbxLayout tbx_lazy(TbxLayout l) { l.lazy = true; return l; }
+template <class Dev>
+constexpr int tbx_array_count()
+{
+    Dev x{};
+    int k = 0;
+    x.arrays([&k](auto*&, TbxLayout) { k++; });
+    return k;
+}
+// f(void** member, layout with row_bytes filled in, bytes for n envs) per array
+template <class Dev, class F>
+void tbx_each_array(Dev& x, size_t n, F&& f)
+{
+    x.arrays([&](auto*& p, TbxLayout l) {
+        if (!l.row_bytes) l.row_bytes = (uint32_t)sizeof(*p);
+        f(reinterpret_cast<void**>(&p), l, (size_t)l.fields * n * l.row_bytes);
+    });
+}
+template <class Dev>
+void tbx_free_arrays(Dev& x)
+{
+    tbx_each_array(x, 0, [](void** p, TbxLayout, size_t) { hipFree(*p); *p = nullptr; });
+}
+// Every listed array of one instance for n envs (lazy: the lazy ones instead).  All or nothing: after a failed hipMalloc what was
+// made is freed again and every one of these pointers is null, so "already made" is any one of them.  (What the pointers held
+// before is NOT freed: a snapshot slot starts as a copy of the live state.)
+template <class Dev>
+hipError_t tbx_alloc_arrays(Dev& x, size_t n, bool lazy = false)
+{
+    hipError_t r = hipSuccess;
+    tbx_each_array(x, n, [&](void** p, TbxLayout l, size_t) { if (l.lazy == lazy) *p = nullptr; });
+    tbx_each_array(x, n, [&](void** p, TbxLayout l, size_t bytes) {
+        if (l.lazy == lazy && r == hipSuccess && (r = hipMalloc(p, bytes)) != hipSuccess) *p = nullptr;
+    });
+    if (r != hipSuccess) tbx_each_array(x, n, [&](void** p, TbxLayout l, size_t) { if (l.lazy == lazy) { hipFree(*p); *p = nullptr; } });
+    return r;
+}
+template <class Dev>
+hipError_t tbx_zero_arrays(Dev& x, size_t n)
+{
+    hipError_t r = hipSuccess;
+    tbx_each_array(x, n, [&](void** p, TbxLayout, size_t bytes) { if (r == hipSuccess && *p) r = hipMemset(*p, 0, bytes); });
+    return r;
+}
+// the arrays of one instance that exist, appended to a fork plan; live: its RNG words are the ones the fork's `salt` rewrites
+template <class Dev>
+void tbx_fork_arrays(TbxForkPlan& plan, Dev& x, bool live)
+{
+    tbx_each_array(x, 0, [&](void** p, TbxLayout l, size_t) { plan.rows(*p, l.row_bytes, (int)l.fields, live ? l.rng_off : 0, live ? (int)l.rng_words : 0); });
+}
+// what every game's state struct holds of the engine's common buffers (duck-typed: the structs order these members differently)
+template <class Dev>
+void tbx_bind_outputs(Dev& d, const tbx_engine* e)
+{
+    d.reward = e->reward; d.done = e->done; d.lives_out = e->lives_out; d.score_out = e->score_out; d.packed = e->packed;
+}
+template <class Dev>
+void tbx_bind_engine(Dev& d, const tbx_engine* e)
+{
+    d.n = e->n;
+    d.sim_rng = e->sim_rng; d.prev_score = e->prev_score; d.err_flag = e->err_flag;
+    tbx_bind_outputs(d, e);
+}
+// one wave per item, TBX_WAVES_PER_BLOCK waves per block
+inline dim3 grid_for(int count) { return dim3((count + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK); }
+
 // per-game operations; all launches are asynchronous on `s`
 struct GameOps {
     virtual ~GameOps() {}
