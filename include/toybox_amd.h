@@ -574,6 +574,36 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
  *   The host form copies in one pass when no selected destination is another selected row's source; otherwise, and always in
  *   the device form, the rows are gathered into a scratch copy first (allocated on first use, as large as the copied arrays). */
 #define TBX_EDIT_COPY_ENV          40   /* {src[, salt]} */
+/* every game -- CHECKPOINTS: env states set aside on the device and taken up again later.  The fork branches inside the batch,
+ * but every call steps every env, so no slot of the batch can hold a state still; a store of cells beside the batch can.  It
+ * replaces to_state_json ... write_state_json LATER (interventions/base.py:391-406) for tree search, archives of start states
+ * and "same state, K policies" sweeps, with nothing leaving HBM.
+ *   TBX_EDIT_CHECKPOINT_SLOTS {slots}, tbx_edit only, mask NULL, per_env 0: makes the engine's checkpoint store -- `slots` >= 1
+ *   planes of N cells, all empty; cell (slot, row) holds one env.  0 releases the store.  An existing store is released first
+ *   (its contents are lost); on TBX_E_NOMEM the engine has no store.  tbx_edit_device returns TBX_E_INVALID for this op.
+ *   tbx_destroy frees the store.
+ *   TBX_EDIT_CHECKPOINT_SAVE {slot}, the same for every env or one row per env: every selected env i is written into cell
+ *   (slot_i, i), which becomes valid.  Saved: exactly what TBX_EDIT_COPY_ENV copies (above).  A save changes nothing in the live
+ *   engine -- step-written render records stay in force, so a rollout loop that saves every K steps keeps its record path.
+ *   TBX_EDIT_CHECKPOINT_RESTORE {slot[, row[, salt]]}: every selected env i becomes the env stored in cell (slot_i, row_i); row
+ *   absent or -1: the env's own row i.  salt as in the fork: every RNG word of the restored env becomes splitmix64(word ^ salt),
+ *   0 or absent: none.  The env's next step with the same action returns what the saved env's next step returned.  What the
+ *   fork does not copy stays as it is here too: the outputs of the last step (TBX_BUF_REWARD .. TBX_BUF_AGENT_EP_LENGTH), the
+ *   gather ring, the batch-wide config, tbx_agent_set_noops counts and env_offset.  The plane ring is stored oldest plane first,
+ *   so a restore at another ring head than the save's puts every plane where that head expects it.  Step-written render records
+ *   are stale afterwards, as after any edit.
+ *   Errors: tbx_edit checks first (a small kernel and an 8-byte read-back) and changes nothing on an error: TBX_E_INVALID, naming
+ *   the first offending env, when there is no store, when a selected row names a slot outside 0 .. slots-1 or a row outside
+ *   0 .. N-1, or when a restore names an empty cell.  tbx_edit_device cannot report: such an env is left untouched, on save and
+ *   on restore, and the others go through.
+ *   A store belongs to the set of per-env arrays that existed when it was made ({planes, row bytes} of each, in order).  When
+ *   that set has changed -- Breakout left the canonical wall (its per-env brick table appeared), the generic path's gray frames
+ *   were allocated, tbx_agent_init was called (again, with another geometry, stack or new_plane) -- SAVE and RESTORE return
+ *   TBX_E_UNSUPPORTED and touch nothing until TBX_EDIT_CHECKPOINT_SLOTS makes a new store.  Restoring under a different
+ *   batch-wide config is the caller's business, as with tbx_set_state. */
+#define TBX_EDIT_CHECKPOINT_SLOTS   41  /* {slots} */
+#define TBX_EDIT_CHECKPOINT_SAVE    42  /* {slot} */
+#define TBX_EDIT_CHECKPOINT_RESTORE 43  /* {slot[, row[, salt]]} */
 
 #define TBX_QUERY_BRK_BRICKS_REMAINING 110  /* -> 1  num_bricks_remaining :309-310 */
 #define TBX_QUERY_BRK_NUM_BRICKS       111  /* -> 1  num_bricks :312-313 */
@@ -606,6 +636,9 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
                                              * as written); get_random_tile :360-378, get_random_track_position :380-386 (tag_mask 14); -1 x 3, 0 without a candidate */
 #define TBX_QUERY_AMI_RANDOM_DIR       134  /* {seed, draw, env_offset, tx, ty} -> 2  direction (TBX_DIR_*) drawn among those of Up, Down, Left, Right whose
                                              * neighbour tile is walkable, and their number (get_random_dir_for_tile :550-583); -1, 0 if none */
+/* every game */
+#define TBX_QUERY_CHECKPOINT_VALID     140  /* {slot[, row]} -> 1  1: cell (slot, row) holds an env, 0: it is empty, -1: no such cell or no store
+                                             * (row absent or -1: the env's own row); tbx_reduce_width is 1 for every game */
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);

@@ -66,6 +66,9 @@ EDIT_AMI_PLAYER_TILE = 24
 EDIT_AMI_PLAYER_RANDOM_START = 25
 EDIT_SI_UFO_APPEARANCE = 30
 EDIT_COPY_ENV = 40
+EDIT_CHECKPOINT_SLOTS = 41
+EDIT_CHECKPOINT_SAVE = 42
+EDIT_CHECKPOINT_RESTORE = 43
 QUERY_BRK_BRICKS_REMAINING = 110
 QUERY_BRK_NUM_BRICKS = 111
 QUERY_BRK_COLUMN = 112
@@ -90,6 +93,7 @@ QUERY_SI_SHIP = 130
 QUERY_AMI_TILES_MASK = 131
 QUERY_AMI_RANDOM_TILE = 133
 QUERY_AMI_RANDOM_DIR = 134
+QUERY_CHECKPOINT_VALID = 140
 
 BRK_MAX_BALLS, BRK_COLS, BRK_MAX_ROWS, BRK_MAX_BRICKS, BRK_MAX_STARTS, BRK_MAX_SEGMENTS = 4, 18, 14, 256, 8, 16
 

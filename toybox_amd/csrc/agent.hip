@@ -349,7 +349,7 @@ void agent_arrays(tbx_engine* e, bool generic, F&& f)
         f(AgentArray{reinterpret_cast<void**>(&p), elems * sizeof(*p), N, fields, fill, made, in_env});
     };
     auto fixed = [&](auto*& p, size_t count, int fill) { f(AgentArray{reinterpret_cast<void**>(&p), sizeof(*p), count, 1, fill, true, false}); };
-    // the wrapper stack's per-env state (the two buffer slots themselves live with the game: GameOps::copy_envs) ...
+    // the wrapper stack's per-env state (the two buffer slots themselves live with the game: GameOps::list_envs) ...
     per_env(a.ep_ret, 1, 0, true); per_env(a.ep_len, 1, 0, true); per_env(a.ep_index, 1, 0, true); per_env(a.prev_lives, 1, 0, true);
     per_env(a.needs_reset, 1, 0, true);
     per_env(a.was_real_done, 1, 1, true);                  // EpisodicLifeEnv.__init__: was_real_done = True
@@ -502,12 +502,18 @@ void tbx_agent_free(tbx_engine* e)
     e->agent = nullptr;
 }
 
-// TBX_EDIT_COPY_ENV: the arrays the table marks as part of an env (those that exist: TbxForkPlan::rows skips a null base).  The
-// outputs of the last step, the no-op overrides and the per-step scratch are not.
+// TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: the arrays the table marks as part of an env (those that exist: TbxForkPlan::rows
+// skips a null base).  The outputs of the last step, the no-op overrides and the per-step scratch are not.  The plane ring says
+// which of its planes is the oldest right now (TbxForkSeg::rot).
 void tbx_agent_copy_envs(tbx_engine* e, TbxForkPlan& plan)
 {
     if (!e->agent) return;
-    agent_arrays(e, true, [&](AgentArray x) { if (x.in_env) plan.rows(*x.p, x.row_bytes, x.fields); });
+    AgentState& a = *e->agent;
+    agent_arrays(e, true, [&](AgentArray x) {
+        if (!x.in_env || !*x.p) return;
+        plan.rows(*x.p, x.row_bytes, x.fields);
+        if (*x.p == a.ring) plan.segs.back().rot = (uint32_t)((a.head + 1) % a.cfg.stack);
+    });
 }
 
 int tbx_agent_buffer(tbx_engine* e, int which, void** out_ptr, size_t* out_bytes)

@@ -2225,7 +2225,7 @@ struct AmiOps : GameOps {
 
     // TBX_EDIT_COPY_ENV: scalars and RNG (struct of arrays), the env-major tiles / boxes / movers and the movers' struct-of-arrays
     // mirror, of the live state and of the agent layer's two slots
-    void copy_envs(tbx_engine*, TbxForkPlan& plan) override
+    void list_envs(tbx_engine*, TbxForkPlan& plan) override
     {
         for (AmiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_fork_arrays(plan, *x, x == &d);   // (the kept copies too: mode 2 travels with the env)
     }

@@ -2331,12 +2331,12 @@ struct BreakoutOps : GameOps {
 
     // TBX_EDIT_COPY_ENV: the struct-of-arrays state, the per-env brick table of the custom mode and the two record slots of the
     // agent layer (a copy of a canonical env is canonical: `custom` stays as it is)
-    void copy_envs(tbx_engine*, TbxForkPlan& plan) override
+    void list_envs(tbx_engine*, TbxForkPlan& plan) override
     {
         tbx_fork_arrays(plan, d, true);
         tbx_fork_arrays(plan, slots, false);           // (the kept copies too: an env copied while its observation is the kept buffer's)
-        recs.valid = false;
     }
+    void envs_rewritten(tbx_engine*) override { recs.valid = false; }
 
     int reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s) override
     {

@@ -727,7 +727,7 @@ struct GridWorldOps : GameOps {
 
     // TBX_EDIT_COPY_ENV: scalars (struct of arrays), the env-major tile table and grid, of the live state and of the agent
     // layer's two slots (GridWorld has no RNG of its own)
-    void copy_envs(tbx_engine*, TbxForkPlan& plan) override
+    void list_envs(tbx_engine*, TbxForkPlan& plan) override
     {
         for (GwDev* x : {&d, &dA, &dB}) tbx_fork_arrays(plan, *x, x == &d);
     }

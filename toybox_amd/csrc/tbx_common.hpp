@@ -440,6 +440,12 @@ struct tbx_engine {
     TbxDevBuf<double> reduce_out;   // [N][width] result staging of tbx_reduce
     TbxDevBuf<void> staging;        // device POD staging for get/set state
     TbxDevBuf<uint8_t> fork_scratch;   // TBX_EDIT_COPY_ENV: the gathered rows between the two passes of a fork (engine.hip, fork_envs)
+    // TBX_EDIT_CHECKPOINT_*: `ckpt_slots` planes of N env cells, each plane laid out like the fork's scratch (every per-env array
+    // at a 256-byte-aligned offset, ckpt_slot_bytes in all), then valid[slots][N] and the two words of the host forms' check
+    TbxDevBuf<uint8_t> ckpt_store;
+    int ckpt_slots = 0;
+    size_t ckpt_slot_bytes = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> ckpt_sig;   // {fields, row_bytes} of the arrays the store was made for, in plan order
     GameOps* ops = nullptr;
     struct AgentState* agent = nullptr;   // fused agent-side preprocessing (agent.hip), lazily created
     struct GatherState* gather = nullptr; // multi-GPU record gather over RCCL (gather.hip), created by tbx_gather_init
@@ -462,7 +468,7 @@ struct tbx_engine {
 hipError_t tbx_serve_stop(tbx_engine* e);   // engine.hip
 hipError_t tbx_finish_pending(tbx_engine* e);   // engine.hip: ends a step that is between "_begin" and "_end" (outputs delivered, result kept)
 int tbx_agent_deliver(tbx_engine* e);       // agent.hip: the waiting half of tbx_agent_step_end
-void tbx_agent_copy_envs(tbx_engine* e, struct TbxForkPlan& plan);   // agent.hip: the wrapper stack's per-env arrays of TBX_EDIT_COPY_ENV
+void tbx_agent_copy_envs(tbx_engine* e, struct TbxForkPlan& plan);   // agent.hip: the wrapper stack's per-env arrays of TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*
 
 // Stream `s` waits for everything queued so far on the stream the previous call used.  That stream may be the caller's: the
 // handle is kept until the next call or tbx_sync (toybox_amd.h: a stream named in a call must stay alive that long -- the
@@ -565,21 +571,23 @@ struct TbxEditArgs {
 // N rows of row_bytes each, [fields][N][row_bytes].  A struct-of-arrays scalar [F][N] is F planes of 4- or 8-byte rows, an
 // env-major table [N][R] one plane of R-byte rows, the plane ring `stack` planes of out_h * out_w bytes.  rng_words > 0: every
 // row holds that many 64-bit RNG words at byte rng_off (what the fork's `salt` argument rewrites in the destinations).
+// rot: the plane that is first in LOGICAL order (the plane ring: its oldest plane, head + 1); the fork copies planes as they lie
+// and ignores it, a checkpoint cell keeps them in logical order (engine.hip, checkpoint_copy).
 struct TbxForkSeg {
     uint8_t* base;
     uint64_t scratch_off;         // where the array's gathered copy lies in tbx_engine::fork_scratch (filled in by fork_envs)
-    uint32_t fields, row_bytes, rng_off, rng_words;
+    uint32_t fields, row_bytes, rng_off, rng_words, rot;
 };
 struct TbxForkPlan {
     std::vector<TbxForkSeg> segs;
     template <typename T>
     void soa(T* base, int fields, int rng_words = 0)           // [fields][N] scalars
     {
-        if (base) segs.push_back(TbxForkSeg{reinterpret_cast<uint8_t*>(base), 0, (uint32_t)fields, (uint32_t)sizeof(T), 0u, (uint32_t)rng_words});
+        if (base) segs.push_back(TbxForkSeg{reinterpret_cast<uint8_t*>(base), 0, (uint32_t)fields, (uint32_t)sizeof(T), 0u, (uint32_t)rng_words, 0u});
     }
     void rows(void* base, size_t row_bytes, int fields = 1, size_t rng_off = 0, int rng_words = 0)   // [fields][N][row_bytes]
     {
-        if (base) segs.push_back(TbxForkSeg{static_cast<uint8_t*>(base), 0, (uint32_t)fields, (uint32_t)row_bytes, (uint32_t)rng_off, (uint32_t)rng_words});
+        if (base) segs.push_back(TbxForkSeg{static_cast<uint8_t*>(base), 0, (uint32_t)fields, (uint32_t)row_bytes, (uint32_t)rng_off, (uint32_t)rng_words, 0u});
     }
 };
 
@@ -735,10 +743,12 @@ struct GameOps {
     // batched interventions (include/toybox_amd.h, tbx_edit / tbx_reduce): one kernel over the selected envs
     virtual int edit(tbx_engine* e, int /*op*/, const TbxEditArgs&, const uint8_t* /*mask_dev*/, hipStream_t) { return e->fail(TBX_E_INVALID, "this game has no such edit"); }
     virtual int reduce(tbx_engine* e, int /*query*/, const TbxEditArgs&, double* /*out_dev*/, int /*width*/, hipStream_t) { return e->fail(TBX_E_INVALID, "this game has no such query"); }
-    // TBX_EDIT_COPY_ENV: every per-env array that decides the env's future outputs -- the game state, its device-only mirrors and
-    // (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan; step-written render records
-    // no longer describe the state afterwards.  The engine adds sim_rng, prev_score and the agent layer and runs the copy.
-    virtual void copy_envs(tbx_engine* e, TbxForkPlan& plan) = 0;
+    // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
+    // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The
+    // engine adds sim_rng, prev_score and the agent layer and runs the copy.  Listing changes nothing; a copy that WROTE live
+    // envs (a fork, a restore -- not a save) says so with envs_rewritten(): step-written render records no longer describe the state.
+    virtual void list_envs(tbx_engine* e, TbxForkPlan& plan) = 0;
+    virtual void envs_rewritten(tbx_engine*) {}
     // an engine option changed (tbx_set_option): pick it up
     virtual void options_changed(tbx_engine*) {}
     // generic path: full-resolution gray frames of slot A (source 1), slot B (2) or the live state (0); envs whose

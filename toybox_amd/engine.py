@@ -57,6 +57,26 @@ class HostArray:
         return np.frombuffer(buf, dtype=dt, count=count).reshape(shape)
 
 
+def checkpoint_args(n_envs, slot, rows=None, salt=None):
+    """The argument rows of TBX_EDIT_CHECKPOINT_SAVE / _RESTORE and TBX_QUERY_CHECKPOINT_VALID: columns {slot[, row[, salt]]},
+    trailing absent ones dropped, a salt without rows with -1 ("the env's own row") in the row column.  All scalars: a list, the
+    same for every env; any column one per env: float64 [N, columns] (a scalar column broadcasts; a wrong length raises)."""
+    cols = [slot]
+    if rows is not None or salt is not None:
+        cols.append(-1 if rows is None else rows)
+    if salt is not None:
+        cols.append(salt)
+    if not any(np.ndim(c) for c in cols):
+        return [float(c) for c in cols]
+    args = np.empty((int(n_envs), len(cols)), np.float64)
+    for k, c in enumerate(cols):
+        c = np.asarray(c, np.float64)
+        if c.ndim > 1 or (c.ndim == 1 and c.shape[0] != int(n_envs)):
+            raise ValueError("checkpoint arguments are ints or one value per env (%d), got shape %r" % (n_envs, c.shape))
+        args[:, k] = c
+    return args
+
+
 class Engine:
     def __init__(self, game, n_envs=1, device=0, config=None, lib=None):
         self._lib = lib if lib is not None else load()
@@ -290,6 +310,25 @@ class Engine:
         else:
             args = [float(c) for c in cols]
         self.edit(_abi.EDIT_COPY_ENV, args, mask)
+
+    def checkpoint_slots(self, slots):
+        """TBX_EDIT_CHECKPOINT_SLOTS: a fresh, empty checkpoint store of `slots` planes of N cells on the device (an existing one
+        is released first; 0 releases it).  The store belongs to the per-env arrays the engine has now: call this after agent_init."""
+        self.edit(_abi.EDIT_CHECKPOINT_SLOTS, [int(slots)])
+
+    def checkpoint_save(self, slot, mask=None):
+        """TBX_EDIT_CHECKPOINT_SAVE: every env whose mask entry is true (None: all) is written into cell (slot, its own row) --
+        everything fork() copies; slot an int or int[N].  Nothing in the live engine changes."""
+        self.edit(_abi.EDIT_CHECKPOINT_SAVE, checkpoint_args(self.n_envs, slot), mask)
+
+    def checkpoint_restore(self, slot, rows=None, mask=None, salt=None):
+        """TBX_EDIT_CHECKPOINT_RESTORE: every selected env i becomes the env saved in cell (slot, rows[i]) (rows None: its own row);
+        slot, rows, salt each an int or one per env; salt as in fork()."""
+        self.edit(_abi.EDIT_CHECKPOINT_RESTORE, checkpoint_args(self.n_envs, slot, rows, salt), mask)
+
+    def checkpoint_valid(self, slot, rows=None):
+        """TBX_QUERY_CHECKPOINT_VALID as int8[N]: 1 cell (slot, rows[i] or i) holds an env, 0 it is empty, -1 no such cell or no store"""
+        return self.reduce(_abi.QUERY_CHECKPOINT_VALID, checkpoint_args(self.n_envs, slot, rows))[:, 0].astype(np.int8)
 
     def reduce(self, query, args=()):
         """tbx_reduce: a per-env feature as float64 [N, width] (integers are exact; missing entries read -1)"""

@@ -203,6 +203,27 @@ class ToyboxVecEnv:
         self.engine.fork(s, mask=sel, salt=salt)
         return self._frames()
 
+    def checkpoint_slots(self, slots):
+        """A fresh, empty checkpoint store of `slots` planes of num_envs cells on the device (Engine.checkpoint_slots); 0 releases it"""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        self.engine.checkpoint_slots(slots)
+
+    def save_checkpoint(self, slot, envs=None):
+        """The envs `envs` (None: all; a boolean mask or indices) are set aside in cell (slot, their own row) of the store.  Between
+        step_async and step_wait the step ends first (its results are dropped)."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        self.engine.checkpoint_save(slot, mask=_fork_map(self.num_envs, 0, envs)[1])
+
+    def restore_checkpoint(self, slot, rows=None, envs=None, salt=None):
+        """The envs `envs` become the envs saved in cell (slot, rows[i]) (rows None: their own row); salt as in fork().  Returns the
+        observation batch the policy should see next, as fork() does.  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        self.engine.checkpoint_restore(slot, rows=rows, mask=_fork_map(self.num_envs, 0, envs)[1], salt=salt)
+        return self._frames()
+
     def get_images(self):
         return self.engine.render(3)
 
@@ -450,6 +471,58 @@ class ToyboxPreprocVecEnv:
         if out is not prev:
             out[...] = prev
         out[dst] = prev[s[dst]]
+        self._stacked = out
+        return self._obs(out)
+
+    def checkpoint_slots(self, slots):
+        """A fresh, empty checkpoint store of `slots` planes of num_envs cells on the device (Engine.checkpoint_slots); 0 releases it"""
+        if self._in_flight is not None:
+            self.step_wait()
+        self.engine.checkpoint_slots(slots)
+
+    def save_checkpoint(self, slot, envs=None):
+        """The envs `envs` (None: all; a boolean mask or indices) are set aside in cell (slot, their own row) of the store: the game,
+        the wrapper stack's per-env state and the frame stack, as the device holds them.  Between step_async and step_wait the step
+        ends first (its results are dropped)."""
+        if self._in_flight is not None:
+            self.step_wait()
+        self.engine.checkpoint_save(slot, mask=_fork_map(self.num_envs, 0, envs)[1])
+
+    def restore_checkpoint(self, slot, rows=None, envs=None, salt=None):
+        """The envs `envs` become the envs saved in cell (slot, rows[i]) (rows None: their own row); salt as in fork().  Returns the
+        observation batch the policy should see next, as fork() does.  The host-side stacks of obs_layout="planes" (in place) and
+        "host_stack" (into the next array of the pool) take the restored envs' planes from the device's plane ring, oldest first;
+        the other envs' host data stays.  Between step_async and step_wait the step ends first (its results are dropped)."""
+        if self._in_flight is not None:
+            self.step_wait()
+        sel = _fork_map(self.num_envs, 0, envs)[1]
+        self.engine.checkpoint_restore(slot, rows=rows, mask=sel, salt=salt)
+        if self.obs_layout == "device_stack":
+            obs = self._next_obs_array()
+            self.engine.agent_fetch(obs=obs)
+            return self._obs(obs)
+        from .. import hip
+        k, n = self.stack, self.num_envs
+        ptr, nbytes = self.engine.device_buffer(_abi.BUF_AGENT_RING)
+        ring = np.empty((k, n, self.size, self.size), np.uint8)
+        self.engine.sync()
+        hip.memcpy_dtoh(ring, ptr, nbytes)
+        head = self.engine.agent_ring_head()
+        logical = [ring[(head + 1 + c) % k] for c in range(k)]           # oldest first
+        idx = np.flatnonzero(sel)
+        if self.obs_layout == "planes":
+            R = len(self._ring)
+            planes = [self._ring[(self._head - j) % R] for j in range(k)][::-1]
+            for p, src in zip(planes, logical):
+                p[idx] = src[idx]
+            return self._obs(PlaneStack(planes))
+        if self._stacked is None:
+            raise RuntimeError("restore_checkpoint before the first reset()")
+        prev, out = self._stacked, self._next_obs_array()
+        if out is not prev:
+            out[...] = prev
+        for c, src in enumerate(logical):
+            out[idx, :, :, c] = src[idx]
         self._stacked = out
         return self._obs(out)
 
