@@ -639,6 +639,28 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
 /* every game */
 #define TBX_QUERY_CHECKPOINT_VALID     140  /* {slot[, row]} -> 1  1: cell (slot, row) holds an env, 0: it is empty, -1: no such cell or no store
                                              * (row absent or -1: the env's own row); tbx_reduce_width is 1 for every game */
+/* Lookahead: what happens to every env over the next `frames` frames under an action schedule -- computed from the state as it
+ * stands, in registers, and thrown away: NOTHING in the engine changes (state, sim RNGs, prev_score, step outputs, render
+ * records, agent layer, checkpoint store, the error flag), so no later frame or observation differs.
+ *   Schedule: the horizon (1 .. TBX_LOOKAHEAD_MAX_FRAMES frames) is cut into periods of `hold` (>= 1) frames, frame j in period
+ *   p = j / hold.  Period 0 plays `first`, every later one `rest`: an ALE action id of the game's legal set, or -1 = drawn by the
+ *   rule of tbx_step_synthetic with counter t + p: legal[splitmix64(seed ^ ((env_offset + env) << 32) ^ (t + p)) % n_legal],
+ *   seed = seed_lo | seed_hi << 32 (seed_lo, seed_hi, t, env_offset: integers below 2^32).  hold = 1, first = rest = -1 foretells
+ *   tbx_step_synthetic(seed, t + j, env_offset) without auto-reset.  Trailing arguments may be left out: hold 1, first -1,
+ *   rest -1, seed 0, t 0, env_offset 0.  TBX_QUERY_LOOKAHEAD_ALL answers once per legal action a (in legal-set order: Breakout
+ *   0 1 3 4, Amidar 0 .. 5, SpaceInvaders 0 1 3 4 11 12, GridWorld 0 2 3 4 5) with first = legal[a], row out[env][a][0 .. 4].
+ *   Run: frames 0 .. frames-1 through the game's own step, ending after the first frame that leaves lives <= 0 (an env whose game
+ *   is already over still runs frame 0); no auto-reset, no draw from the sim RNG, no wrapper of the agent layer -- raw frames
+ *   (with the agent layer on pass hold = skip).
+ *   Out, five doubles: [0] return = sum of max(score_j - score_{j-1}, 0), score_{-1} the state's score now; [1] score and
+ *   [2] lives after the last frame run; [3] frames run; [4] index of the first frame after which lives is below the lives at
+ *   the start, -1 if none.
+ *   TBX_E_INVALID, nothing launched: frames outside 1 .. 1024, hold < 1, more than 8 arguments, a shared first / rest that is
+ *   neither -1 nor legal.  In per-env rows such an env's output (every candidate of it) is five zeros -- frames run 0 -- and the
+ *   other envs are answered. */
+#define TBX_LOOKAHEAD_MAX_FRAMES 1024
+#define TBX_QUERY_LOOKAHEAD      150  /* {frames, hold, first, rest, seed_lo, seed_hi, t, env_offset} -> 5 */
+#define TBX_QUERY_LOOKAHEAD_ALL  151  /* {frames, hold, (ignored), rest, seed_lo, seed_hi, t, env_offset} -> 5 * n_legal(game) */
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);

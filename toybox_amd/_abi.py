@@ -94,6 +94,9 @@ QUERY_AMI_TILES_MASK = 131
 QUERY_AMI_RANDOM_TILE = 133
 QUERY_AMI_RANDOM_DIR = 134
 QUERY_CHECKPOINT_VALID = 140
+LOOKAHEAD_MAX_FRAMES = 1024
+QUERY_LOOKAHEAD = 150
+QUERY_LOOKAHEAD_ALL = 151
 
 BRK_MAX_BALLS, BRK_COLS, BRK_MAX_ROWS, BRK_MAX_BRICKS, BRK_MAX_STARTS, BRK_MAX_SEGMENTS = 4, 18, 14, 256, 8, 16
 

@@ -1264,6 +1264,28 @@ __global__ __launch_bounds__(TBX_BLOCK) void ami_step_kernel(AmiDev d, ActionSou
     ami_step_body<false>(d, d, d, src, flags, first_env + rel, lane);
 }
 
+// TBX_QUERY_LOOKAHEAD / _ALL: one wave per (env, candidate); one load, `frames` turns of ami_step on the registers, no store; the
+// exit at game over is wave-uniform.  cands = 1: the single form.
+__global__ __launch_bounds__(TBX_BLOCK) void ami_lookahead_kernel(AmiDev d, TbxEditArgs a, int cands, long long first_pair, int count, double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int rel = wave_uniform(blockIdx.x * TBX_WAVES_PER_BLOCK + (threadIdx.x >> 6));
+    if (rel >= count) return;
+    const long long pair = first_pair + rel;
+    const int env = wave_uniform((int)(pair / cands)), cand = cands > 1 ? wave_uniform((int)(pair - (long long)env * cands)) : -1;
+    double* const o = out + pair * 5;
+    TbxLookahead<TBX_GAME_AMIDAR> look;
+    if (!wave_uniform(look.read(a, env, cand))) {
+        if (lane == 0) tbx_lookahead_refuse(o);
+        return;
+    }
+    look.uniform();
+    AmiRegs s;
+    ami_load(d, env, lane, s);
+    look.run(lane == 0 ? o : nullptr, [&](uint32_t buttons) { ami_step(*d.tab, lane, (uint32_t)wave_uniform((int)buttons), s); },
+             [&] { return wave_uniform(s.f[A_SCORE]); }, [&] { return wave_uniform(s.f[A_LIVES]); });
+}
+
 __global__ __launch_bounds__(TBX_BLOCK) void ami_agent_step_kernel(AmiDev d, AmiDev slot_a, AmiDev slot_b, ActionSource src, uint32_t flags, int first_env, int count)
 {
     const int lane = threadIdx.x & 63;
@@ -2238,6 +2260,16 @@ struct AmiOps : GameOps {
         default: return e->fail(TBX_E_INVALID, "amidar: unknown edit");
         }
         hipLaunchKernelGGL(ami_edit_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, d, op, a, mask_dev);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+
+    int lookahead(tbx_engine* e, const TbxEditArgs& a, bool all, double* out_dev, hipStream_t s) override
+    {
+        const int cands = all ? tbx_legal_count(TBX_GAME_AMIDAR) : 1;
+        tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
+            hipLaunchKernelGGL(ami_lookahead_kernel, grid_for(count), dim3(TBX_BLOCK), 0, s, d, a, cands, p0, count, out_dev);
+        });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

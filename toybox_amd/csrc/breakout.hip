@@ -291,35 +291,10 @@ __global__ __launch_bounds__(TBX_BLOCK) void brk_new_game_kernel(BrkDev d, BrkCf
 
 // ------------------------------------------------------------------ step
 
-// one frame of one env on one wave
+// one frame of one env on one wave: the transition alone, state in registers (the brick table of a CUSTOM engine is read, never written)
 template <bool CUSTOM>
-__device__ __forceinline__ void brk_step_body(const BrkDev& d, const BrkCfg& c, const ActionSource& src, uint32_t flags, int env, int lane)
+__device__ __forceinline__ void brk_wave_frame(const BrkDev& d, const BrkCfg& c, int env, int lane, uint32_t buttons, BrkRegs& s)
 {
-    const size_t N = (size_t)d.n;
-    if (src.exec_flag && lane == 0) src.exec_flag[env] = tbx_agent_env_finished(src, env) ? 0 : 1;
-    if (tbx_agent_env_finished(src, env)) return;     // MaxAndSkipEnv left its loop when this env's game ended
-
-    // ---- action -> buttons
-    uint32_t buttons;
-    if (src.single_env >= 0) {
-        buttons = src.single_buttons;
-    } else {
-        int a;
-        if (src.actions) a = src.actions[env];
-        else {
-            uint64_t h = tbx_splitmix64(src.seed ^ ((src.env_offset + (uint64_t)env) << 32) ^ src.t);
-            a = tbx_legal_action(TBX_GAME_BREAKOUT, (int)(h % 4ull));
-        }
-        buttons = tbx_ale_buttons(a);
-        if (buttons == 0xFFu) {
-            buttons = 0;
-            if (lane == 0) atomicOr(d.err_flag, 1u);
-        }
-    }
-
-    BrkRegs s;
-    brk_load(d, env, lane, s);
-
     // ---- lane-owned brick rectangles
     double kx[MAXK], ky[MAXK], kw[MAXK], kh[MAXK];
     const int nk = (s.n_bricks + 63) >> 6;
@@ -483,6 +458,37 @@ __device__ __forceinline__ void brk_step_body(const BrkDev& d, const BrkCfg& c, 
             s.mybits |= dbits;
         }
     }
+}
+
+// one frame of one env on one wave, from memory to memory
+template <bool CUSTOM>
+__device__ __forceinline__ void brk_step_body(const BrkDev& d, const BrkCfg& c, const ActionSource& src, uint32_t flags, int env, int lane)
+{
+    const size_t N = (size_t)d.n;
+    if (src.exec_flag && lane == 0) src.exec_flag[env] = tbx_agent_env_finished(src, env) ? 0 : 1;
+    if (tbx_agent_env_finished(src, env)) return;     // MaxAndSkipEnv left its loop when this env's game ended
+
+    // ---- action -> buttons
+    uint32_t buttons;
+    if (src.single_env >= 0) {
+        buttons = src.single_buttons;
+    } else {
+        int a;
+        if (src.actions) a = src.actions[env];
+        else {
+            uint64_t h = tbx_splitmix64(src.seed ^ ((src.env_offset + (uint64_t)env) << 32) ^ src.t);
+            a = tbx_legal_action(TBX_GAME_BREAKOUT, (int)(h % 4ull));
+        }
+        buttons = tbx_ale_buttons(a);
+        if (buttons == 0xFFu) {
+            buttons = 0;
+            if (lane == 0) atomicOr(d.err_flag, 1u);
+        }
+    }
+
+    BrkRegs s;
+    brk_load(d, env, lane, s);
+    brk_wave_frame<CUSTOM>(d, c, env, lane, buttons, s);
 
     // ---- outputs, auto-reset
     int32_t rew = s.score - d.prev_score[env];
@@ -926,6 +932,47 @@ __global__ __launch_bounds__(128) void brk_step_tpe_kernel(BrkDev d, const BrkCf
     const int env = blockIdx.x * blockDim.x + threadIdx.x;
     if (env >= d.n) return;
     brk_step_tpe_body<AGENT>(d, *cp, src, flags, recs, recs_a, recs_b, env);   // tables are indexed per thread: read from memory, not from kernel arguments
+}
+
+// TBX_QUERY_LOOKAHEAD / _ALL, canonical wall: one THREAD per (env, candidate), the candidates of an env in neighbouring lanes (their
+// state loads hit the same lines).  One load, `frames` turns of brk_t_step on the registers, no store; lanes whose game has ended
+// leave the loop (masked).  cands = 1: the single form.
+__global__ __launch_bounds__(128) void brk_lookahead_tpe_kernel(BrkDev d, const BrkCfg* __restrict__ cp, TbxEditArgs a, int cands, long long first_pair, int count,
+                                                                double* __restrict__ out)
+{
+    const int rel = blockIdx.x * blockDim.x + threadIdx.x;
+    if (rel >= count) return;
+    const long long pair = first_pair + rel;
+    const int env = (int)(pair / cands), cand = cands > 1 ? (int)(pair - (long long)env * cands) : -1;
+    double* const o = out + pair * 5;
+    TbxLookahead<TBX_GAME_BREAKOUT> look;
+    if (!look.read(a, env, cand)) { tbx_lookahead_refuse(o); return; }
+    const BrkCfg& c = *cp;
+    BrkT s;
+    t_load(d, env, s);
+    look.run(o, [&](uint32_t buttons) { brk_t_step(c, s, buttons); }, [&] { return s.score; }, [&] { return s.lives; });
+}
+
+// ... and the wave form for an engine that has left the canonical wall (and for TBX_OPT_STEP_FORM = 2): one wave per pair
+template <bool CUSTOM>
+__global__ __launch_bounds__(TBX_BLOCK) void brk_lookahead_kernel(BrkDev d, BrkCfg c, TbxEditArgs a, int cands, long long first_pair, int count, double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int rel = wave_uniform(blockIdx.x * TBX_WAVES_PER_BLOCK + (threadIdx.x >> 6));
+    if (rel >= count) return;
+    const long long pair = first_pair + rel;
+    const int env = wave_uniform((int)(pair / cands)), cand = cands > 1 ? wave_uniform((int)(pair - (long long)env * cands)) : -1;
+    double* const o = out + pair * 5;
+    TbxLookahead<TBX_GAME_BREAKOUT> look;
+    if (!wave_uniform(look.read(a, env, cand))) {
+        if (lane == 0) tbx_lookahead_refuse(o);
+        return;
+    }
+    look.uniform();
+    BrkRegs s;
+    brk_load(d, env, lane, s);
+    look.run(lane == 0 ? o : nullptr, [&](uint32_t buttons) { brk_wave_frame<CUSTOM>(d, c, env, lane, (uint32_t)wave_uniform((int)buttons), s); },
+             [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.lives); });
 }
 
 // reset-time wrappers of the agent layer for the envs flagged in r.kind (agent_device.hpp, AgentResetProc)
@@ -2326,6 +2373,17 @@ struct BreakoutOps : GameOps {
         tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_edit_kernel<decltype(cu)::value != 0>, grid, block, 0, s, d, c.n_rows, op, a, mask_dev); });
         TBX_HIP(hipGetLastError());
         recs.valid = false;
+        return TBX_OK;
+    }
+
+    int lookahead(tbx_engine* e, const TbxEditArgs& a, bool all, double* out_dev, hipStream_t s) override
+    {
+        const int cands = all ? tbx_legal_count(TBX_GAME_BREAKOUT) : 1;
+        tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
+            if (!custom && use_tpe) hipLaunchKernelGGL(brk_lookahead_tpe_kernel, dim3((count + 127) / 128), dim3(128), 0, s, d, cfg_dev, a, cands, p0, count, out_dev);
+            else tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_lookahead_kernel<decltype(cu)::value != 0>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, a, cands, p0, count, out_dev); });
+        });
+        TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
 

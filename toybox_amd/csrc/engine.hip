@@ -1583,6 +1583,8 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_AMI_RANDOM_TILE: return game == TBX_GAME_AMIDAR ? 4 : TBX_E_INVALID;
     case TBX_QUERY_AMI_RANDOM_DIR: return game == TBX_GAME_AMIDAR ? 2 : TBX_E_INVALID;
     case TBX_QUERY_CHECKPOINT_VALID: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 1 : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_ALL: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 * tbx_legal_count(game) : TBX_E_INVALID;
     default: return TBX_E_INVALID;
     }
 }
@@ -1608,6 +1610,23 @@ static int edit_args(tbx_engine* e, const double* args, int n_args, int per_env,
 // the queries every game has (the engine's own), else the game's
 static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s)
 {
+    if (query == TBX_QUERY_LOOKAHEAD || query == TBX_QUERY_LOOKAHEAD_ALL) {
+        // shared values are refused here, before anything is launched; per-env rows are met by the kernel (that env's row: zeros)
+        if (a.n < 1 || a.n > 8) return e->fail(TBX_E_INVALID, "lookahead takes {frames[, hold, first, rest, seed_lo, seed_hi, t, env_offset]}");
+        if (!a.per_env) {
+            auto playable = [&](double v) {
+                if (v == -1.0) return true;
+                for (int i = 0; i < tbx_legal_count(e->game); i++)
+                    if (v == (double)tbx_legal_action(e->game, i)) return true;
+                return false;
+            };
+            if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+            if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+            if (a.n > 2 && query == TBX_QUERY_LOOKAHEAD && !playable(a.v[2])) return e->fail(TBX_E_INVALID, "lookahead: first is neither -1 nor a legal action of this game");
+            if (a.n > 3 && !playable(a.v[3])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        }
+        return e->ops->lookahead(e, a, query == TBX_QUERY_LOOKAHEAD_ALL, out_dev, s);
+    }
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     if (a.n < 1 || a.n > 2) return e->fail(TBX_E_INVALID, "TBX_QUERY_CHECKPOINT_VALID takes {slot[, row]}");
     hipLaunchKernelGGL(ckpt_valid_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, ckpt_view(e), a, out_dev, e->n);

@@ -88,7 +88,8 @@ __device__ __forceinline__ void gw_new_scalars(const GwDev& d, GwT& s)
 }
 
 // one frame of one env: at most one cell in the held direction (up, down, left, right in that priority)
-__device__ __forceinline__ void gw_step(const GwDev& d, int env, GwT& s, uint32_t buttons)
+// (board: the env's CELLS bytes, written where a reward is collected; tiles: its [GT][3] table, read only)
+__device__ __forceinline__ void gw_step_on(uint8_t* board, const uint32_t* tiles, GwT& s, uint32_t buttons)
 {
     if (s.over) return;
     int dx = 0, dy = 0;
@@ -99,10 +100,10 @@ __device__ __forceinline__ void gw_step(const GwDev& d, int env, GwT& s, uint32_
     else return;
     const int nx = s.px + dx, ny = s.py + dy;
     if (nx < 0 || ny < 0 || nx >= s.w || ny >= s.h || nx >= GD || ny >= GD) return;
-    uint8_t* cell = d.grid + (size_t)env * CELLS + ny * GD + nx;
+    uint8_t* cell = board + ny * GD + nx;
     const int id = *cell;
     if (id >= s.nt || id >= GT) return;
-    const uint32_t* t = d.tiles + ((size_t)env * GT + id) * 3;
+    const uint32_t* t = tiles + id * 3;
     const uint32_t fl = t[2];
     if (!(fl & 256u)) return;
     const int32_t reward = (int32_t)t[1];
@@ -110,6 +111,10 @@ __device__ __forceinline__ void gw_step(const GwDev& d, int env, GwT& s, uint32_
     s.score += reward;
     if (reward != 0) *cell = (uint8_t)s.becomes;
     if (fl & 1u) s.over = 1;
+}
+__device__ __forceinline__ void gw_step(const GwDev& d, int env, GwT& s, uint32_t buttons)
+{
+    gw_step_on(d.grid + (size_t)env * CELLS, d.tiles + (size_t)env * GT * 3, s, buttons);
 }
 
 __global__ __launch_bounds__(TBX_BLOCK) void gw_new_game_kernel(GwDev d, const uint8_t* mask)
@@ -183,6 +188,35 @@ __global__ __launch_bounds__(128) void gw_step_kernel(GwDev d, ActionSource src,
     const int rel = blockIdx.x * blockDim.x + threadIdx.x;
     if (rel >= count) return;
     gw_step_body(d, src, flags, first_env + rel);
+}
+
+// TBX_QUERY_LOOKAHEAD / _ALL: one wave per (env, candidate).  The scalars fit in registers, the 1 KB board a frame may write does
+// not: the wave copies it into its own LDS slice once and steps on that copy (every lane runs the scalar procedure redundantly,
+// as in the reset kernel below) -- HBM is read once and never written.  cands = 1: the single form.
+__global__ __launch_bounds__(TBX_BLOCK) void gw_lookahead_kernel(GwDev d, TbxEditArgs a, int cands, long long first_pair, int count, double* __restrict__ out)
+{
+    __shared__ uint32_t boards[TBX_WAVES_PER_BLOCK][CELLS / 4];
+    const int lane = threadIdx.x & 63;
+    const int rel = wave_uniform(blockIdx.x * TBX_WAVES_PER_BLOCK + (threadIdx.x >> 6));
+    if (rel >= count) return;
+    const long long pair = first_pair + rel;
+    const int env = wave_uniform((int)(pair / cands)), cand = cands > 1 ? wave_uniform((int)(pair - (long long)env * cands)) : -1;
+    double* const o = out + pair * 5;
+    TbxLookahead<TBX_GAME_GRIDWORLD> look;
+    if (!wave_uniform(look.read(a, env, cand))) {
+        if (lane == 0) tbx_lookahead_refuse(o);
+        return;
+    }
+    look.uniform();
+    uint32_t* const mine = boards[wave_uniform((int)(threadIdx.x >> 6))];
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(d.grid + (size_t)env * CELLS);
+    for (int i = lane; i < CELLS / 4; i += 64) mine[i] = src[i];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       // gw_step_on() reads cells other lanes copied
+    const uint32_t* tiles = d.tiles + (size_t)env * GT * 3;
+    GwT s;
+    gw_load(d, env, s);
+    look.run(lane == 0 ? o : nullptr, [&](uint32_t buttons) { gw_step_on(reinterpret_cast<uint8_t*>(mine), tiles, s, buttons); },
+             [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.over ? 0 : 1); });
 }
 
 // reset-time wrappers of the agent layer (agent_device.hpp, AgentResetProc), thread per flagged env
@@ -721,6 +755,16 @@ struct GridWorldOps : GameOps {
         }
         TBX_HIP(hipMemcpyAsync(e->staging.p, pod_host, sizeof(tbx_gridworld_state_t) * (size_t)count, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(gw_unpack_kernel, dim3(count), dim3(64), 0, s, d, env, (const tbx_gridworld_state_t*)e->staging.p);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+
+    int lookahead(tbx_engine* e, const TbxEditArgs& a, bool all, double* out_dev, hipStream_t s) override
+    {
+        const int cands = all ? tbx_legal_count(TBX_GAME_GRIDWORLD) : 1;
+        tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
+            hipLaunchKernelGGL(gw_lookahead_kernel, grid_for(count), dim3(TBX_BLOCK), 0, s, d, a, cands, p0, count, out_dev);
+        });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

@@ -567,6 +567,89 @@ struct TbxEditArgs {
     }
 };
 
+// TBX_QUERY_LOOKAHEAD / _ALL (include/toybox_amd.h): the schedule of one (env, candidate) pair and the loop every game's
+// lookahead kernel runs around its own step body.  The state lives in the caller's registers between one load and NO store.
+template <int GAME>
+struct TbxLookahead {
+    int frames, hold, first, rest;
+    uint64_t key;                 // seed ^ ((env_offset + env) << 32)
+    uint64_t t;
+    static __device__ __forceinline__ bool playable(int a)
+    {
+        if (a == -1) return true;
+        bool ok = false;
+#pragma unroll
+        for (int i = 0; i < tbx_legal_count(GAME); i++) ok = ok || a == tbx_legal_action(GAME, i);
+        return ok;
+    }
+    // cand >= 0: candidate `cand` of TBX_QUERY_LOOKAHEAD_ALL (its first action is legal[cand]); false: this env's row is refused
+    __device__ __forceinline__ bool read(const TbxEditArgs& a, int env, int cand)
+    {
+        frames = a.geti(env, 0);
+        hold = a.n > 1 ? a.geti(env, 1) : 1;
+        first = cand >= 0 ? tbx_legal_action(GAME, cand) : a.n > 2 ? a.geti(env, 2) : -1;
+        rest = a.n > 3 ? a.geti(env, 3) : -1;
+        const uint64_t seed = (uint64_t)a.getu(env, 4) | ((uint64_t)a.getu(env, 5) << 32);
+        t = a.getu(env, 6);
+        key = seed ^ (((uint64_t)a.getu(env, 7) + (uint64_t)env) << 32);
+        return frames >= 1 && frames <= TBX_LOOKAHEAD_MAX_FRAMES && hold >= 1 && playable(first) && playable(rest);
+    }
+    // wave-per-env callers: every lane read the same row -- say so, and the frame loop's control runs on the scalar unit
+    __device__ __forceinline__ void uniform()
+    {
+        frames = wave_uniform(frames); hold = wave_uniform(hold); first = wave_uniform(first); rest = wave_uniform(rest);
+        key = wave_uniform64(key); t = wave_uniform64(t);
+    }
+    __device__ __forceinline__ uint32_t buttons(int period) const
+    {
+        int a = period == 0 ? first : rest;
+        if (a < 0) a = tbx_legal_action(GAME, (int)(tbx_splitmix64(key ^ (t + (uint64_t)period)) % (uint64_t)tbx_legal_count(GAME)));
+        return tbx_ale_buttons(a);
+    }
+    // step(buttons) runs one frame; score() / lives() read the state.  `out` != nullptr in the lane that writes the five doubles.
+    // Wave-per-env callers hand in wave-uniform score() / lives(), so the exit at game over is wave-uniform; in thread-per-env
+    // callers it masks the finished lanes.
+    template <class Step, class Score, class Lives>
+    __device__ __forceinline__ void run(double* out, Step&& step, Score&& score, Lives&& lives) const
+    {
+        int prev = score();
+        const int lives0 = lives();
+        long long ret = 0;
+        int run_frames = 0, lost_at = -1, period = 0, left = hold, lv = lives0;
+        uint32_t b = buttons(0);
+#pragma clang loop unroll(disable)
+        for (int j = 0; j < frames; j++) {
+            if (left == 0) { left = hold; b = buttons(++period); }
+            left--;
+            step(b);
+            const int sc = score();
+            if (sc > prev) ret += (long long)sc - (long long)prev;
+            prev = sc;
+            lv = lives();
+            if (lost_at < 0 && lv < lives0) lost_at = j;
+            run_frames = j + 1;
+            if (lv <= 0) break;
+        }
+        if (out) { out[0] = (double)ret; out[1] = (double)prev; out[2] = (double)lv; out[3] = (double)run_frames; out[4] = (double)lost_at; }
+    }
+};
+// a refused row: frames run = 0
+__device__ __forceinline__ void tbx_lookahead_refuse(double* out)
+{
+#pragma unroll
+    for (int i = 0; i < 5; i++) out[i] = 0.0;
+}
+// the (env, candidate) pairs of one launch: the grids of a query stay below 2^30 pairs each
+constexpr long long TBX_LOOKAHEAD_PAIRS_PER_LAUNCH = 1ll << 30;
+// f(first_pair, count) per launch
+template <class F>
+void tbx_lookahead_launches(int n, int cands, F&& f)
+{
+    const long long pairs = (long long)n * cands;
+    for (long long p0 = 0; p0 < pairs; p0 += TBX_LOOKAHEAD_PAIRS_PER_LAUNCH)
+        f(p0, (int)(pairs - p0 < TBX_LOOKAHEAD_PAIRS_PER_LAUNCH ? pairs - p0 : TBX_LOOKAHEAD_PAIRS_PER_LAUNCH));
+}
+
 // TBX_EDIT_COPY_ENV (engine.hip, fork_envs): one per-env array of an engine as the copy kernels see it -- `fields` planes of
 // N rows of row_bytes each, [fields][N][row_bytes].  A struct-of-arrays scalar [F][N] is F planes of 4- or 8-byte rows, an
 // env-major table [N][R] one plane of R-byte rows, the plane ring `stack` planes of out_h * out_w bytes.  rng_words > 0: every
@@ -743,6 +826,9 @@ struct GameOps {
     // batched interventions (include/toybox_amd.h, tbx_edit / tbx_reduce): one kernel over the selected envs
     virtual int edit(tbx_engine* e, int /*op*/, const TbxEditArgs&, const uint8_t* /*mask_dev*/, hipStream_t) { return e->fail(TBX_E_INVALID, "this game has no such edit"); }
     virtual int reduce(tbx_engine* e, int /*query*/, const TbxEditArgs&, double* /*out_dev*/, int /*width*/, hipStream_t) { return e->fail(TBX_E_INVALID, "this game has no such query"); }
+    // TBX_QUERY_LOOKAHEAD (cands = 1, the first action from the arguments) / _ALL (cands = the game's legal count): one launch over
+    // the (env, candidate) pairs, out_dev[env][candidate][5]; the arguments' shared values are already checked (engine.hip)
+    virtual int lookahead(tbx_engine* e, const TbxEditArgs&, bool /*all*/, double* /*out_dev*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
     // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The
     // engine adds sim_rng, prev_score and the agent layer and runs the copy.  Listing changes nothing; a copy that WROTE live

@@ -77,6 +77,39 @@ def checkpoint_args(n_envs, slot, rows=None, salt=None):
     return args
 
 
+LOOKAHEAD_FIELDS = ("ret", "score", "lives", "frames_run", "life_lost_at")
+
+
+def lookahead_args(n_envs, frames, hold=1, first=None, rest=None, seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD / _ALL: columns {frames, hold, first, rest, seed_lo, seed_hi, t, env_offset}.
+    Returns (args, per_env): all scalars give one shared row (a list of 8 floats, per_env False); any column one value per env
+    gives float64 [N, 8] (per_env True; scalar columns broadcast, a wrong length raises).  first / rest: an ALE action id or None
+    = -1 = drawn by the synthetic rule; the seed (below 2**64) is split into its 32-bit halves.  Ranges are checked here where
+    every env shares the value (ValueError); per-env rows are checked on the device, where a bad row answers zeros."""
+    cols = [frames, hold, -1 if first is None else first, -1 if rest is None else rest, seed, t, env_offset]
+    per_env = any(np.ndim(c) for c in cols)
+    n = int(n_envs)
+    for name, c in zip(("frames", "hold", "first", "rest", "seed", "t", "env_offset"), cols):
+        if np.ndim(c) > 1 or (np.ndim(c) == 1 and len(c) != n):
+            raise ValueError("lookahead %s is a scalar or one value per env (%d), got shape %r" % (name, n, np.shape(c)))
+    if not np.ndim(frames) and not 1 <= int(frames) <= _abi.LOOKAHEAD_MAX_FRAMES:
+        raise ValueError("lookahead frames must be 1 .. %d, got %r" % (_abi.LOOKAHEAD_MAX_FRAMES, frames))
+    if not np.ndim(hold) and int(hold) < 1:
+        raise ValueError("lookahead hold must be at least 1, got %r" % (hold,))
+    for name, c, top in (("seed", seed, 1 << 64), ("t", t, 1 << 32), ("env_offset", env_offset, 1 << 32)):
+        v = np.asarray(c, dtype=object).reshape(-1)
+        if any(int(x) < 0 or int(x) >= top for x in v):
+            raise ValueError("lookahead %s must be in 0 .. 2**%d - 1" % (name, 64 if name == "seed" else 32))
+    sd = np.asarray(seed, dtype=np.uint64)
+    cols = cols[:4] + [sd & np.uint64(0xFFFFFFFF), sd >> np.uint64(32)] + cols[5:]
+    if not per_env:
+        return [float(c) for c in cols], False
+    args = np.empty((n, len(cols)), np.float64)
+    for k, c in enumerate(cols):
+        args[:, k] = np.asarray(c, np.float64)
+    return args, True
+
+
 class Engine:
     def __init__(self, game, n_envs=1, device=0, config=None, lib=None):
         self._lib = lib if lib is not None else load()
@@ -329,6 +362,25 @@ class Engine:
     def checkpoint_valid(self, slot, rows=None):
         """TBX_QUERY_CHECKPOINT_VALID as int8[N]: 1 cell (slot, rows[i] or i) holds an env, 0 it is empty, -1 no such cell or no store"""
         return self.reduce(_abi.QUERY_CHECKPOINT_VALID, checkpoint_args(self.n_envs, slot, rows))[:, 0].astype(np.int8)
+
+    def lookahead(self, frames, hold=1, first=None, rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD: what the next `frames` raw frames bring every env under the schedule `first` for the first `hold`
+        frames, `rest` after them (ALE action ids; None: drawn by the rule of step_synthetic(seed, t + period, env_offset)) --
+        computed on the device from the state as it stands and thrown away: the engine is untouched.  Every argument a scalar
+        or one per env.  Returns a dict of [N] arrays: ret (float64: the sum of the positive score steps), score, lives, frames_run
+        (shorter than `frames` where the game ended) and life_lost_at (the first frame that cost a life, -1: none), int64."""
+        args, _ = lookahead_args(self.n_envs, frames, hold, first, rest, seed, t, env_offset)
+        return self._lookahead_dict(self.reduce(_abi.QUERY_LOOKAHEAD, args))
+
+    def lookahead_all(self, frames, hold=1, rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_ALL: lookahead() once per legal action a (self.legal_actions order) as the first action; the same dict,
+        arrays shaped [N, n_legal]."""
+        args, _ = lookahead_args(self.n_envs, frames, hold, None, rest, seed, t, env_offset)
+        return self._lookahead_dict(self.reduce(_abi.QUERY_LOOKAHEAD_ALL, args).reshape(self.n_envs, len(self.legal_actions), 5))
+
+    @staticmethod
+    def _lookahead_dict(out):
+        return {k: (out[..., i].copy() if i == 0 else out[..., i].astype(np.int64)) for i, k in enumerate(LOOKAHEAD_FIELDS)}
 
     def reduce(self, query, args=()):
         """tbx_reduce: a per-env feature as float64 [N, width] (integers are exact; missing entries read -1)"""

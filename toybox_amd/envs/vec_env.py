@@ -60,6 +60,21 @@ def _pool_size(obs_pool, reuse_obs_buffer):
     return p
 
 
+def _lookahead(env, frames, hold, first, rest, all_actions, seed, t):
+    """Engine.lookahead / lookahead_all for an adapter: action indices -> ALE ids going in, nothing to map coming out (the
+    candidates of lookahead_all are in action-index order: the action set is the engine's legal set, sorted as it already is)"""
+    def ale(a):
+        if a is None:
+            return None
+        a = np.asarray(a, np.int64)
+        if a.min() < 0 or a.max() >= len(env._action_set):
+            raise AssertionError("action index out of range")
+        return env._lut[a] if a.ndim else int(env._lut[a])
+    if all_actions:
+        return env.engine.lookahead_all(frames, hold=hold, rest=ale(rest), seed=seed, t=t)
+    return env.engine.lookahead(frames, hold=hold, first=ale(first), rest=ale(rest), seed=seed, t=t)
+
+
 def _fork_map(n, src, envs):
     """(src int[N], selected bool[N]) of a fork: src an int (one source fanned out) or one index per env; envs None (every
     env), a boolean mask or indices.  Unselected envs name themselves."""
@@ -224,6 +239,17 @@ class ToyboxVecEnv:
         self.engine.checkpoint_restore(slot, rows=rows, mask=_fork_map(self.num_envs, 0, envs)[1], salt=salt)
         return self._frames()
 
+    def lookahead(self, steps, first=None, rest=None, all_actions=False, seed=0, t=0):
+        """What the next `steps` steps bring every env, without taking them (Engine.lookahead): the env plays action index `first`
+        in the first step and `rest` in the others (None: drawn like Engine.step_synthetic(seed, t + step)); all_actions=True
+        answers for every action index as the first one, arrays [num_envs, n_actions].  Returns a dict of ret (the reward summed),
+        score, lives, frames_run and life_lost_at.  The env, its RNG and its next observation are untouched.  These are raw game
+        frames from the state as it stands: an episode's end is the game's end and nothing is reset.  Between step_async and
+        step_wait the step ends first (its results are dropped)."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _lookahead(self, int(steps), 1, first, rest, all_actions, seed, t)
+
     def get_images(self):
         return self.engine.render(3)
 
@@ -335,6 +361,7 @@ class ToyboxPreprocVecEnv:
         self._fill_repeat = frame_stack == "env"
         self.scale = bool(scale)
         self.stack, self.size = int(stack), int(size)
+        self._skip = int(skip)
         self.observation_space = Box(0, 1.0, (size, size, stack), "float32") if self.scale else Box(0, 255, (size, size, stack), "uint8")
         if seed is not None:
             self.engine.seed_array([hash_seed(int(seed) + i + 1) % 2 ** 31 for i in range(self.num_envs)])
@@ -525,6 +552,18 @@ class ToyboxPreprocVecEnv:
             out[idx, :, :, c] = src[idx]
         self._stacked = out
         return self._obs(out)
+
+    def lookahead(self, steps, first=None, rest=None, all_actions=False, seed=0, t=0):
+        """What the next `steps` agent steps (steps x skip raw frames, every action held for skip frames) bring every env, without
+        taking them (Engine.lookahead): action index `first` in the first step, `rest` in the others (None: drawn like
+        Engine.step_synthetic(seed, t + step)); all_actions=True answers for every action index as the first one, arrays
+        [num_envs, n_actions].  Returns a dict of ret, score, lives, frames_run and life_lost_at, counted in RAW frames.
+        The wrappers are NOT simulated: no no-op or fire reset, no episodic life (the run ends when the GAME ends, not at a lost
+        life -- life_lost_at tells where that was), no reward clipping (ret sums raw score steps), no frame maximum.  The env, its
+        wrapper state and its next observation are untouched.  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _lookahead(self, int(steps) * self._skip, self._skip, first, rest, all_actions, seed, t)
 
     def close(self):
         if not self.closed:

@@ -202,6 +202,34 @@ class BatchIntervention:
         else:
             self._edit(_abi.EDIT_COPY_ENV, src, salt, envs=envs)
 
+    # ---- every game: look before you branch.  What the next frames bring the envs of the range under an action schedule, computed
+    # on the device and thrown away (Engine.lookahead): pending record edits are written first, nothing else changes.
+    def _lookahead(self, all_actions, frames, hold, first, rest, seed, t, env_offset):
+        self._flush()
+        sl = slice(self.first, self.first + self.count)
+
+        def col(c, fill):
+            if not np.ndim(c):
+                return c
+            full = np.full(self.engine.n_envs, fill, np.asarray(c).dtype)
+            full[sl] = c
+            return full
+        cols = dict(frames=col(frames, 1), hold=col(hold, 1), rest=None if rest is None else col(rest, -1), seed=col(seed, 0), t=col(t, 0),
+                    env_offset=col(env_offset, 0))
+        if all_actions:
+            out = self.engine.lookahead_all(**cols)
+        else:
+            out = self.engine.lookahead(first=None if first is None else col(first, -1), **cols)
+        return {k: v[sl] for k, v in out.items()}
+
+    def lookahead(self, frames, hold=1, first=None, rest=None, seed=0, t=0, env_offset=0):
+        """Engine.lookahead over the range: a dict of ret, score, lives, frames_run, life_lost_at, each [count]"""
+        return self._lookahead(False, frames, hold, first, rest, seed, t, env_offset)
+
+    def lookahead_all(self, frames, hold=1, rest=None, seed=0, t=0, env_offset=0):
+        """Engine.lookahead_all over the range: the same dict, each [count, n_legal]"""
+        return self._lookahead(True, frames, hold, None, rest, seed, t, env_offset)
+
     # ================================================================== BreakoutIntervention (interventions/breakout.py)
     def num_bricks_remaining(self):
         """:309-310 -> int[N]"""
