@@ -9,7 +9,6 @@ the device engine must equal from the restore on; from there every engine plays 
 import numpy as np
 
 from fork_replay import sim_rngs, states_bytes
-from toybox_amd import _abi
 
 
 def pick_rows(sel, a, b):
@@ -58,23 +57,9 @@ class Twin:
         return self.pick(case.observation(self.a), case.observation(self.b))
 
     def agent_rows(self, case, actions):
-        """one agent step of both engines per action row; -> rows as Agent.run returns them"""
-        ra, rb = agent_rows(case, self.a, actions), agent_rows(case, self.b, actions)
+        """one agent step of both engines per action row; -> rows as Agent.rows returns them"""
+        ra, rb = case.rows(self.a, actions), case.rows(self.b, actions)
         return [tuple(self.pick(x, y) for x, y in zip(p, q)) for p, q in zip(ra, rb)]
-
-
-def agent_rows(case, e, actions):
-    """Agent.run with the action rows given: -> list of (obs, reward, done, ep_done, ep_return, ep_length[, plane]) per step"""
-    out = []
-    for a in actions:
-        _, reward, done = e.agent_step(a)
-        ended, ret, length = e.agent_episodes()
-        row = (case.observation(e), reward.copy(), done.copy(), ended.copy(), np.where(ended, ret, 0), np.where(ended, length, 0))
-        if case.new_plane == 1:
-            from support import read_buffer
-            row += (read_buffer(e, _abi.BUF_AGENT_PLANE, (case.n, case.size, case.size)),)
-        out.append(row)
-    return out
 
 
 def restore_map(n, src, sel):
@@ -97,19 +82,3 @@ def replay_to(case, lib, eff, t_s, run=None):
     if hasattr(case, "own_slots"):
         case.own_slots(e)
     return e
-
-
-def assert_rows(got, want, what):
-    assert len(got) == len(want)
-    for t, (g, w) in enumerate(zip(got, want)):
-        for k, (x, y) in enumerate(zip(g, w)):
-            if not np.array_equal(x, y):
-                bad = np.flatnonzero((np.asarray(x) != np.asarray(y)).reshape(len(x), -1).any(axis=1))
-                raise AssertionError("%s: output %d differs at step %d in %d envs, first %s" % (what, k, t, len(bad), bad[:8]))
-
-
-def assert_snapshot(got, want, what):
-    for name, x, y in zip(("state records", "simulator RNG"), got, want):
-        if not np.array_equal(x, y):
-            bad = np.flatnonzero((x != y).reshape(len(x), -1).any(axis=1))
-            raise AssertionError("%s: %s differ in %d envs, first %s" % (what, name, len(bad), bad[:8]))

@@ -120,10 +120,14 @@ class Agent:
         return read_buffer(e, _abi.BUF_AGENT_OBS, (n, s, s, 4))
 
     def run(self, e, t0, t1, src=None):
-        """agent steps t0 .. t1-1; -> list of (obs, reward, done, ep_done, ep_return, ep_length[, plane]) per step"""
+        """agent steps t0 .. t1-1; -> rows as rows() returns them"""
+        return self.rows(e, (self.actions(t, src) for t in range(t0, t1)))
+
+    def rows(self, e, actions):
+        """one agent step per action row given; -> list of (obs, reward, done, ep_done, ep_return, ep_length[, plane]) per step"""
         out = []
-        for t in range(t0, t1):
-            _, reward, done = e.agent_step(self.actions(t, src))
+        for a in actions:
+            _, reward, done = e.agent_step(a)
             ended, ret, length = e.agent_episodes()
             row = (self.observation(e), reward.copy(), done.copy(), ended.copy(), np.where(ended, ret, 0), np.where(ended, length, 0))
             if self.new_plane == 1:

@@ -6,9 +6,9 @@ fails on a library without the ops ("unknown edit", "unknown query") or a packag
 import numpy as np
 import pytest
 
-from checkpoint_replay import (Solo, Twin, agent_rows, assert_rows, assert_snapshot, mixed_actions, pick_rows, replay_to,
-                               restore_map)
+from checkpoint_replay import Solo, Twin, mixed_actions, pick_rows, replay_to, restore_map
 from fork_replay import Agent, Raw, fork_maps, sim_rngs, snapshot, states_bytes
+from fork_replay import assert_rows_equal as assert_rows, assert_snapshot_equal as assert_snapshot
 from support import read_buffer, splitmix64
 from test_gpu_fork import _pick_moment
 from toybox_amd import Engine, ToyboxAmdError, _abi
@@ -211,7 +211,7 @@ def _agent_case(game, hip_lib, oracle_lib, n=24, t_s=40, t_r=63, T2=60, src=None
     assert_snapshot(snapshot(g), x.snapshot(), what + " right after the restore")
     acts = [mixed_actions(case, sel, eff, t_s, t_r, k) for k in range(T2)]
     want = x.agent_rows(case, acts)
-    assert_rows(agent_rows(case, g, acts), want, what)
+    assert_rows(case.rows(g, acts), want, what)
     assert_snapshot(snapshot(g), x.snapshot(), what + " at the end")
     if need_done:
         ended, done = np.stack([r[3] for r in want]), np.stack([r[2] for r in want])

@@ -502,10 +502,10 @@ void tbx_agent_free(tbx_engine* e)
     e->agent = nullptr;
 }
 
-// TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: the arrays the table marks as part of an env (those that exist: TbxForkPlan::rows
+// TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: the arrays the table marks as part of an env (those that exist: TbxEnvPlan::rows
 // skips a null base).  The outputs of the last step, the no-op overrides and the per-step scratch are not.  The plane ring says
-// which of its planes is the oldest right now (TbxForkSeg::rot).
-void tbx_agent_copy_envs(tbx_engine* e, TbxForkPlan& plan)
+// which of its planes is the oldest right now (TbxEnvSeg::rot).
+void tbx_agent_copy_envs(tbx_engine* e, TbxEnvPlan& plan)
 {
     if (!e->agent) return;
     AgentState& a = *e->agent;

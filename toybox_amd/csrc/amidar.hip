@@ -2247,9 +2247,9 @@ struct AmiOps : GameOps {
 
     // TBX_EDIT_COPY_ENV: scalars and RNG (struct of arrays), the env-major tiles / boxes / movers and the movers' struct-of-arrays
     // mirror, of the live state and of the agent layer's two slots
-    void list_envs(tbx_engine*, TbxForkPlan& plan) override
+    void list_envs(tbx_engine*, TbxEnvPlan& plan) override
     {
-        for (AmiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_fork_arrays(plan, *x, x == &d);   // (the kept copies too: mode 2 travels with the env)
+        for (AmiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_list_arrays(plan, *x, x == &d);   // (the kept copies too: mode 2 travels with the env)
     }
 
     int edit(tbx_engine* e, int op, const TbxEditArgs& a, const uint8_t* mask_dev, hipStream_t s) override

@@ -2389,10 +2389,10 @@ struct BreakoutOps : GameOps {
 
     // TBX_EDIT_COPY_ENV: the struct-of-arrays state, the per-env brick table of the custom mode and the two record slots of the
     // agent layer (a copy of a canonical env is canonical: `custom` stays as it is)
-    void list_envs(tbx_engine*, TbxForkPlan& plan) override
+    void list_envs(tbx_engine*, TbxEnvPlan& plan) override
     {
-        tbx_fork_arrays(plan, d, true);
-        tbx_fork_arrays(plan, slots, false);           // (the kept copies too: an env copied while its observation is the kept buffer's)
+        tbx_list_arrays(plan, d, true);
+        tbx_list_arrays(plan, slots, false);           // (the kept copies too: an env copied while its observation is the kept buffer's)
     }
     void envs_rewritten(tbx_engine*) override { recs.valid = false; }
 

@@ -2,6 +2,7 @@
 // No CPU fallback: every entry point that computes needs a visible gfx950 device.
 
 #include "engine_host.hpp"
+#include "envcopy.hpp"
 #include "pipeline.hpp"
 #include <emmintrin.h>   // host side only: tbx_host_stack_push
 
@@ -308,7 +309,7 @@ int tbx_destroy(tbx_engine* e)
     }
     pipe_free(e);
     hipFree(e->actions);
-    e->edit_args.release(); e->reduce_out.release(); e->fork_scratch.release(); e->ckpt_store.release(); e->frame_own.release(); e->staging.release();
+    e->edit_args.release(); e->reduce_out.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
     hipFree(e->mask); hipFree(e->err_flag); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
     if (e->io_host) hipHostFree(e->io_host);
     if (e->scal_host) hipHostFree(e->scal_host);
@@ -779,445 +780,6 @@ hipError_t tbx_serve_stop(tbx_engine* e)
     return r;
 }
 
-// ---- TBX_EDIT_COPY_ENV (include/toybox_amd.h): the selected envs become copies of other envs of the batch
-//
-// The per-env state is a list of arrays [fields][N][row_bytes] (TbxForkSeg: the game's, GameOps::list_envs; the engine's sim_rng
-// and prev_score; the agent layer's, tbx_agent_copy_envs).  Two kernels move them: scalars (rows of 1 .. 8 bytes, one THREAD per
-// destination env walks every plane of every such array -- the stores of a wave are coalesced) and rows (anything wider, one
-// WAVE per destination row, 16 bytes per lane: the 28 KB observation stack is where the bytes are).
-// Simultaneous assignment: PHASE 0 copies array -> array in one pass and is only used when the host has seen that no selected
-// destination is another selected row's source; otherwise PHASE 1 gathers array[src_i] -> scratch[i] for every selected i and,
-// behind it in stream order, PHASE 2 writes scratch[i] -> array[i].
-constexpr int FORK_SEGS = 16;                 // arrays per launch
-constexpr unsigned FORK_MAX_BLOCKS = 2048;    // rows kernel: the grid is capped and strides over the rest
-struct ForkBatch {
-    TbxForkSeg seg[FORK_SEGS];
-    int n_segs;
-};
-
-// the source of destination env i, or -1: not selected, a source outside the batch (the device form leaves such an env
-// untouched), or -- for the copy passes -- the env itself
-__device__ __forceinline__ int fork_source(const TbxEditArgs& a, const uint8_t* mask, int i, int n, bool self_counts)
-{
-    if (mask && !mask[i]) return -1;
-    const int src = a.geti(i, 0);
-    if (src < 0 || src >= n || (!self_counts && src == i)) return -1;
-    return src;
-}
-
-// one row of rb bytes by one wave: 16 bytes per lane where row length and both arrays allow it (align 16), else 4, else 1
-__device__ __forceinline__ uint32_t row_align(uint32_t rb, const uint8_t* rd0, const uint8_t* wr0)
-{
-    const uint32_t bits = rb | (uint32_t)(uintptr_t)rd0 | (uint32_t)(uintptr_t)wr0;
-    return (bits & 15u) == 0 ? 16u : (bits & 3u) == 0 ? 4u : 1u;
-}
-__device__ __forceinline__ void copy_row(const uint8_t* rd, uint8_t* wr, uint32_t rb, int lane, uint32_t align)
-{
-    if (align == 16u) {
-        uint32_t o = (uint32_t)lane * 16u;
-        for (; o + 3072u < rb; o += 4096u) {     // four 16-byte loads in flight per lane, then their stores
-            const uint4 v0 = *reinterpret_cast<const uint4*>(rd + o), v1 = *reinterpret_cast<const uint4*>(rd + o + 1024u);
-            const uint4 v2 = *reinterpret_cast<const uint4*>(rd + o + 2048u), v3 = *reinterpret_cast<const uint4*>(rd + o + 3072u);
-            *reinterpret_cast<uint4*>(wr + o) = v0; *reinterpret_cast<uint4*>(wr + o + 1024u) = v1;
-            *reinterpret_cast<uint4*>(wr + o + 2048u) = v2; *reinterpret_cast<uint4*>(wr + o + 3072u) = v3;
-        }
-        for (; o < rb; o += 1024u) *reinterpret_cast<uint4*>(wr + o) = *reinterpret_cast<const uint4*>(rd + o);
-    } else if (align == 4u) {
-        for (uint32_t o = (uint32_t)lane * 4u; o < rb; o += 256u) *reinterpret_cast<uint32_t*>(wr + o) = *reinterpret_cast<const uint32_t*>(rd + o);
-    } else {
-        for (uint32_t o = (uint32_t)lane; o < rb; o += 64u) wr[o] = rd[o];
-    }
-}
-// ... and one scalar row (1 .. 8 bytes) by one thread: element `from` of plane rd -> element `to` of plane wr
-__device__ __forceinline__ void copy_scalar(const uint8_t* rd, uint8_t* wr, uint32_t rb, size_t from, size_t to)
-{
-    switch (rb) {
-    case 8: reinterpret_cast<uint64_t*>(wr)[to] = reinterpret_cast<const uint64_t*>(rd)[from]; break;
-    case 4: reinterpret_cast<uint32_t*>(wr)[to] = reinterpret_cast<const uint32_t*>(rd)[from]; break;
-    case 2: reinterpret_cast<uint16_t*>(wr)[to] = reinterpret_cast<const uint16_t*>(rd)[from]; break;
-    default:
-        for (uint32_t o = 0; o < rb; o++) wr[to * rb + o] = rd[from * rb + o];
-    }
-}
-// the `salt` of a fork or a restore: every RNG word of env i in the listed arrays becomes splitmix64(word ^ salt)
-__device__ __forceinline__ void salt_env(const ForkBatch& b, int i, int n, uint64_t salt)
-{
-    for (int k = 0; k < b.n_segs; k++) {
-        const TbxForkSeg& g = b.seg[k];
-        for (uint32_t f = 0; f < g.fields; f++) {
-            uint64_t* w = reinterpret_cast<uint64_t*>(g.base + ((size_t)f * n + (size_t)i) * g.row_bytes + g.rng_off);
-            for (uint32_t j = 0; j < g.rng_words; j++) w[j] = tbx_splitmix64(w[j] ^ salt);
-        }
-    }
-}
-
-template <int PHASE>
-__global__ __launch_bounds__(256) void fork_scalars_kernel(ForkBatch b, uint8_t* scratch, TbxEditArgs a, const uint8_t* __restrict__ mask, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int src = fork_source(a, mask, i, n, false);
-    if (src < 0) return;
-    const size_t from = PHASE == 2 ? (size_t)i : (size_t)src, to = (size_t)i;
-    for (int k = 0; k < b.n_segs; k++) {
-        const TbxForkSeg& g = b.seg[k];
-        if (g.row_bytes > 8) continue;
-        const uint8_t* rd = PHASE == 2 ? scratch + g.scratch_off : g.base;
-        uint8_t* wr = PHASE == 1 ? scratch + g.scratch_off : g.base;
-        const size_t plane = (size_t)n * g.row_bytes;
-        for (uint32_t f = 0; f < g.fields; f++, rd += plane, wr += plane) copy_scalar(rd, wr, g.row_bytes, from, to);
-    }
-}
-
-template <int PHASE>
-__global__ __launch_bounds__(TBX_BLOCK) void fork_rows_kernel(ForkBatch b, uint8_t* scratch, TbxEditArgs a, const uint8_t* __restrict__ mask, int n)
-{
-    const int lane = threadIdx.x & 63;
-    const int wave0 = wave_uniform((int)(blockIdx.x * TBX_WAVES_PER_BLOCK + (threadIdx.x >> 6)));
-    const int n_waves = (int)(gridDim.x * TBX_WAVES_PER_BLOCK);
-    for (int i = wave0; i < n; i += n_waves) {               // destination envs, several in flight per block
-        const int src = fork_source(a, mask, i, n, false);
-        if (src < 0) continue;
-        const size_t from = PHASE == 2 ? (size_t)i : (size_t)src;
-        for (int k = 0; k < b.n_segs; k++) {
-            const TbxForkSeg& g = b.seg[k];
-            if (g.row_bytes <= 8) continue;
-            const uint32_t rb = g.row_bytes;
-            const uint8_t* rd0 = PHASE == 2 ? scratch + g.scratch_off : g.base;
-            uint8_t* wr0 = PHASE == 1 ? scratch + g.scratch_off : g.base;
-            const size_t plane = (size_t)n * rb;
-            const uint32_t align = row_align(rb, rd0, wr0);
-            for (uint32_t f = 0; f < g.fields; f++) copy_row(rd0 + f * plane + from * rb, wr0 + f * plane + (size_t)i * rb, rb, lane, align);
-        }
-    }
-}
-
-// the fork's `salt`: every RNG word of a selected destination becomes splitmix64(word ^ salt) (behind the copy, in stream order)
-__global__ __launch_bounds__(256) void fork_salt_kernel(ForkBatch b, TbxEditArgs a, const uint8_t* __restrict__ mask, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || fork_source(a, mask, i, n, true) < 0) return;
-    const uint64_t salt = a.getu(i, 1);
-    if (salt) salt_env(b, i, n, salt);
-}
-
-// Every per-env array of the engine as it is now, each with its offset in a packed copy of them all (the fork's scratch, one
-// plane of the checkpoint store: 256-byte-aligned, so a row copy that can take 16 bytes per lane still can); -> that copy's size.
-// Listing changes nothing in the engine.
-static size_t env_plan(tbx_engine* e, TbxForkPlan& plan)
-{
-    e->ops->list_envs(e, plan);
-    plan.soa(e->sim_rng, 2, 1);
-    plan.soa(e->prev_score, 1);
-    tbx_agent_copy_envs(e, plan);
-    size_t bytes = 0;
-    for (TbxForkSeg& g : plan.segs) {
-        g.scratch_off = bytes;
-        bytes += ((size_t)g.fields * (size_t)e->n * g.row_bytes + 255) & ~(size_t)255;
-    }
-    return bytes;
-}
-
-// direct: one pass (the caller has checked that no selected destination is a selected row's source)
-static int fork_envs(tbx_engine* e, const TbxEditArgs& a, const uint8_t* mask_dev, bool direct, hipStream_t s)
-{
-    if (a.n < 1) return e->fail(TBX_E_INVALID, "TBX_EDIT_COPY_ENV takes {src[, salt]}");
-    TbxForkPlan plan;
-    const size_t scratch = env_plan(e, plan);
-    e->ops->envs_rewritten(e);
-    const size_t N = (size_t)e->n;
-    if (!direct) EHIP(e->fork_scratch.reserve(scratch));       // (freeing the old one waits for whatever still reads it)
-    const dim3 sgrid((unsigned)((N + 255) / 256)), sblock(256);
-    const dim3 rgrid(std::min((unsigned)((N + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK), FORK_MAX_BLOCKS)), rblock(TBX_BLOCK);
-    std::vector<ForkBatch> batches;
-    for (size_t k = 0; k < plan.segs.size(); k++) {
-        if (k % FORK_SEGS == 0) { batches.emplace_back(); batches.back().n_segs = 0; }
-        batches.back().seg[batches.back().n_segs++] = plan.segs[k];
-    }
-    auto pass = [&](int phase) {
-        for (const ForkBatch& b : batches) {
-            bool sc = false, rw = false;
-            for (int k = 0; k < b.n_segs; k++) (b.seg[k].row_bytes <= 8 ? sc : rw) = true;
-            if (sc) {
-                if (phase == 0) hipLaunchKernelGGL(fork_scalars_kernel<0>, sgrid, sblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
-                else if (phase == 1) hipLaunchKernelGGL(fork_scalars_kernel<1>, sgrid, sblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
-                else hipLaunchKernelGGL(fork_scalars_kernel<2>, sgrid, sblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
-            }
-            if (rw) {
-                if (phase == 0) hipLaunchKernelGGL(fork_rows_kernel<0>, rgrid, rblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
-                else if (phase == 1) hipLaunchKernelGGL(fork_rows_kernel<1>, rgrid, rblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
-                else hipLaunchKernelGGL(fork_rows_kernel<2>, rgrid, rblock, 0, s, b, e->fork_scratch.p, a, mask_dev, e->n);
-            }
-        }
-    };
-    if (direct) pass(0);
-    else { pass(1); pass(2); }
-    if (a.n >= 2) {
-        ForkBatch rng;
-        rng.n_segs = 0;
-        for (const TbxForkSeg& g : plan.segs)
-            if (g.rng_words && rng.n_segs < FORK_SEGS) rng.seg[rng.n_segs++] = g;
-        hipLaunchKernelGGL(fork_salt_kernel, sgrid, sblock, 0, s, rng, a, mask_dev, e->n);
-    }
-    EHIP(hipGetLastError());
-    return TBX_OK;
-}
-
-// the host form sees the rows: a selected row with a source outside the batch is an error (nothing has been changed), and the
-// one-pass copy is safe when no selected destination (other than a copy of itself) is the source of another selected row
-static int fork_check_host(tbx_engine* e, const double* args, int n_args, int per_env, const uint8_t* mask_host, bool& direct)
-{
-    if (n_args < 1 || !args) return e->fail(TBX_E_INVALID, "TBX_EDIT_COPY_ENV takes {src[, salt]}");
-    const int n = e->n;
-    auto source = [&](int i) {
-        double x = args[per_env ? (size_t)i * n_args : 0];
-        if (!(x > -2.0e9)) x = -2.0e9;                         // (TbxEditArgs::geti)
-        if (x > 2.0e9) x = 2.0e9;
-        return (int)x;
-    };
-    std::vector<uint8_t> is_source((size_t)n, 0);
-    for (int i = 0; i < n; i++) {
-        if (mask_host && !mask_host[i]) continue;
-        const int src = source(i);
-        if (src < 0 || src >= n)
-            return e->fail(TBX_E_INVALID, "TBX_EDIT_COPY_ENV: env " + std::to_string(i) + " names source " + std::to_string(src) + ", outside 0 .. " + std::to_string(n - 1));
-        if (src != i) is_source[(size_t)src] = 1;
-    }
-    direct = true;
-    for (int i = 0; i < n && direct; i++)
-        if ((!mask_host || mask_host[i]) && source(i) != i && is_source[(size_t)i]) direct = false;
-    return TBX_OK;
-}
-
-// ---- TBX_EDIT_CHECKPOINT_SLOTS / _SAVE / _RESTORE, TBX_QUERY_CHECKPOINT_VALID (include/toybox_amd.h): env states set aside
-//
-// The store is `slots` planes; a plane holds every array of env_plan() for N envs at the plan's offsets, [fields][N][row_bytes]
-// each, so cell (slot, row) is row `row` of every array of plane `slot`.  Behind the planes: valid[slots][N], then the two words
-// the host forms' check writes.  Live arrays and store never alias, so a save and a restore are ONE pass each, by the fork's two
-// kernel shapes (a thread per env for rows of up to 8 bytes, a wave per env row for wider ones).  The plane ring is kept in
-// LOGICAL order (oldest plane first): its head is batch-wide and has usually moved between a save and the restore.
-struct CkptStore {
-    uint8_t* planes;
-    uint8_t* valid;               // [slots][N]
-    uint64_t slot_bytes;
-    int slots;
-};
-constexpr int CKPT_BAD_SLOT = 1, CKPT_BAD_ROW = 2, CKPT_EMPTY = 3;
-
-// the cell of selected env i: -> slot (row in `row`), -1 not selected, or -(1 + CKPT_*) for a row the op cannot carry out
-template <bool SAVE>
-__device__ __forceinline__ int ckpt_cell(const CkptStore& st, const TbxEditArgs& a, const uint8_t* mask, int i, int n, int& row)
-{
-    if (mask && !mask[i]) return -1;
-    const int slot = a.geti(i, 0);
-    if (slot < 0 || slot >= st.slots) return -(1 + CKPT_BAD_SLOT);
-    row = i;
-    if (!SAVE) {
-        const int r = a.n >= 2 ? a.geti(i, 1) : -1;
-        if (r != -1) row = r;
-        if (row < 0 || row >= n) return -(1 + CKPT_BAD_ROW);
-        if (!st.valid[(size_t)slot * n + row]) return -(1 + CKPT_EMPTY);
-    }
-    return slot;
-}
-
-// the host forms' check: word 0 = min over the rows that cannot be carried out of (env << 2 | CKPT_*), word 1 = their number - 1
-// (both start as all ones)
-template <bool SAVE>
-__global__ __launch_bounds__(256) void ckpt_check_kernel(CkptStore st, uint32_t* words, TbxEditArgs a, const uint8_t* __restrict__ mask, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int row;
-    const int c = ckpt_cell<SAVE>(st, a, mask, i, n, row);
-    if (c >= -1) return;
-    atomicMin(&words[0], ((uint32_t)i << 2) | (uint32_t)(-c - 1));
-    atomicAdd(&words[1], 1u);
-}
-
-// mark: this launch sets the saved cells' valid bytes (one launch of a save does)
-template <bool SAVE>
-__global__ __launch_bounds__(256) void ckpt_scalars_kernel(ForkBatch b, CkptStore st, TbxEditArgs a, const uint8_t* __restrict__ mask, int n, int mark)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int row;
-    const int slot = ckpt_cell<SAVE>(st, a, mask, i, n, row);
-    if (slot < 0) return;
-    uint8_t* cell = st.planes + (size_t)slot * st.slot_bytes;
-    for (int k = 0; k < b.n_segs; k++) {
-        const TbxForkSeg& g = b.seg[k];
-        if (g.row_bytes > 8) continue;
-        const size_t plane = (size_t)n * g.row_bytes;
-        for (uint32_t c = 0; c < g.fields; c++) {              // c: the plane's place in logical order
-            uint32_t f = g.rot + c;
-            if (f >= g.fields) f -= g.fields;
-            uint8_t* live = g.base + f * plane;
-            uint8_t* kept = cell + g.scratch_off + c * plane;
-            if (SAVE) copy_scalar(live, kept, g.row_bytes, (size_t)i, (size_t)row);
-            else copy_scalar(kept, live, g.row_bytes, (size_t)row, (size_t)i);
-        }
-    }
-    if (SAVE && mark) st.valid[(size_t)slot * n + row] = 1;
-}
-
-template <bool SAVE>
-__global__ __launch_bounds__(TBX_BLOCK) void ckpt_rows_kernel(ForkBatch b, CkptStore st, TbxEditArgs a, const uint8_t* __restrict__ mask, int n)
-{
-    const int lane = threadIdx.x & 63;
-    const int wave0 = wave_uniform((int)(blockIdx.x * TBX_WAVES_PER_BLOCK + (threadIdx.x >> 6)));
-    const int n_waves = (int)(gridDim.x * TBX_WAVES_PER_BLOCK);
-    for (int i = wave0; i < n; i += n_waves) {               // envs, several in flight per block
-        int row;
-        const int slot = ckpt_cell<SAVE>(st, a, mask, i, n, row);
-        if (slot < 0) continue;
-        uint8_t* cell = st.planes + (size_t)slot * st.slot_bytes;
-        for (int k = 0; k < b.n_segs; k++) {
-            const TbxForkSeg& g = b.seg[k];
-            if (g.row_bytes <= 8) continue;
-            const uint32_t rb = g.row_bytes;
-            const size_t plane = (size_t)n * rb;
-            uint8_t* kept0 = cell + g.scratch_off;
-            const uint32_t align = row_align(rb, g.base, kept0);
-            for (uint32_t c = 0; c < g.fields; c++) {
-                uint32_t f = g.rot + c;
-                if (f >= g.fields) f -= g.fields;
-                uint8_t* live = g.base + f * plane + (size_t)i * rb;
-                uint8_t* kept = kept0 + c * plane + (size_t)row * rb;
-                if (SAVE) copy_row(live, kept, rb, lane, align);
-                else copy_row(kept, live, rb, lane, align);
-            }
-        }
-    }
-}
-
-// the restore's `salt` (args {slot, row, salt}), behind the copy in stream order: the envs that were restored
-__global__ __launch_bounds__(256) void ckpt_salt_kernel(ForkBatch b, CkptStore st, TbxEditArgs a, const uint8_t* __restrict__ mask, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int row;
-    if (ckpt_cell<false>(st, a, mask, i, n, row) < 0) return;
-    const uint64_t salt = a.getu(i, 2);
-    if (salt) salt_env(b, i, n, salt);
-}
-
-__global__ __launch_bounds__(256) void ckpt_valid_kernel(CkptStore st, TbxEditArgs a, double* __restrict__ out, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int slot = a.n >= 1 ? a.geti(i, 0) : -1;
-    int row = a.n >= 2 ? a.geti(i, 1) : -1;
-    if (row == -1) row = i;
-    out[i] = (!st.valid || slot < 0 || slot >= st.slots || row < 0 || row >= n) ? -1.0 : st.valid[(size_t)slot * n + row] ? 1.0 : 0.0;
-}
-
-static CkptStore ckpt_view(const tbx_engine* e)
-{
-    CkptStore st;
-    st.planes = e->ckpt_store.p;
-    st.slot_bytes = e->ckpt_slot_bytes;
-    st.slots = e->ckpt_slots;
-    st.valid = e->ckpt_slots ? e->ckpt_store.p + (size_t)e->ckpt_slots * e->ckpt_slot_bytes : nullptr;
-    return st;
-}
-
-static std::vector<std::pair<uint32_t, uint32_t>> plan_signature(const TbxForkPlan& plan)
-{
-    std::vector<std::pair<uint32_t, uint32_t>> sig;
-    for (const TbxForkSeg& g : plan.segs) sig.emplace_back(g.fields, g.row_bytes);
-    return sig;
-}
-
-// TBX_EDIT_CHECKPOINT_SLOTS: the stream has been drained by the caller
-static int checkpoint_slots(tbx_engine* e, const double* args, int n_args, int per_env, const uint8_t* mask_host)
-{
-    if (n_args != 1 || !args || per_env || mask_host || !(args[0] >= 0.0 && args[0] <= 1048576.0) || args[0] != (double)(int)args[0])
-        return e->fail(TBX_E_INVALID, "TBX_EDIT_CHECKPOINT_SLOTS takes {slots} (an integer >= 0), the same for every env and without a mask");
-    e->ckpt_store.release();
-    e->ckpt_slots = 0;
-    e->ckpt_slot_bytes = 0;
-    e->ckpt_sig.clear();
-    const int slots = (int)args[0];
-    if (!slots) return TBX_OK;
-    TbxForkPlan plan;
-    const size_t slot_bytes = env_plan(e, plan);
-    const size_t valid_bytes = ((size_t)slots * (size_t)e->n + 7) & ~(size_t)7;
-    const size_t total = (size_t)slots * slot_bytes + valid_bytes + 2 * sizeof(uint32_t);
-    if (e->ckpt_store.reserve(total) != hipSuccess) {
-        (void)hipGetLastError();
-        return e->fail(TBX_E_NOMEM, "TBX_EDIT_CHECKPOINT_SLOTS: no device memory for " + std::to_string(slots) + " slots of " + std::to_string(slot_bytes) + " bytes");
-    }
-    e->ckpt_slots = slots;
-    e->ckpt_slot_bytes = slot_bytes;
-    e->ckpt_sig = plan_signature(plan);
-    EHIP(hipMemsetAsync(e->ckpt_store.p + (size_t)slots * slot_bytes, 0, valid_bytes, e->stream));
-    EHIP(hipStreamSynchronize(e->stream));
-    return TBX_OK;
-}
-
-// SAVE / RESTORE on stream s.  check: the host form -- rows that cannot be carried out are an error, and nothing is changed
-static int checkpoint_copy(tbx_engine* e, bool save, const TbxEditArgs& a, const uint8_t* mask_dev, bool check, hipStream_t s)
-{
-    const char* name = save ? "TBX_EDIT_CHECKPOINT_SAVE" : "TBX_EDIT_CHECKPOINT_RESTORE";
-    if (a.n < 1 || a.n > (save ? 1 : 3)) return e->fail(TBX_E_INVALID, std::string(name) + (save ? " takes {slot}" : " takes {slot[, row[, salt]]}"));
-    if (!e->ckpt_slots) return e->fail(TBX_E_INVALID, std::string(name) + ": env 0: there is no checkpoint store (TBX_EDIT_CHECKPOINT_SLOTS makes one)");
-    TbxForkPlan plan;
-    env_plan(e, plan);
-    if (plan_signature(plan) != e->ckpt_sig)
-        return e->fail(TBX_E_UNSUPPORTED, std::string(name) + ": the engine's per-env arrays are no longer the ones the checkpoint store was made for; TBX_EDIT_CHECKPOINT_SLOTS makes a new store");
-    const CkptStore st = ckpt_view(e);
-    const size_t N = (size_t)e->n;
-    const dim3 sgrid((unsigned)((N + 255) / 256)), sblock(256);
-    const dim3 rgrid(std::min((unsigned)((N + TBX_WAVES_PER_BLOCK - 1) / TBX_WAVES_PER_BLOCK), FORK_MAX_BLOCKS)), rblock(TBX_BLOCK);
-    if (check) {
-        uint32_t* words = reinterpret_cast<uint32_t*>(st.valid + (((size_t)st.slots * N + 7) & ~(size_t)7));
-        uint32_t got[2];
-        EHIP(hipMemsetAsync(words, 0xFF, sizeof got, s));
-        if (save) hipLaunchKernelGGL(ckpt_check_kernel<true>, sgrid, sblock, 0, s, st, words, a, mask_dev, e->n);
-        else hipLaunchKernelGGL(ckpt_check_kernel<false>, sgrid, sblock, 0, s, st, words, a, mask_dev, e->n);
-        EHIP(hipGetLastError());
-        EHIP(hipMemcpyAsync(got, words, sizeof got, hipMemcpyDeviceToHost, s));
-        EHIP(hipStreamSynchronize(s));
-        if (got[0] != 0xFFFFFFFFu) {
-            const int why = (int)(got[0] & 3u);
-            const std::string what = why == CKPT_BAD_SLOT ? "names a slot outside 0 .. " + std::to_string(st.slots - 1)
-                                   : why == CKPT_BAD_ROW ? "names a row outside 0 .. " + std::to_string(e->n - 1) : "names an empty cell";
-            return e->fail(TBX_E_INVALID, std::string(name) + ": env " + std::to_string(got[0] >> 2) + " " + what + " (" + std::to_string(got[1] + 1u) + " such envs; nothing was changed)");
-        }
-    }
-    if (!save) e->ops->envs_rewritten(e);
-    bool marked = false;
-    for (size_t k0 = 0; k0 < plan.segs.size(); k0 += FORK_SEGS) {
-        ForkBatch b;
-        b.n_segs = 0;
-        bool sc = false, rw = false;
-        for (size_t k = k0; k < plan.segs.size() && k < k0 + FORK_SEGS; k++) {
-            b.seg[b.n_segs++] = plan.segs[k];
-            (plan.segs[k].row_bytes <= 8 ? sc : rw) = true;
-        }
-        if (save && !marked) sc = true;                        // (the first launch of a save marks the cells valid)
-        if (sc) {
-            if (save) hipLaunchKernelGGL(ckpt_scalars_kernel<true>, sgrid, sblock, 0, s, b, st, a, mask_dev, e->n, marked ? 0 : 1);
-            else hipLaunchKernelGGL(ckpt_scalars_kernel<false>, sgrid, sblock, 0, s, b, st, a, mask_dev, e->n, 0);
-            marked = true;
-        }
-        if (rw) {
-            if (save) hipLaunchKernelGGL(ckpt_rows_kernel<true>, rgrid, rblock, 0, s, b, st, a, mask_dev, e->n);
-            else hipLaunchKernelGGL(ckpt_rows_kernel<false>, rgrid, rblock, 0, s, b, st, a, mask_dev, e->n);
-        }
-    }
-    if (!save && a.n >= 3) {
-        ForkBatch rng;
-        rng.n_segs = 0;
-        for (const TbxForkSeg& g : plan.segs)
-            if (g.rng_words && rng.n_segs < FORK_SEGS) rng.seg[rng.n_segs++] = g;
-        hipLaunchKernelGGL(ckpt_salt_kernel, sgrid, sblock, 0, s, rng, st, a, mask_dev, e->n);
-    }
-    EHIP(hipGetLastError());
-    return TBX_OK;
-}
-
 extern "C" {
 
 // one frame of one env, optionally with its picture (channels 0 / 1 / 3 / 4) in e->serve_frame
@@ -1628,10 +1190,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
         return e->ops->lookahead(e, a, query == TBX_QUERY_LOOKAHEAD_ALL, out_dev, s);
     }
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
-    if (a.n < 1 || a.n > 2) return e->fail(TBX_E_INVALID, "TBX_QUERY_CHECKPOINT_VALID takes {slot[, row]}");
-    hipLaunchKernelGGL(ckpt_valid_kernel, dim3((e->n + 255) / 256), dim3(256), 0, s, ckpt_view(e), a, out_dev, e->n);
-    EHIP(hipGetLastError());
-    return TBX_OK;
+    return checkpoint_valid(e, a, out_dev, s);
 }
 
 int tbx_edit_device(tbx_engine* e, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream)

@@ -771,9 +771,9 @@ struct GridWorldOps : GameOps {
 
     // TBX_EDIT_COPY_ENV: scalars (struct of arrays), the env-major tile table and grid, of the live state and of the agent
     // layer's two slots (GridWorld has no RNG of its own)
-    void list_envs(tbx_engine*, TbxForkPlan& plan) override
+    void list_envs(tbx_engine*, TbxEnvPlan& plan) override
     {
-        for (GwDev* x : {&d, &dA, &dB}) tbx_fork_arrays(plan, *x, x == &d);
+        for (GwDev* x : {&d, &dA, &dB}) tbx_list_arrays(plan, *x, x == &d);
     }
 
     int scalars(tbx_engine* e, int32_t* score_dev, int32_t* lives_dev, int32_t* level_dev, hipStream_t s) override

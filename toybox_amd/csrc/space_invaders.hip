@@ -2174,9 +2174,9 @@ struct SiOps : GameOps {
     // TBX_EDIT_COPY_ENV: the four env-major tables (the head row carries the scalars, the formation-origin mirror and the RNG) of
     // the live state and of the agent layer's two slots; `custom` and `plain` are engine-wide and stay (a copy of a canonical
     // env is canonical)
-    void list_envs(tbx_engine*, TbxForkPlan& plan) override
+    void list_envs(tbx_engine*, TbxEnvPlan& plan) override
     {
-        for (SiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_fork_arrays(plan, *x, x == &d);   // (the kept copies too: mode 2 travels with the env)
+        for (SiDev* x : {&d, &dA, &dB, &dKA, &dKB}) tbx_list_arrays(plan, *x, x == &d);   // (the kept copies too: mode 2 travels with the env)
     }
     void envs_rewritten(tbx_engine*) override { recs.valid = false; }
 

@@ -439,13 +439,7 @@ struct tbx_engine {
     TbxDevBuf<double> edit_args;    // [N][n_args] per-env arguments of tbx_edit / tbx_reduce (host-pointer forms)
     TbxDevBuf<double> reduce_out;   // [N][width] result staging of tbx_reduce
     TbxDevBuf<void> staging;        // device POD staging for get/set state
-    TbxDevBuf<uint8_t> fork_scratch;   // TBX_EDIT_COPY_ENV: the gathered rows between the two passes of a fork (engine.hip, fork_envs)
-    // TBX_EDIT_CHECKPOINT_*: `ckpt_slots` planes of N env cells, each plane laid out like the fork's scratch (every per-env array
-    // at a 256-byte-aligned offset, ckpt_slot_bytes in all), then valid[slots][N] and the two words of the host forms' check
-    TbxDevBuf<uint8_t> ckpt_store;
-    int ckpt_slots = 0;
-    size_t ckpt_slot_bytes = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> ckpt_sig;   // {fields, row_bytes} of the arrays the store was made for, in plan order
+    struct TbxEnvCopy* envcopy = nullptr;   // TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*: the fork's scratch copy, the checkpoint store (envcopy.hip), made on first use
     GameOps* ops = nullptr;
     struct AgentState* agent = nullptr;   // fused agent-side preprocessing (agent.hip), lazily created
     struct GatherState* gather = nullptr; // multi-GPU record gather over RCCL (gather.hip), created by tbx_gather_init
@@ -468,7 +462,7 @@ struct tbx_engine {
 hipError_t tbx_serve_stop(tbx_engine* e);   // engine.hip
 hipError_t tbx_finish_pending(tbx_engine* e);   // engine.hip: ends a step that is between "_begin" and "_end" (outputs delivered, result kept)
 int tbx_agent_deliver(tbx_engine* e);       // agent.hip: the waiting half of tbx_agent_step_end
-void tbx_agent_copy_envs(tbx_engine* e, struct TbxForkPlan& plan);   // agent.hip: the wrapper stack's per-env arrays of TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*
+void tbx_agent_copy_envs(tbx_engine* e, struct TbxEnvPlan& plan);   // agent.hip: the wrapper stack's per-env arrays of TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*
 
 // Stream `s` waits for everything queued so far on the stream the previous call used.  That stream may be the caller's: the
 // handle is kept until the next call or tbx_sync (toybox_amd.h: a stream named in a call must stay alive that long -- the
@@ -558,13 +552,14 @@ struct TbxEditArgs {
         const double x = get(env, i);
         return x >= 4294967295.0 ? 0xFFFFFFFFu : x > 0.0 ? (uint32_t)x : 0u;
     }
-    __device__ __forceinline__ int geti(int env, int i) const
+    // an integer argument: clamped to +-2e9, NaN reads -2e9 (the host forms check their rows with the same rule)
+    __host__ __device__ __forceinline__ static int to_int(double x)
     {
-        double x = get(env, i);
         if (!(x > -2.0e9)) x = -2.0e9;
         if (x > 2.0e9) x = 2.0e9;
         return (int)x;
     }
+    __device__ __forceinline__ int geti(int env, int i) const { return to_int(get(env, i)); }
 };
 
 // TBX_QUERY_LOOKAHEAD / _ALL (include/toybox_amd.h): the schedule of one (env, candidate) pair and the loop every game's
@@ -650,33 +645,34 @@ void tbx_lookahead_launches(int n, int cands, F&& f)
         f(p0, (int)(pairs - p0 < TBX_LOOKAHEAD_PAIRS_PER_LAUNCH ? pairs - p0 : TBX_LOOKAHEAD_PAIRS_PER_LAUNCH));
 }
 
-// TBX_EDIT_COPY_ENV (engine.hip, fork_envs): one per-env array of an engine as the copy kernels see it -- `fields` planes of
-// N rows of row_bytes each, [fields][N][row_bytes].  A struct-of-arrays scalar [F][N] is F planes of 4- or 8-byte rows, an
-// env-major table [N][R] one plane of R-byte rows, the plane ring `stack` planes of out_h * out_w bytes.  rng_words > 0: every
-// row holds that many 64-bit RNG words at byte rng_off (what the fork's `salt` argument rewrites in the destinations).
-// rot: the plane that is first in LOGICAL order (the plane ring: its oldest plane, head + 1); the fork copies planes as they lie
-// and ignores it, a checkpoint cell keeps them in logical order (engine.hip, checkpoint_copy).
-struct TbxForkSeg {
+// One per-env array of an engine as the env-copy kernels see it (envcopy.hip: fork, checkpoint save and restore) -- `fields`
+// planes of N rows of row_bytes each, [fields][N][row_bytes].  A struct-of-arrays scalar [F][N] is F planes of 4- or 8-byte rows,
+// an env-major table [N][R] one plane of R-byte rows, the plane ring `stack` planes of out_h * out_w bytes.  rng_words > 0: every
+// row holds that many 64-bit RNG words at byte rng_off (what a `salt` argument rewrites in the envs that were written).
+// A row is LIVE (in the engine's array at `base`, planes as they lie) or PACKED (in a packed copy of all arrays -- the fork's
+// scratch, a slot of the checkpoint store -- at byte packed_off of it, planes in LOGICAL order).  rot: the live plane that is
+// first in logical order (the plane ring: its oldest plane, head + 1); plane c of a packed copy is live plane (rot + c) % fields.
+struct TbxEnvSeg {
     uint8_t* base;
-    uint64_t scratch_off;         // where the array's gathered copy lies in tbx_engine::fork_scratch (filled in by fork_envs)
+    uint64_t packed_off;          // filled in by env_plan (envcopy.hip)
     uint32_t fields, row_bytes, rng_off, rng_words, rot;
 };
-struct TbxForkPlan {
-    std::vector<TbxForkSeg> segs;
+struct TbxEnvPlan {
+    std::vector<TbxEnvSeg> segs;
     template <typename T>
     void soa(T* base, int fields, int rng_words = 0)           // [fields][N] scalars
     {
-        if (base) segs.push_back(TbxForkSeg{reinterpret_cast<uint8_t*>(base), 0, (uint32_t)fields, (uint32_t)sizeof(T), 0u, (uint32_t)rng_words, 0u});
+        if (base) segs.push_back(TbxEnvSeg{reinterpret_cast<uint8_t*>(base), 0, (uint32_t)fields, (uint32_t)sizeof(T), 0u, (uint32_t)rng_words, 0u});
     }
     void rows(void* base, size_t row_bytes, int fields = 1, size_t rng_off = 0, int rng_words = 0)   // [fields][N][row_bytes]
     {
-        if (base) segs.push_back(TbxForkSeg{static_cast<uint8_t*>(base), 0, (uint32_t)fields, (uint32_t)row_bytes, (uint32_t)rng_off, (uint32_t)rng_words, 0u});
+        if (base) segs.push_back(TbxEnvSeg{static_cast<uint8_t*>(base), 0, (uint32_t)fields, (uint32_t)row_bytes, (uint32_t)rng_off, (uint32_t)rng_words, 0u});
     }
 };
 
-// How one per-env device array of a state struct (AmiDev, SiDev, GwDev, BrkDev, ...) lies in memory, in the two forms the fork
+// How one per-env device array of a state struct (AmiDev, SiDev, GwDev, BrkDev, ...) lies in memory, in the two forms the env
 // plan takes.  Every such struct lists its arrays ONCE, in a constexpr member template `arrays(f)` that calls f(member, TbxLayout)
-// per array; allocation, release and the fork plan of an instance are derived from that list by the helpers below, and a
+// per array; allocation, release and the env plan of an instance are derived from that list by the helpers below, and a
 // static_assert next to the list compares tbx_array_count with the struct's size, so a pointer member without an entry does not build.
 struct TbxLayout {
     uint32_t fields, row_bytes, rng_off, rng_words;   // row_bytes 0: the element's size
@@ -731,9 +727,9 @@ hipError_t tbx_zero_arrays(Dev& x, size_t n)
     tbx_each_array(x, n, [&](void** p, TbxLayout, size_t bytes) { if (r == hipSuccess && *p) r = hipMemset(*p, 0, bytes); });
     return r;
 }
-// the arrays of one instance that exist, appended to a fork plan; live: its RNG words are the ones the fork's `salt` rewrites
+// the arrays of one instance that exist, appended to an env plan; live: its RNG words are the ones a `salt` rewrites
 template <class Dev>
-void tbx_fork_arrays(TbxForkPlan& plan, Dev& x, bool live)
+void tbx_list_arrays(TbxEnvPlan& plan, Dev& x, bool live)
 {
     tbx_each_array(x, 0, [&](void** p, TbxLayout l, size_t) { plan.rows(*p, l.row_bytes, (int)l.fields, live ? l.rng_off : 0, live ? (int)l.rng_words : 0); });
 }
@@ -833,7 +829,7 @@ struct GameOps {
     // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The
     // engine adds sim_rng, prev_score and the agent layer and runs the copy.  Listing changes nothing; a copy that WROTE live
     // envs (a fork, a restore -- not a save) says so with envs_rewritten(): step-written render records no longer describe the state.
-    virtual void list_envs(tbx_engine* e, TbxForkPlan& plan) = 0;
+    virtual void list_envs(tbx_engine* e, TbxEnvPlan& plan) = 0;
     virtual void envs_rewritten(tbx_engine*) {}
     // an engine option changed (tbx_set_option): pick it up
     virtual void options_changed(tbx_engine*) {}
