@@ -661,6 +661,29 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
 #define TBX_LOOKAHEAD_MAX_FRAMES 1024
 #define TBX_QUERY_LOOKAHEAD      150  /* {frames, hold, first, rest, seed_lo, seed_hi, t, env_offset} -> 5 */
 #define TBX_QUERY_LOOKAHEAD_ALL  151  /* {frames, hold, (ignored), rest, seed_lo, seed_hi, t, env_offset} -> 5 * n_legal(game) */
+/* Plans: the lookahead with an action sequence instead of one first action, and a search over every sequence of a depth.
+ *   Plan codes: with L = n_legal(game), a plan of `depth` periods is code = sum over p of digit_p * L^p, digit_p an index into the
+ *   legal set in its order (above), digit_0 the first action.  Period p (frames p * hold .. (p + 1) * hold - 1, as above) plays
+ *   legal[digit_p] while p < depth and `rest` from then on (-1: drawn with counter t + p, the key as above).  Everything else --
+ *   the run, the exit at game over, the five fields, "nothing in the engine changes", shared or per-env rows through tbx_reduce /
+ *   tbx_reduce_device -- is the lookahead's.  Trailing arguments may be left out: hold 1, depth 0 (search: 1), code 0,
+ *   objective 0, rest -1, seed 0, t 0, env_offset 0.
+ *   TBX_QUERY_LOOKAHEAD_PLAN plays one plan per env: depth 0 .. TBX_PLAN_MAX_DEPTH(game) (the largest with L^depth <= 2^32),
+ *   0 <= code < L^depth.  depth 0 is TBX_QUERY_LOOKAHEAD with first = rest, depth 1 the same with first = legal[code].
+ *   TBX_QUERY_LOOKAHEAD_SEARCH plays all L^depth plans of every env (1 <= depth, L^depth <= TBX_LOOKAHEAD_MAX_PLANS: Breakout 6,
+ *   SpaceInvaders and Amidar 4, GridWorld 5) and answers, for each first action a in legal-set order, row out[env][a][0 .. 5] =
+ *   {ret, score, lives, frames run, life lost at, code} of the BEST plan with digit_0 = a.  Best is a total order: with
+ *   loss = life lost at < 0 ? TBX_LOOKAHEAD_MAX_FRAMES + 1 : life lost at, objective 0 (return) takes the larger ret, then the
+ *   larger lives, then the larger loss, then the smaller code; objective 1 (survival) the larger lives, then the larger loss,
+ *   then the larger ret, then the smaller code.  Feeding a returned code to TBX_QUERY_LOOKAHEAD_PLAN gives the row's five fields.
+ *   The leaves are played one after the other by (env, first action, chunk) units and only the winners leave the GPU; large
+ *   searches are cut into several launches.  Neither changes the answer.
+ *   TBX_E_INVALID, nothing launched: a shared value out of the ranges above (frames, hold, depth, code, objective, rest), more
+ *   than 9 arguments.  In per-env rows such an env's output is zeros -- frames run 0 -- and the other envs are answered. */
+#define TBX_LOOKAHEAD_MAX_PLANS 4096
+#define TBX_PLAN_MAX_DEPTH(game) ((game) == TBX_GAME_BREAKOUT ? 16 : (game) == TBX_GAME_GRIDWORLD ? 13 : 12)
+#define TBX_QUERY_LOOKAHEAD_PLAN   152  /* {frames, hold, depth, code, rest, seed_lo, seed_hi, t, env_offset} -> 5 */
+#define TBX_QUERY_LOOKAHEAD_SEARCH 153  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset} -> 6 * n_legal(game) */
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);
@@ -956,6 +979,8 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
 #define TBX_OPT_FUSED_OVERLAP_ACTIVE 103
 /* read-only: 1 if tbx_rollout_synthetic(channels = 3) would run as overlapped chunks right now, 0 if as single calls */
 #define TBX_OPT_ROLLOUT_CHUNKS_ACTIVE 104
+/* read-only: into how many chunks the last TBX_QUERY_LOOKAHEAD_SEARCH cut every (env, first action) group of plans (0: none yet) */
+#define TBX_OPT_SEARCH_CHUNKS 105
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
 /* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could

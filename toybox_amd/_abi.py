@@ -42,6 +42,7 @@ OPT_ROLLOUT_CHUNKS = 9             # tbx_rollout_synthetic as one step launch + 
 ROLLOUT_CHUNKS_AUTO, ROLLOUT_CHUNKS_ON, ROLLOUT_CHUNKS_OFF = 0, 1, 2
 ROLLOUT_CHUNKS_PER_FRAME, ROLLOUT_CHUNKS_SPAN = 3, 4   # on, with the rasteriser form named: a launch per frame on two lanes, one per chunk on one
 OPT_ROLLOUT_CHUNKS_ACTIVE = 104    # read-only: it would run that way right now
+OPT_SEARCH_CHUNKS = 105            # read-only: chunks per (env, first action) group of the last TBX_QUERY_LOOKAHEAD_SEARCH
 PIPELINE_OFF, PIPELINE_AUTO, PIPELINE_STEP_BESIDE_RENDER, PIPELINE_OVERLAP_RENDERS = 0, 1, 2, 3
 STEP_FORM_AUTO, STEP_FORM_THREAD_PER_ENV, STEP_FORM_WAVE_PER_ENV = 0, 1, 2
 
@@ -97,6 +98,12 @@ QUERY_CHECKPOINT_VALID = 140
 LOOKAHEAD_MAX_FRAMES = 1024
 QUERY_LOOKAHEAD = 150
 QUERY_LOOKAHEAD_ALL = 151
+LOOKAHEAD_MAX_PLANS = 4096
+QUERY_LOOKAHEAD_PLAN = 152
+QUERY_LOOKAHEAD_SEARCH = 153
+# the legal sets in the engine's order (tbx_legal_actions) and TBX_PLAN_MAX_DEPTH: the largest depth with n_legal ** depth <= 2 ** 32
+LEGAL_ACTIONS = {"breakout": (0, 1, 3, 4), "space_invaders": (0, 1, 3, 4, 11, 12), "amidar": (0, 1, 2, 3, 4, 5), "gridworld": (0, 2, 3, 4, 5)}
+PLAN_MAX_DEPTH = {"breakout": 16, "space_invaders": 12, "amidar": 12, "gridworld": 13}
 
 BRK_MAX_BALLS, BRK_COLS, BRK_MAX_ROWS, BRK_MAX_BRICKS, BRK_MAX_STARTS, BRK_MAX_SEGMENTS = 4, 18, 14, 256, 8, 16
 

@@ -1286,6 +1286,20 @@ __global__ __launch_bounds__(TBX_BLOCK) void ami_lookahead_kernel(AmiDev d, TbxE
              [&] { return wave_uniform(s.f[A_SCORE]); }, [&] { return wave_uniform(s.f[A_LIVES]); });
 }
 
+// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (tbx_plan_kernel, tbx_search_kernel): a wave per unit, the plan as the action source
+struct AmiLook {
+    static constexpr int GAME = TBX_GAME_AMIDAR, BLOCK = TBX_BLOCK;
+    static constexpr bool WAVE = true;
+    AmiDev d;
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look) const
+    {
+        AmiRegs s;
+        ami_load(d, env, lane, s);
+        return look.run_fields([&](uint32_t buttons) { ami_step(*d.tab, lane, (uint32_t)wave_uniform((int)buttons), s); },
+                               [&] { return wave_uniform(s.f[A_SCORE]); }, [&] { return wave_uniform(s.f[A_LIVES]); });
+    }
+};
+
 __global__ __launch_bounds__(TBX_BLOCK) void ami_agent_step_kernel(AmiDev d, AmiDev slot_a, AmiDev slot_b, ActionSource src, uint32_t flags, int first_env, int count)
 {
     const int lane = threadIdx.x & 63;
@@ -2270,6 +2284,18 @@ struct AmiOps : GameOps {
         tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
             hipLaunchKernelGGL(ami_lookahead_kernel, grid_for(count), dim3(TBX_BLOCK), 0, s, d, a, cands, p0, count, out_dev);
         });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_plan(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s) override
+    {
+        tbx_launch_plan(AmiLook{d}, a, e->n, out_dev, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        tbx_launch_search(AmiLook{d}, a, chunks, first_env, envs, rows, s);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

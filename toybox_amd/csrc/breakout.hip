@@ -975,6 +975,37 @@ __global__ __launch_bounds__(TBX_BLOCK) void brk_lookahead_kernel(BrkDev d, BrkC
              [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.lives); });
 }
 
+// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (tbx_plan_kernel, tbx_search_kernel): the same two forms with the plan as the action source.
+// A thread per unit on the canonical wall ...
+struct BrkTLook {
+    static constexpr int GAME = TBX_GAME_BREAKOUT, BLOCK = 128;
+    static constexpr bool WAVE = false;
+    BrkDev d;
+    const BrkCfg* cp;
+    __device__ __forceinline__ TbxLookFields leaf(int env, int, const TbxLookahead<GAME, true>& look) const
+    {
+        const BrkCfg& c = *cp;
+        BrkT s;
+        t_load(d, env, s);
+        return look.run_fields([&](uint32_t buttons) { brk_t_step(c, s, buttons); }, [&] { return s.score; }, [&] { return s.lives; });
+    }
+};
+// ... and a wave per unit once the wall is custom (and for TBX_OPT_STEP_FORM = 2)
+template <bool CUSTOM>
+struct BrkWaveLook {
+    static constexpr int GAME = TBX_GAME_BREAKOUT, BLOCK = TBX_BLOCK;
+    static constexpr bool WAVE = true;
+    BrkDev d;
+    BrkCfg c;
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look) const
+    {
+        BrkRegs s;
+        brk_load(d, env, lane, s);
+        return look.run_fields([&](uint32_t buttons) { brk_wave_frame<CUSTOM>(d, c, env, lane, (uint32_t)wave_uniform((int)buttons), s); },
+                               [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.lives); });
+    }
+};
+
 // reset-time wrappers of the agent layer for the envs flagged in r.kind (agent_device.hpp, AgentResetProc)
 struct BrkTEnv {
     const BrkCfg& c;
@@ -2386,6 +2417,22 @@ struct BreakoutOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+
+    int lookahead_plan(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s) override
+    {
+        if (!custom && use_tpe) tbx_launch_plan(BrkTLook{d, cfg_dev}, a, e->n, out_dev, s);
+        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_plan(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, e->n, out_dev, s); });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        if (!custom && use_tpe) tbx_launch_search(BrkTLook{d, cfg_dev}, a, chunks, first_env, envs, rows, s);
+        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_search(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, chunks, first_env, envs, rows, s); });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int search_lanes() const override { return !custom && use_tpe ? 1 : 64; }
 
     // TBX_EDIT_COPY_ENV: the struct-of-arrays state, the per-env brick table of the custom mode and the two record slots of the
     // agent layer (a copy of a canonical env is canonical: `custom` stays as it is)

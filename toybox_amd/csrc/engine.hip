@@ -309,7 +309,7 @@ int tbx_destroy(tbx_engine* e)
     }
     pipe_free(e);
     hipFree(e->actions);
-    e->edit_args.release(); e->reduce_out.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
+    e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
     hipFree(e->mask); hipFree(e->err_flag); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
     if (e->io_host) hipHostFree(e->io_host);
     if (e->scal_host) hipHostFree(e->scal_host);
@@ -1147,6 +1147,8 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_CHECKPOINT_VALID: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 1 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_ALL: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_PLAN: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_SEARCH: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     default: return TBX_E_INVALID;
     }
 }
@@ -1166,6 +1168,78 @@ static int edit_args(tbx_engine* e, const double* args, int n_args, int per_env,
     EHIP(e->edit_args.reserve(bytes, e->stream));
     EHIP(hipMemcpyAsync(e->edit_args.p, args, bytes, hipMemcpyHostToDevice, s));
     a.per_env = e->edit_args.p;
+    return TBX_OK;
+}
+
+// chunks > 1: the winner among the partial rows parts[group][chunks][6] of every (env, first action) group of envs from
+// first_env on, by the order of the search kernel; a group without a leaf (a refused row) answers zeros
+__global__ __launch_bounds__(256) void tbx_search_pick_kernel(const double* __restrict__ parts, TbxEditArgs a, int legal, int chunks, long long first_group, int count,
+                                                              double* __restrict__ out)
+{
+    const int rel = blockIdx.x * 256 + threadIdx.x;
+    if (rel >= count) return;
+    const long long group = first_group + rel;
+    const int env = (int)(group / legal);
+    const int objective = a.n > 3 ? a.geti(env, 3) : 0;
+    const double* p = parts + group * chunks * 6;
+    TbxLookFields best{0, 0, 0, 0, 0};
+    uint32_t best_code = 0;
+    bool none = true;
+    for (int c = 0; c < chunks; c++, p += 6) {
+        if (p[5] < 0.0) continue;
+        const TbxLookFields f{(long long)p[0], (int)p[1], (int)p[2], (int)p[3], (int)p[4]};
+        const uint32_t code = (uint32_t)p[5];
+        if (none || tbx_search_better(objective, f, code, best, best_code)) { best = f; best_code = code; none = false; }
+    }
+    tbx_search_store(out + group * 6, best, best_code, none, false);
+}
+
+// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH: shared values are refused here, before anything is launched; per-env rows are met by the
+// kernels.  The search is cut into chunks (tbx_search_chunks) and into launches over env ranges (tbx_search_launches).
+static int lookahead_plans(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, hipStream_t s)
+{
+    const bool search = query == TBX_QUERY_LOOKAHEAD_SEARCH;
+    const int L = tbx_legal_count(e->game);
+    if (a.n < 1 || a.n > 9)
+        return e->fail(TBX_E_INVALID, search ? "search takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset]}" : "plan takes {frames[, hold, depth, code, rest, seed_lo, seed_hi, t, env_offset]}");
+    long long plans = TBX_LOOKAHEAD_MAX_PLANS, frames = TBX_LOOKAHEAD_MAX_FRAMES;      // per-env rows: the most a valid row can ask for
+    if (!a.per_env) {
+        auto playable = [&](double v) {
+            if (v == -1.0) return true;
+            for (int i = 0; i < L; i++)
+                if (v == (double)tbx_legal_action(e->game, i)) return true;
+            return false;
+        };
+        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        const double depth = a.n > 2 ? a.v[2] : search ? 1.0 : 0.0;
+        if (!(depth >= (search ? 1.0 : 0.0) && depth <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "lookahead: depth must be 0 (search: 1) .. TBX_PLAN_MAX_DEPTH(game)");
+        const uint64_t count = tbx_plan_count(e->game, TbxEditArgs::to_int(depth));
+        if (search && count > (uint64_t)TBX_LOOKAHEAD_MAX_PLANS) return e->fail(TBX_E_INVALID, "search: n_legal^depth must not exceed TBX_LOOKAHEAD_MAX_PLANS");
+        if (search && a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "search: objective must be 0 (return) or 1 (survival)");
+        if (!search && a.n > 3 && !(a.v[3] >= 0.0 && a.v[3] < (double)count)) return e->fail(TBX_E_INVALID, "plan: code must be 0 .. n_legal^depth - 1");
+        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        plans = (long long)count;
+        frames = TbxEditArgs::to_int(a.v[0]);
+    }
+    if (!search) return e->ops->lookahead_plan(e, a, out_dev, s);
+    const int chunks = tbx_search_chunks(e->n, L, plans / L, e->ops->search_lanes());
+    double* rows = out_dev;
+    if (chunks > 1) {
+        EHIP(e->search_parts.reserve(sizeof(double) * 6 * (size_t)e->n * (size_t)L * (size_t)chunks, e->stream, s));
+        rows = e->search_parts.p;
+    }
+    e->search_chunks = chunks;
+    int rc = TBX_OK;
+    tbx_search_launches(e->n, (long long)L * chunks, plans * frames, [&](int env0, int envs) {
+        if (rc) return;
+        rc = e->ops->lookahead_search(e, a, chunks, env0, envs, rows, s);
+        if (rc || chunks == 1) return;
+        const int groups = envs * L;
+        hipLaunchKernelGGL(tbx_search_pick_kernel, dim3((groups + 255) / 256), dim3(256), 0, s, rows, a, L, chunks, (long long)env0 * L, groups, out_dev);
+    });
+    if (rc) return rc;
+    EHIP(hipGetLastError());
     return TBX_OK;
 }
 
@@ -1189,6 +1263,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
         }
         return e->ops->lookahead(e, a, query == TBX_QUERY_LOOKAHEAD_ALL, out_dev, s);
     }
+    if (query == TBX_QUERY_LOOKAHEAD_PLAN || query == TBX_QUERY_LOOKAHEAD_SEARCH) return lookahead_plans(e, query, a, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     return checkpoint_valid(e, a, out_dev, s);
 }
@@ -1360,6 +1435,7 @@ int tbx_get_option(tbx_engine* e, int option, int* value_out)
     if (value_out && option == TBX_OPT_RENDER_STEP_FUSED) { *value_out = e->ops->render_step_fused(3) ? 1 : 0; return TBX_OK; }
     if (value_out && option == TBX_OPT_FUSED_OVERLAP_ACTIVE) { *value_out = fused_overlap_on(e, nullptr, 3) ? 1 : 0; return TBX_OK; }
     if (value_out && option == TBX_OPT_ROLLOUT_CHUNKS_ACTIVE) { *value_out = rollout_chunks_on(e, 3) ? 1 : 0; return TBX_OK; }
+    if (value_out && option == TBX_OPT_SEARCH_CHUNKS) { *value_out = e->search_chunks; return TBX_OK; }
     if (option < 0 || option >= TBX_OPT_COUNT || !value_out) return e->fail(TBX_E_INVALID, "unknown option");
     *value_out = e->opt[option];
     return TBX_OK;

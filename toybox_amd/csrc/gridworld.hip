@@ -219,6 +219,28 @@ __global__ __launch_bounds__(TBX_BLOCK) void gw_lookahead_kernel(GwDev d, TbxEdi
              [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.over ? 0 : 1); });
 }
 
+// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (tbx_plan_kernel, tbx_search_kernel): a wave per unit, the plan as the action source; every
+// leaf copies the board into the wave's LDS slice again
+struct GwLook {
+    static constexpr int GAME = TBX_GAME_GRIDWORLD, BLOCK = TBX_BLOCK;
+    static constexpr bool WAVE = true;
+    GwDev d;
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look) const
+    {
+        __shared__ uint32_t boards[TBX_WAVES_PER_BLOCK][CELLS / 4];
+        uint32_t* const mine = boards[wave_uniform((int)(threadIdx.x >> 6))];
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(d.grid + (size_t)env * CELLS);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       // the previous leaf's reads of the slice come first
+        for (int i = lane; i < CELLS / 4; i += 64) mine[i] = src[i];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       // gw_step_on() reads cells other lanes copied
+        const uint32_t* tiles = d.tiles + (size_t)env * GT * 3;
+        GwT s;
+        gw_load(d, env, s);
+        return look.run_fields([&](uint32_t buttons) { gw_step_on(reinterpret_cast<uint8_t*>(mine), tiles, s, buttons); },
+                               [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.over ? 0 : 1); });
+    }
+};
+
 // reset-time wrappers of the agent layer (agent_device.hpp, AgentResetProc), thread per flagged env
 // the dynamic state of one env (scalars, tile table, board) copied live -> slot by `lanes` cooperating lanes
 __device__ __forceinline__ void gw_copy_env(const GwDev& dst, const GwDev& src, int env, int lane, int lanes)
@@ -765,6 +787,18 @@ struct GridWorldOps : GameOps {
         tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
             hipLaunchKernelGGL(gw_lookahead_kernel, grid_for(count), dim3(TBX_BLOCK), 0, s, d, a, cands, p0, count, out_dev);
         });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_plan(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s) override
+    {
+        tbx_launch_plan(GwLook{d}, a, e->n, out_dev, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        tbx_launch_search(GwLook{d}, a, chunks, first_env, envs, rows, s);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

@@ -856,6 +856,21 @@ __global__ __launch_bounds__(TBX_BLOCK) void si_lookahead_kernel(SiDev d, SiCfg 
              [&] { return wave_uniform(s.f[F_SCORE]); }, [&] { return wave_uniform(s.f[F_LIVES]); });
 }
 
+// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (tbx_plan_kernel, tbx_search_kernel): a wave per unit, the full load, the plan as the action source
+struct SiLook {
+    static constexpr int GAME = TBX_GAME_SPACE_INVADERS, BLOCK = TBX_BLOCK;
+    static constexpr bool WAVE = true;
+    SiDev d;
+    SiCfg c;
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look) const
+    {
+        SiRegs s;
+        si_load(d, env, lane, s);
+        return look.run_fields([&](uint32_t buttons) { si_step(c, lane, (uint32_t)wave_uniform((int)buttons), s); },
+                               [&] { return wave_uniform(s.f[F_SCORE]); }, [&] { return wave_uniform(s.f[F_LIVES]); });
+    }
+};
+
 // records of envs [first_env, first_env + count) from their state (after a new game, a state write, an agent step ...)
 __global__ __launch_bounds__(TBX_BLOCK) void si_rec_prep_kernel(SiDev d, SiRenderRec* __restrict__ recs, int first_env, int count)
 {
@@ -2196,6 +2211,18 @@ struct SiOps : GameOps {
         tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
             hipLaunchKernelGGL(si_lookahead_kernel, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, a, cands, p0, count, out_dev);
         });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_plan(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s) override
+    {
+        tbx_launch_plan(SiLook{d, c}, a, e->n, out_dev, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        tbx_launch_search(SiLook{d, c}, a, chunks, first_env, envs, rows, s);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

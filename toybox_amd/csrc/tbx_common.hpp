@@ -110,6 +110,15 @@ __host__ __device__ __forceinline__ int tbx_legal_action(int game, int i)
     if (game == TBX_GAME_AMIDAR) return i;
     return i == 0 ? 0 : i == 1 ? 1 : i == 2 ? 3 : i == 3 ? 4 : i == 4 ? 11 : 12;
 }
+// Plans (TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH): the largest depth whose n_legal^depth codes fit 2^32 (TBX_PLAN_MAX_DEPTH), and
+// n_legal^depth for a depth in that range
+__host__ __device__ __forceinline__ int tbx_plan_max_depth(int game) { return TBX_PLAN_MAX_DEPTH(game); }
+__host__ __device__ __forceinline__ uint64_t tbx_plan_count(int game, int depth)
+{
+    uint64_t c = 1;
+    for (int i = 0; i < depth; i++) c *= (uint64_t)tbx_legal_count(game);
+    return c;
+}
 
 // how the step kernels obtain their action
 struct ActionSource {
@@ -438,6 +447,8 @@ struct tbx_engine {
     size_t frame_bytes = 0;         // ... and the size of that frame, N * H * W * channels of the call that produced it
     TbxDevBuf<double> edit_args;    // [N][n_args] per-env arguments of tbx_edit / tbx_reduce (host-pointer forms)
     TbxDevBuf<double> reduce_out;   // [N][width] result staging of tbx_reduce
+    TbxDevBuf<double> search_parts; // [N][n_legal][chunks][6] partial rows of TBX_QUERY_LOOKAHEAD_SEARCH cut into chunks
+    int search_chunks = 0;          // chunks of the last TBX_QUERY_LOOKAHEAD_SEARCH (0: none yet)
     TbxDevBuf<void> staging;        // device POD staging for get/set state
     struct TbxEnvCopy* envcopy = nullptr;   // TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*: the fork's scratch copy, the checkpoint store (envcopy.hip), made on first use
     GameOps* ops = nullptr;
@@ -564,11 +575,21 @@ struct TbxEditArgs {
 
 // TBX_QUERY_LOOKAHEAD / _ALL (include/toybox_amd.h): the schedule of one (env, candidate) pair and the loop every game's
 // lookahead kernel runs around its own step body.  The state lives in the caller's registers between one load and NO store.
-template <int GAME>
+// The five fields of one played schedule, as TbxLookahead::run_fields leaves them in registers.
+struct TbxLookFields {
+    long long ret;
+    int score, lives, frames_run, lost_at;
+};
+// PLAN (TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH): the action of period p < depth is digit p of `code` in base n_legal instead of
+// `first`; the branch exists in that instantiation only (depth and code are dead members in the other), so the 150 / 151 kernels
+// compile to what they were (profiles/search.md).
+template <int GAME, bool PLAN = false>
 struct TbxLookahead {
     int frames, hold, first, rest;
     uint64_t key;                 // seed ^ ((env_offset + env) << 32)
     uint64_t t;
+    int depth = 0;                // PLAN: periods that play a digit of the code
+    uint32_t code = 0;            // PLAN: sum of digit_p * n_legal^p, below n_legal^depth <= 2^32 (a full 4^16 tree: codes 0 .. 2^32-1)
     static __device__ __forceinline__ bool playable(int a)
     {
         if (a == -1) return true;
@@ -595,9 +616,36 @@ struct TbxLookahead {
         frames = wave_uniform(frames); hold = wave_uniform(hold); first = wave_uniform(first); rest = wave_uniform(rest);
         key = wave_uniform64(key); t = wave_uniform64(t);
     }
+    // PLAN, {frames, hold, depth, code | objective, rest, seed_lo, seed_hi, t, env_offset}: everything but column 3, which the
+    // caller reads (the plan query its code, the search its objective and then every code of its chunk in turn)
+    __device__ __forceinline__ bool read_plan(const TbxEditArgs& a, int env, int depth_default)
+    {
+        frames = a.geti(env, 0);
+        hold = a.n > 1 ? a.geti(env, 1) : 1;
+        depth = a.n > 2 ? a.geti(env, 2) : depth_default;
+        first = -1;
+        rest = a.n > 4 ? a.geti(env, 4) : -1;
+        const uint64_t seed = (uint64_t)a.getu(env, 5) | ((uint64_t)a.getu(env, 6) << 32);
+        t = a.getu(env, 7);
+        key = seed ^ (((uint64_t)a.getu(env, 8) + (uint64_t)env) << 32);
+        return frames >= 1 && frames <= TBX_LOOKAHEAD_MAX_FRAMES && hold >= 1 && depth >= 0 && depth <= tbx_plan_max_depth(GAME) && playable(rest);
+    }
+    __device__ __forceinline__ void uniform_plan()
+    {
+        uniform();
+        depth = wave_uniform(depth); code = (uint32_t)wave_uniform((int)code);
+    }
     __device__ __forceinline__ uint32_t buttons(int period) const
     {
         int a = period == 0 ? first : rest;
+        if constexpr (PLAN) {
+            a = rest;
+            if (period < depth) {                       // once per period: `period` divisions by a constant
+                uint32_t c = code;
+                for (int i = 0; i < period; i++) c /= (uint32_t)tbx_legal_count(GAME);
+                a = tbx_legal_action(GAME, (int)(c % (uint32_t)tbx_legal_count(GAME)));
+            }
+        }
         if (a < 0) a = tbx_legal_action(GAME, (int)(tbx_splitmix64(key ^ (t + (uint64_t)period)) % (uint64_t)tbx_legal_count(GAME)));
         return tbx_ale_buttons(a);
     }
@@ -606,6 +654,13 @@ struct TbxLookahead {
     // callers it masks the finished lanes.
     template <class Step, class Score, class Lives>
     __device__ __forceinline__ void run(double* out, Step&& step, Score&& score, Lives&& lives) const
+    {
+        const TbxLookFields f = run_fields(step, score, lives);
+        if (out) { out[0] = (double)f.ret; out[1] = (double)f.score; out[2] = (double)f.lives; out[3] = (double)f.frames_run; out[4] = (double)f.lost_at; }
+    }
+    // ... the same into registers (the search compares leaf after leaf and stores once)
+    template <class Step, class Score, class Lives>
+    __device__ __forceinline__ TbxLookFields run_fields(Step&& step, Score&& score, Lives&& lives) const
     {
         int prev = score();
         const int lives0 = lives();
@@ -625,7 +680,7 @@ struct TbxLookahead {
             run_frames = j + 1;
             if (lv <= 0) break;
         }
-        if (out) { out[0] = (double)ret; out[1] = (double)prev; out[2] = (double)lv; out[3] = (double)run_frames; out[4] = (double)lost_at; }
+        return TbxLookFields{ret, prev, lv, run_frames, lost_at};
     }
 };
 // a refused row: frames run = 0
@@ -643,6 +698,137 @@ void tbx_lookahead_launches(int n, int cands, F&& f)
     const long long pairs = (long long)n * cands;
     for (long long p0 = 0; p0 < pairs; p0 += TBX_LOOKAHEAD_PAIRS_PER_LAUNCH)
         f(p0, (int)(pairs - p0 < TBX_LOOKAHEAD_PAIRS_PER_LAUNCH ? pairs - p0 : TBX_LOOKAHEAD_PAIRS_PER_LAUNCH));
+}
+
+// ---- TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (include/toybox_amd.h).  A game hands in a policy G next to its lookahead kernel:
+//   G::GAME, G::WAVE (a wave per unit, else a thread), G::BLOCK, and
+//   TbxLookFields G::leaf(env, lane, look) const  -- load env from HBM, play `look` on the registers (run_fields), store nothing.
+
+// "x beats y": a total order once the code breaks the last tie, so the winner does not depend on how the leaves are cut up.
+// objective 0 (return): ret, lives, loss; objective 1 (survival): lives, loss, ret; larger wins, then the smaller code.
+__device__ __forceinline__ bool tbx_search_better(int objective, const TbxLookFields& x, uint32_t xcode, const TbxLookFields& y, uint32_t ycode)
+{
+    const int lx = x.lost_at < 0 ? TBX_LOOKAHEAD_MAX_FRAMES + 1 : x.lost_at, ly = y.lost_at < 0 ? TBX_LOOKAHEAD_MAX_FRAMES + 1 : y.lost_at;
+    if (objective == 0 && x.ret != y.ret) return x.ret > y.ret;
+    if (x.lives != y.lives) return x.lives > y.lives;
+    if (lx != ly) return lx > ly;
+    if (x.ret != y.ret) return x.ret > y.ret;
+    return xcode < ycode;
+}
+// a row of 6 doubles; `none`: no leaf behind it -- the final row of a refused env is zeros, a partial row carries code -1
+__device__ __forceinline__ void tbx_search_store(double* o, const TbxLookFields& f, uint32_t code, bool none, bool partial)
+{
+    o[0] = none ? 0.0 : (double)f.ret; o[1] = none ? 0.0 : (double)f.score; o[2] = none ? 0.0 : (double)f.lives;
+    o[3] = none ? 0.0 : (double)f.frames_run; o[4] = none ? 0.0 : (double)f.lost_at; o[5] = none ? (partial ? -1.0 : 0.0) : (double)code;
+}
+
+// TBX_QUERY_LOOKAHEAD_PLAN: the cands = 1 form of the lookahead kernels with the plan as the action source, a unit per env
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_plan_kernel(G g, TbxEditArgs a, int n, double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int env = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (env >= n) return;
+    double* const o = out + (size_t)env * 5;
+    TbxLookahead<G::GAME, true> look;
+    bool ok = look.read_plan(a, env, 0);
+    const double code = a.get(env, 3);
+    ok = ok && code >= 0.0 && code < (double)tbx_plan_count(G::GAME, ok ? look.depth : 0);
+    look.code = ok ? (uint32_t)code : 0u;
+    if (G::WAVE) ok = wave_uniform(ok);
+    if (!ok) {
+        if (!G::WAVE || lane == 0) tbx_lookahead_refuse(o);
+        return;
+    }
+    if (G::WAVE) look.uniform_plan();
+    const TbxLookFields f = g.leaf(env, lane, look);
+    if (!G::WAVE || lane == 0) { o[0] = (double)f.ret; o[1] = (double)f.score; o[2] = (double)f.lives; o[3] = (double)f.frames_run; o[4] = (double)f.lost_at; }
+}
+
+template <class G>
+void tbx_launch_plan(const G& g, const TbxEditArgs& a, int n, double* out_dev, hipStream_t s)
+{
+    const long long threads = (long long)n * (G::WAVE ? 64 : 1);
+    hipLaunchKernelGGL(tbx_plan_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, n, out_dev);
+}
+
+// TBX_QUERY_LOOKAHEAD_SEARCH: a unit is (env, first action, chunk), unit = (env * n_legal + cand) * chunks + chunk.  It walks the
+// suffix codes [chunk * S / chunks, (chunk + 1) * S / chunks) of its env's S = n_legal^(depth - 1) one after the other -- reload,
+// play, compare with the best so far (wave forms: in SGPRs) -- and stores ONE row: rows[unit], which with chunks = 1 is the
+// query's own output row, otherwise a partial row for tbx_search_pick_kernel.
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_search_kernel(G g, TbxEditArgs a, int chunks, long long first_unit, int count, double* __restrict__ rows)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const int lane = threadIdx.x & 63;
+    const int rel = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (rel >= count) return;
+    const long long unit = first_unit + rel;
+    int env = (int)(unit / (L * chunks));
+    const int r = (int)(unit - (long long)env * (L * chunks));
+    int cand = r / chunks, chunk = r - cand * chunks;
+    TbxLookahead<G::GAME, true> look;
+    bool ok = look.read_plan(a, env, 1);
+    int objective = a.n > 3 ? a.geti(env, 3) : 0;
+    ok = ok && look.depth >= 1 && (objective == 0 || objective == 1);
+    uint32_t S = ok ? (uint32_t)tbx_plan_count(G::GAME, look.depth - 1) : 0u;     // (depth <= TBX_PLAN_MAX_DEPTH: below 2^32)
+    ok = ok && (uint64_t)S * (uint64_t)L <= (uint64_t)TBX_LOOKAHEAD_MAX_PLANS;
+    if (G::WAVE) {
+        env = wave_uniform(env); cand = wave_uniform(cand); chunk = wave_uniform(chunk); objective = wave_uniform(objective);
+        ok = wave_uniform(ok); S = (uint32_t)wave_uniform((int)S);
+        look.uniform_plan();
+    }
+    TbxLookFields best{0, 0, 0, 0, 0};
+    uint32_t best_code = 0;
+    bool none = true;
+    if (ok) {
+        const uint32_t lo = (uint32_t)((uint64_t)chunk * S / (uint32_t)chunks), hi = (uint32_t)((uint64_t)(chunk + 1) * S / (uint32_t)chunks);
+        for (uint32_t sfx = lo; sfx < hi; sfx++) {
+            look.code = (uint32_t)cand + (uint32_t)L * sfx;
+            // every leaf RELOADS its env: with the index opaque the compiler cannot keep a second, pristine copy of the state in
+            // registers across the loop (it did: Amidar 85 -> 132 VGPRs, two waves of occupancy) -- the reload hits L2
+            int env_now = env;
+            if (G::WAVE) asm volatile("" : "+s"(env_now));
+            else asm volatile("" : "+v"(env_now));
+            const TbxLookFields f = g.leaf(env_now, lane, look);
+            if (none || tbx_search_better(objective, f, look.code, best, best_code)) { best = f; best_code = look.code; none = false; }
+        }
+    }
+    if (!G::WAVE || lane == 0) tbx_search_store(rows + unit * 6, best, best_code, none, chunks > 1);
+}
+
+template <class G>
+void tbx_launch_search(const G& g, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s)
+{
+    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_search_launches: below 2^30)
+    const long long threads = count * (G::WAVE ? 64 : 1);
+    hipLaunchKernelGGL(tbx_search_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, chunks, per_env * first_env, (int)count, rows);
+}
+
+// How many chunks a search is cut into: a power of two, the smallest that brings (env, first action, chunk) units to
+// TBX_SEARCH_FILL_WAVES waves -- one per SIMD of an MI355X (256 CUs x 4) -- and at most `suffixes` (the largest power of two
+// below it; per-env rows: the suffixes of the deepest tree TBX_LOOKAHEAD_MAX_PLANS allows, a shallower env leaves chunks empty).
+// lanes: 64 where a wave is the unit, 1 where a thread is.
+constexpr long long TBX_SEARCH_FILL_WAVES = 1024;
+inline int tbx_search_chunks(int n, int legal, long long suffixes, int lanes)
+{
+    const long long want = TBX_SEARCH_FILL_WAVES * (64 / lanes);
+    int chunks = 1;
+    while ((long long)n * legal * chunks < want && 2ll * chunks <= suffixes) chunks *= 2;
+    return chunks;
+}
+// One launch of a search plays at most this many leaf-frames (plans x frames), so that a single kernel on a shared card stays
+// near half a second: profiles/search.md has the rate behind the number.
+constexpr long long TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH = 1ll << 31;
+// f(first_env, envs) per launch: env ranges under the leaf-frame budget and under TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units;
+// leaf_frames_per_env: plans x frames of one env (per-env rows: the largest a valid row can ask for)
+template <class F>
+void tbx_search_launches(int n, long long units_per_env, long long leaf_frames_per_env, F&& f)
+{
+    long long step = TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH / leaf_frames_per_env;
+    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
+    if (step < 1) step = 1;
+    for (long long e0 = 0; e0 < n; e0 += step) f((int)e0, (int)(n - e0 < step ? n - e0 : step));
 }
 
 // One per-env array of an engine as the env-copy kernels see it (envcopy.hip: fork, checkpoint save and restore) -- `fields`
@@ -825,6 +1011,11 @@ struct GameOps {
     // TBX_QUERY_LOOKAHEAD (cands = 1, the first action from the arguments) / _ALL (cands = the game's legal count): one launch over
     // the (env, candidate) pairs, out_dev[env][candidate][5]; the arguments' shared values are already checked (engine.hip)
     virtual int lookahead(tbx_engine* e, const TbxEditArgs&, bool /*all*/, double* /*out_dev*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    // TBX_QUERY_LOOKAHEAD_PLAN: tbx_plan_kernel over every env.  TBX_QUERY_LOOKAHEAD_SEARCH: tbx_search_kernel over the units of envs
+    // [first_env, first_env + envs), rows[unit]; search_lanes(): the lanes one unit takes in the form the engine is in (64 or 1)
+    virtual int lookahead_plan(tbx_engine* e, const TbxEditArgs&, double* /*out_dev*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    virtual int lookahead_search(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    virtual int search_lanes() const { return 64; }
     // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
     // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The
     // engine adds sim_rng, prev_score and the agent layer and runs the copy.  Listing changes nothing; a copy that WROTE live

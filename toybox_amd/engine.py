@@ -110,6 +110,100 @@ def lookahead_args(n_envs, frames, hold=1, first=None, rest=None, seed=0, t=0, e
     return args, True
 
 
+SEARCH_OBJECTIVES = {"return": 0, "survival": 1}
+
+
+def _game_name(game):
+    return game if isinstance(game, str) else _abi.GAME_NAMES[int(game)]
+
+
+def plan_code(game, actions):
+    """ALE action ids [..., depth] -> plan codes [...] (uint64): code = sum of digit_p * n_legal ** p, digit_p the index of action p
+    in the game's legal set, action 0 the first played.  An action outside the legal set or a depth beyond PLAN_MAX_DEPTH raises."""
+    game = _game_name(game)
+    legal = np.asarray(_abi.LEGAL_ACTIONS[game], np.int64)
+    a = np.asarray(actions, np.int64)
+    if a.ndim < 1 or a.shape[-1] > _abi.PLAN_MAX_DEPTH[game]:
+        raise ValueError("a plan is [..., depth] action ids with depth 0 .. %d, got shape %r" % (_abi.PLAN_MAX_DEPTH[game], a.shape))
+    if not np.isin(a, legal).all():
+        raise ValueError("a plan holds an action outside the legal set %r of %s" % (tuple(legal), game))
+    digits = np.searchsorted(legal, a).astype(np.uint64)
+    code = np.zeros(a.shape[:-1], np.uint64)
+    for p in range(a.shape[-1] - 1, -1, -1):
+        code = code * np.uint64(len(legal)) + digits[..., p]
+    return code
+
+
+def plan_digits(n_legal, code, depth):
+    """plan codes [...] -> their digits [..., depth] (int64): indices into the legal set, digit 0 first"""
+    c = np.asarray(code).astype(np.uint64)
+    out = np.empty(c.shape + (int(depth),), np.int64)
+    for p in range(int(depth)):
+        out[..., p] = (c % np.uint64(n_legal)).astype(np.int64)
+        c = c // np.uint64(n_legal)
+    return out
+
+
+def plan_actions(game, code, depth):
+    """plan codes [...] -> ALE action ids [..., depth] (int64), the inverse of plan_code"""
+    game = _game_name(game)
+    legal = np.asarray(_abi.LEGAL_ACTIONS[game], np.int64)
+    if not 0 <= int(depth) <= _abi.PLAN_MAX_DEPTH[game]:
+        raise ValueError("plan depth must be 0 .. %d, got %r" % (_abi.PLAN_MAX_DEPTH[game], depth))
+    c = np.asarray(code)
+    if c.size and (c.min() < 0 or int(c.max()) >= len(legal) ** int(depth)):
+        raise ValueError("plan codes of depth %d are 0 .. %d" % (depth, len(legal) ** int(depth) - 1))
+    return legal[plan_digits(len(legal), c, depth)]
+
+
+def _plan_rows(what, game, n_envs, frames, hold, depth, col3, rest, seed, t, env_offset):
+    """columns {frames, hold, depth, code | objective, rest, seed_lo, seed_hi, t, env_offset}: lookahead_args with `first` set
+    aside, then depth and column 3 put in"""
+    game = _game_name(game)
+    for name, c in (("depth", depth), (what, col3)):
+        if np.ndim(c) > 1 or (np.ndim(c) == 1 and len(c) != int(n_envs)):
+            raise ValueError("lookahead %s is a scalar or one value per env (%d), got shape %r" % (name, n_envs, np.shape(c)))
+    if rest is not None and not np.ndim(rest) and int(rest) != -1 and int(rest) not in _abi.LEGAL_ACTIONS[game]:
+        raise ValueError("lookahead rest must be None, -1 or one of %r, got %r" % (_abi.LEGAL_ACTIONS[game], rest))
+    base, per_env = lookahead_args(n_envs, frames, hold, None, rest, seed, t, env_offset)
+    if not per_env and not np.ndim(depth) and not np.ndim(col3):
+        return [base[0], base[1], float(depth), float(col3)] + base[3:], False
+    args = np.empty((int(n_envs), 9), np.float64)
+    args[:, [0, 1, 4, 5, 6, 7, 8]] = np.asarray(base, np.float64)[..., [0, 1, 3, 4, 5, 6, 7]]
+    args[:, 2] = np.asarray(depth, np.float64)
+    args[:, 3] = np.asarray(col3, np.float64)
+    return args, True
+
+
+def plan_args(game, n_envs, frames, hold=1, depth=0, code=0, rest=None, seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD_PLAN: columns {frames, hold, depth, code, rest, seed_lo, seed_hi, t, env_offset};
+    (args, per_env) as lookahead_args gives them.  Shared values are range-checked here (ValueError): depth 0 .. PLAN_MAX_DEPTH,
+    code 0 .. n_legal ** depth - 1, rest None / -1 / a legal action; per-env rows are left to the device (a bad row answers zeros)."""
+    name = _game_name(game)
+    if not np.ndim(depth):
+        if not 0 <= int(depth) <= _abi.PLAN_MAX_DEPTH[name]:
+            raise ValueError("plan depth must be 0 .. %d, got %r" % (_abi.PLAN_MAX_DEPTH[name], depth))
+        if not np.ndim(code) and not 0 <= int(code) < len(_abi.LEGAL_ACTIONS[name]) ** int(depth):
+            raise ValueError("plan code must be 0 .. n_legal ** depth - 1, got %r at depth %r" % (code, depth))
+    return _plan_rows("code", name, n_envs, frames, hold, depth, code, rest, seed, t, env_offset)
+
+
+def search_args(game, n_envs, frames, hold=1, depth=1, objective=0, rest=None, seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD_SEARCH: columns {frames, hold, depth, objective, rest, seed_lo, seed_hi, t,
+    env_offset}; objective 0 / "return" or 1 / "survival".  Shared values are range-checked here (ValueError): depth >= 1 with
+    n_legal ** depth <= LOOKAHEAD_MAX_PLANS; per-env rows are left to the device."""
+    name = _game_name(game)
+    if isinstance(objective, str):
+        if objective not in SEARCH_OBJECTIVES:
+            raise ValueError("search objective is 'return' or 'survival', got %r" % (objective,))
+        objective = SEARCH_OBJECTIVES[objective]
+    if not np.ndim(objective) and int(objective) not in (0, 1):
+        raise ValueError("search objective is 0 (return) or 1 (survival), got %r" % (objective,))
+    if not np.ndim(depth) and not (int(depth) >= 1 and len(_abi.LEGAL_ACTIONS[name]) ** int(depth) <= _abi.LOOKAHEAD_MAX_PLANS):
+        raise ValueError("search depth must be at least 1 with n_legal ** depth <= %d, got %r" % (_abi.LOOKAHEAD_MAX_PLANS, depth))
+    return _plan_rows("objective", name, n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
+
+
 class Engine:
     def __init__(self, game, n_envs=1, device=0, config=None, lib=None):
         self._lib = lib if lib is not None else load()
@@ -377,6 +471,38 @@ class Engine:
         arrays shaped [N, n_legal]."""
         args, _ = lookahead_args(self.n_envs, frames, hold, None, rest, seed, t, env_offset)
         return self._lookahead_dict(self.reduce(_abi.QUERY_LOOKAHEAD_ALL, args).reshape(self.n_envs, len(self.legal_actions), 5))
+
+    def lookahead_plan(self, frames, plan, hold=1, rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_PLAN: lookahead() under an action sequence -- plan: ALE action ids [depth] (shared) or [N, depth],
+        action p held for period p (`hold` frames), `rest` after the last.  The same dict of five [N] arrays."""
+        plan = np.asarray(plan, np.int64)
+        if plan.ndim not in (1, 2) or (plan.ndim == 2 and plan.shape[0] != self.n_envs):
+            raise ValueError("plan is [depth] or [%d, depth] action ids, got shape %r" % (self.n_envs, plan.shape))
+        code = plan_code(self.game, plan)
+        args, _ = plan_args(self.game, self.n_envs, frames, hold, plan.shape[-1], code if plan.ndim == 2 else int(code), rest, seed, t, env_offset)
+        return self._lookahead_dict(self.reduce(_abi.QUERY_LOOKAHEAD_PLAN, args))
+
+    def lookahead_search(self, frames, depth, hold=1, objective="return", rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_SEARCH: all n_legal ** depth plans of every env played on the device; for each first action a
+        (self.legal_actions order) the best plan that begins with it under `objective` ("return": ret, lives, the later first
+        life loss; "survival": lives, the later loss, ret; ties to the smaller code).  The five lookahead() fields [N, n_legal]
+        plus code [N, n_legal] (uint64) and plan [N, n_legal, depth] (ALE ids; per-env depths: the largest, unused periods -1)."""
+        args, per_env = search_args(self.game, self.n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
+        L = len(self.legal_actions)
+        out = self.reduce(_abi.QUERY_LOOKAHEAD_SEARCH, args).reshape(self.n_envs, L, 6)
+        res = self._lookahead_dict(out[..., :5])
+        res["code"] = out[..., 5].astype(np.uint64)
+        d = np.broadcast_to(np.clip(np.asarray(depth, np.int64), 0, _abi.PLAN_MAX_DEPTH[self.game]), (self.n_envs,))
+        width = int(d.max()) if self.n_envs else 0
+        plan = np.asarray(self.legal_actions, np.int64)[plan_digits(L, res["code"], width)]
+        plan[np.broadcast_to(np.arange(width) >= d[:, None, None], plan.shape)] = -1
+        res["plan"] = plan
+        return res
+
+    @property
+    def search_chunks(self):
+        """into how many chunks the last lookahead_search cut every (env, first action) group of plans (0: none yet)"""
+        return self.get_option(_abi.OPT_SEARCH_CHUNKS)
 
     @staticmethod
     def _lookahead_dict(out):

@@ -75,6 +75,36 @@ def _lookahead(env, frames, hold, first, rest, all_actions, seed, t):
     return env.engine.lookahead(frames, hold=hold, first=ale(first), rest=ale(rest), seed=seed, t=t)
 
 
+def _ale(env, a):
+    if a is None:
+        return None
+    a = np.asarray(a, np.int64)
+    if a.size and (a.min() < 0 or a.max() >= len(env._action_set)):
+        raise AssertionError("action index out of range")
+    return env._lut[a] if a.ndim else int(env._lut[a])
+
+
+def _lookahead_plan(env, frames, hold, plan, rest, seed, t):
+    """Engine.lookahead_plan for an adapter: plan [depth] or [num_envs, depth] action indices -> ALE ids"""
+    return env.engine.lookahead_plan(frames, _ale(env, np.asarray(plan, np.int64)), hold=hold, rest=_ale(env, rest), seed=seed, t=t)
+
+
+def _search(env, frames, hold, depth, objective, rest, seed, t):
+    """Engine.lookahead_search for an adapter: `plan` comes back as action indices (the digits of the code: the action set is the
+    engine's legal set in its order), and the winner among an env's rows under the same objective -- ties to the smaller code --
+    is added as best_action [num_envs] and best_plan [num_envs, depth]"""
+    from ..engine import plan_digits
+    out = env.engine.lookahead_search(frames, int(depth), hold=hold, objective=objective, rest=_ale(env, rest), seed=seed, t=t)
+    out["plan"] = plan_digits(len(env._action_set), out["code"], int(depth))
+    loss = np.where(out["life_lost_at"] < 0, 1 << 30, out["life_lost_at"])
+    keys = (out["ret"], out["lives"], loss) if objective in ("return", 0) else (out["lives"], loss, out["ret"])
+    # np.lexsort: the last key is the primary one; ascending, so larger-is-better keys are negated
+    order = np.lexsort((out["code"].astype(np.int64),) + tuple(-np.asarray(k, np.float64) for k in reversed(keys)), axis=1)
+    out["best_action"] = order[:, 0].astype(np.int64)
+    out["best_plan"] = out["plan"][np.arange(out["plan"].shape[0]), out["best_action"]]
+    return out
+
+
 def _fork_map(n, src, envs):
     """(src int[N], selected bool[N]) of a fork: src an int (one source fanned out) or one index per env; envs None (every
     env), a boolean mask or indices.  Unselected envs name themselves."""
@@ -249,6 +279,23 @@ class ToyboxVecEnv:
         if self._in_flight is not None or self._pending is not None:
             self.step_wait()
         return _lookahead(self, int(steps), 1, first, rest, all_actions, seed, t)
+
+    def lookahead_plan(self, steps, plan, rest=None, seed=0, t=0):
+        """lookahead() under an action sequence (Engine.lookahead_plan): plan [depth] or [num_envs, depth] action indices, action p
+        in step p, `rest` in the steps after the last.  The same dict of five."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _lookahead_plan(self, int(steps), 1, plan, rest, seed, t)
+
+    def search(self, steps, depth, objective="return", rest=None, seed=0, t=0):
+        """Every action sequence of `depth` steps, followed by `rest`, played `steps` steps ahead on the device without taking
+        them (Engine.lookahead_search): for each first action index the best plan under objective "return" or "survival" -- ret,
+        score, lives, frames_run, life_lost_at, code [num_envs, n_actions], plan [num_envs, n_actions, depth] (action indices) --
+        and the winner among them, best_action [num_envs] and best_plan [num_envs, depth].  Nothing is touched; a pending
+        step_async ends first, as in lookahead()."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _search(self, int(steps), 1, depth, objective, rest, seed, t)
 
     def get_images(self):
         return self.engine.render(3)
@@ -564,6 +611,20 @@ class ToyboxPreprocVecEnv:
         if self._in_flight is not None:
             self.step_wait()
         return _lookahead(self, int(steps) * self._skip, self._skip, first, rest, all_actions, seed, t)
+
+    def lookahead_plan(self, steps, plan, rest=None, seed=0, t=0):
+        """lookahead() under an action sequence (Engine.lookahead_plan): plan [depth] or [num_envs, depth] action indices, action p
+        held for the skip frames of agent step p, `rest` in the steps after the last.  Raw frames, no wrapper, as in lookahead()."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _lookahead_plan(self, int(steps) * self._skip, self._skip, plan, rest, seed, t)
+
+    def search(self, steps, depth, objective="return", rest=None, seed=0, t=0):
+        """ToyboxVecEnv.search in agent steps: steps x skip raw frames, every action held for skip frames; raw frames, no wrapper,
+        as in lookahead().  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _search(self, int(steps) * self._skip, self._skip, depth, objective, rest, seed, t)
 
     def close(self):
         if not self.closed:

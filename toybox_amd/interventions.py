@@ -230,6 +230,33 @@ class BatchIntervention:
         """Engine.lookahead_all over the range: the same dict, each [count, n_legal]"""
         return self._lookahead(True, frames, hold, None, rest, seed, t, env_offset)
 
+    def _full(self, c, fill):
+        """a per-env column of the range as a column of the whole engine"""
+        if c is None or not np.ndim(c):
+            return c
+        full = np.full((self.engine.n_envs,) + np.shape(c)[1:], fill, np.asarray(c).dtype)
+        full[self.first:self.first + self.count] = c
+        return full
+
+    def lookahead_plan(self, frames, plan, hold=1, rest=None, seed=0, t=0, env_offset=0):
+        """Engine.lookahead_plan over the range: plan [depth] or [count, depth] ALE ids; the dict of five, each [count]"""
+        self._flush()
+        plan = np.asarray(plan, np.int64)
+        if plan.ndim == 2:                                   # (the envs outside the range play the first legal action: thrown away)
+            plan = self._full(plan, self.engine.legal_actions[0])
+        out = self.engine.lookahead_plan(self._full(frames, 1), plan, hold=self._full(hold, 1), rest=self._full(rest, -1), seed=self._full(seed, 0),
+                                         t=self._full(t, 0), env_offset=self._full(env_offset, 0))
+        return {k: v[self.first:self.first + self.count] for k, v in out.items()}
+
+    def lookahead_search(self, frames, depth, hold=1, objective="return", rest=None, seed=0, t=0, env_offset=0):
+        """Engine.lookahead_search over the range: the five fields and code [count, n_legal], plan [count, n_legal, depth]"""
+        self._flush()
+        if np.ndim(objective):
+            objective = self._full(objective, 0)
+        out = self.engine.lookahead_search(self._full(frames, 1), self._full(depth, 1), hold=self._full(hold, 1), objective=objective,
+                                           rest=self._full(rest, -1), seed=self._full(seed, 0), t=self._full(t, 0), env_offset=self._full(env_offset, 0))
+        return {k: v[self.first:self.first + self.count] for k, v in out.items()}
+
     # ================================================================== BreakoutIntervention (interventions/breakout.py)
     def num_bricks_remaining(self):
         """:309-310 -> int[N]"""
