@@ -684,6 +684,30 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
 #define TBX_PLAN_MAX_DEPTH(game) ((game) == TBX_GAME_BREAKOUT ? 16 : (game) == TBX_GAME_GRIDWORLD ? 13 : 12)
 #define TBX_QUERY_LOOKAHEAD_PLAN   152  /* {frames, hold, depth, code, rest, seed_lo, seed_hi, t, env_offset} -> 5 */
 #define TBX_QUERY_LOOKAHEAD_SEARCH 153  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset} -> 6 * n_legal(game) */
+/* Sampled lookahead: `samples` futures per env and legal action, summed on the device.  The columns stand where those of
+ * TBX_QUERY_LOOKAHEAD_SEARCH stand, `samples` for depth and `salt` for the objective.  Trailing arguments may be left out: hold 1,
+ * samples 1, salt 0, rest -1, seed 0, t 0, env_offset 0.
+ *   For every env and every legal action a (legal-set order, as above) future s = 0 .. samples-1 is exactly
+ *   TBX_QUERY_LOOKAHEAD {frames, hold, first = legal[a], rest, seed_s, t, env_offset} played from the env's state with its game RNG
+ *   salted by salt_s:
+ *     seed_s = splitmix64((seed + s) mod 2^64)  (not seed + s: the draw key is seed ^ (env << 32) ^ (t + p), so neighbouring seeds
+ *       would permute one another's draws across periods);
+ *     salt_s = salt == 0 ? 0 : salt + s.  salt_s == 0: the game RNG is taken as it stands; otherwise both words of the game's
+ *       `rand` become splitmix64(word ^ salt_s) -- the rule of TBX_EDIT_COPY_ENV's salt, applied in registers after the load and
+ *       never stored.  GridWorld has no game RNG and ignores the salt.  The simulator RNG is not read by a lookahead.
+ *   The run, the stop after the first frame with lives <= 0, no auto-reset, no wrapper, "nothing in the engine changes": the
+ *   lookahead's.
+ *   Out, row out[env][a][0 .. 7], every field an integer summed in 64-bit integers and converted to binary64 once at the store (so
+ *   the row does not depend on how the samples are cut into chunks and launches): [0] samples = futures played (0: the row was
+ *   refused); [1] ret_sum = sum of the futures' return -- exact while it stays below 2^53, which any score reachable by play keeps;
+ *   [2] ret_min and [3] ret_max = the smallest and the largest return; [4] lives_sum = sum of lives after the last frame run;
+ *   [5] lost = futures with life lost at >= 0; [6] ended = futures that ended with lives <= 0; [7] safe_frames_sum = sum of
+ *   (life lost at < 0 ? frames run : life lost at).
+ *   TBX_E_INVALID, nothing launched: a shared value out of the lookahead's ranges (frames, hold, rest), samples outside
+ *   1 .. TBX_LOOKAHEAD_MAX_SAMPLES, salt < 0 or above 2^32 - 1, salt > 0 with salt + samples - 1 >= 2^32, more than 9 arguments.
+ *   In per-env rows such an env's whole output is zeros -- field 0 = 0 -- and the other envs are answered. */
+#define TBX_LOOKAHEAD_MAX_SAMPLES 4096
+#define TBX_QUERY_LOOKAHEAD_SAMPLES 154  /* {frames, hold, samples, salt, rest, seed_lo, seed_hi, t, env_offset} -> 8 * n_legal(game) */
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);
@@ -981,6 +1005,8 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
 #define TBX_OPT_ROLLOUT_CHUNKS_ACTIVE 104
 /* read-only: into how many chunks the last TBX_QUERY_LOOKAHEAD_SEARCH cut every (env, first action) group of plans (0: none yet) */
 #define TBX_OPT_SEARCH_CHUNKS 105
+/* read-only: into how many chunks the last TBX_QUERY_LOOKAHEAD_SAMPLES cut the samples of every (env, first action) group (0: none yet) */
+#define TBX_OPT_SAMPLE_CHUNKS 106
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
 /* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could

@@ -1286,15 +1286,17 @@ __global__ __launch_bounds__(TBX_BLOCK) void ami_lookahead_kernel(AmiDev d, TbxE
              [&] { return wave_uniform(s.f[A_SCORE]); }, [&] { return wave_uniform(s.f[A_LIVES]); });
 }
 
-// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (tbx_plan_kernel, tbx_search_kernel): a wave per unit, the plan as the action source
+// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH / _SAMPLES (tbx_plan_kernel, tbx_search_kernel, tbx_sample_kernel): a wave per unit, the plan as the
+// action source; salt: the game RNG of a sampled future (tbx_salt_rng)
 struct AmiLook {
     static constexpr int GAME = TBX_GAME_AMIDAR, BLOCK = TBX_BLOCK;
     static constexpr bool WAVE = true;
     AmiDev d;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look) const
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look, uint64_t salt = 0) const
     {
         AmiRegs s;
         ami_load(d, env, lane, s);
+        tbx_salt_rng(s.rng, salt);
         return look.run_fields([&](uint32_t buttons) { ami_step(*d.tab, lane, (uint32_t)wave_uniform((int)buttons), s); },
                                [&] { return wave_uniform(s.f[A_SCORE]); }, [&] { return wave_uniform(s.f[A_LIVES]); });
     }
@@ -2296,6 +2298,12 @@ struct AmiOps : GameOps {
     int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
     {
         tbx_launch_search(AmiLook{d}, a, chunks, first_env, envs, rows, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        tbx_launch_sample(AmiLook{d}, a, chunks, first_env, envs, rows, s);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

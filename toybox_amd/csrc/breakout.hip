@@ -975,18 +975,20 @@ __global__ __launch_bounds__(TBX_BLOCK) void brk_lookahead_kernel(BrkDev d, BrkC
              [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.lives); });
 }
 
-// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (tbx_plan_kernel, tbx_search_kernel): the same two forms with the plan as the action source.
+// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH / _SAMPLES (tbx_plan_kernel, tbx_search_kernel, tbx_sample_kernel): the same two forms with the
+// plan as the action source; salt: the game RNG of a sampled future (tbx_salt_rng).
 // A thread per unit on the canonical wall ...
 struct BrkTLook {
     static constexpr int GAME = TBX_GAME_BREAKOUT, BLOCK = 128;
     static constexpr bool WAVE = false;
     BrkDev d;
     const BrkCfg* cp;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int, const TbxLookahead<GAME, true>& look) const
+    __device__ __forceinline__ TbxLookFields leaf(int env, int, const TbxLookahead<GAME, true>& look, uint64_t salt = 0) const
     {
         const BrkCfg& c = *cp;
         BrkT s;
         t_load(d, env, s);
+        tbx_salt_rng(s.rng, salt);
         return look.run_fields([&](uint32_t buttons) { brk_t_step(c, s, buttons); }, [&] { return s.score; }, [&] { return s.lives; });
     }
 };
@@ -997,10 +999,11 @@ struct BrkWaveLook {
     static constexpr bool WAVE = true;
     BrkDev d;
     BrkCfg c;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look) const
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look, uint64_t salt = 0) const
     {
         BrkRegs s;
         brk_load(d, env, lane, s);
+        tbx_salt_rng(s.rng, salt);
         return look.run_fields([&](uint32_t buttons) { brk_wave_frame<CUSTOM>(d, c, env, lane, (uint32_t)wave_uniform((int)buttons), s); },
                                [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.lives); });
     }
@@ -2429,6 +2432,13 @@ struct BreakoutOps : GameOps {
     {
         if (!custom && use_tpe) tbx_launch_search(BrkTLook{d, cfg_dev}, a, chunks, first_env, envs, rows, s);
         else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_search(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, chunks, first_env, envs, rows, s); });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        if (!custom && use_tpe) tbx_launch_sample(BrkTLook{d, cfg_dev}, a, chunks, first_env, envs, rows, s);
+        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_sample(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, chunks, first_env, envs, rows, s); });
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

@@ -309,7 +309,7 @@ int tbx_destroy(tbx_engine* e)
     }
     pipe_free(e);
     hipFree(e->actions);
-    e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
+    e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); e->sample_parts.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
     hipFree(e->mask); hipFree(e->err_flag); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
     if (e->io_host) hipHostFree(e->io_host);
     if (e->scal_host) hipHostFree(e->scal_host);
@@ -1149,6 +1149,7 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_LOOKAHEAD_ALL: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_PLAN: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
     default: return TBX_E_INVALID;
     }
 }
@@ -1243,6 +1244,63 @@ static int lookahead_plans(tbx_engine* e, int query, const TbxEditArgs& a, doubl
     return TBX_OK;
 }
 
+// chunks > 1: the sum of the partial rows parts[group][chunks][8] (64-bit integers; fields 2 / 3: the smallest / the largest) of
+// every (env, first action) group of envs from first_env on; a group without a sample (a refused row) answers zeros
+__global__ __launch_bounds__(256) void tbx_sample_sum_kernel(const long long* __restrict__ parts, int chunks, long long first_group, int count, double* __restrict__ out)
+{
+    const int rel = blockIdx.x * 256 + threadIdx.x;
+    if (rel >= count) return;
+    const long long group = first_group + rel;
+    const long long* p = parts + group * chunks * 8;
+    TbxSampleSums sum;
+    for (int c = 0; c < chunks; c++, p += 8) sum.merge(p);
+    sum.store(out + group * 8);
+}
+
+// TBX_QUERY_LOOKAHEAD_SAMPLES: shared values are refused here, before anything is launched; per-env rows are met by the kernel.
+// Cut into chunks and launches as the search is, with the samples of a group where the search has its suffixes.
+static int lookahead_samples(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s)
+{
+    const int L = tbx_legal_count(e->game);
+    if (a.n < 1 || a.n > 9) return e->fail(TBX_E_INVALID, "samples takes {frames[, hold, samples, salt, rest, seed_lo, seed_hi, t, env_offset]}");
+    long long samples = TBX_LOOKAHEAD_MAX_SAMPLES, frames = TBX_LOOKAHEAD_MAX_FRAMES;      // per-env rows: the most a valid row can ask for
+    if (!a.per_env) {
+        auto playable = [&](double v) {
+            if (v == -1.0) return true;
+            for (int i = 0; i < L; i++)
+                if (v == (double)tbx_legal_action(e->game, i)) return true;
+            return false;
+        };
+        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        const double count = a.n > 2 ? a.v[2] : 1.0, salt = a.n > 3 ? a.v[3] : 0.0;
+        if (!(count >= 1.0 && count <= (double)TBX_LOOKAHEAD_MAX_SAMPLES)) return e->fail(TBX_E_INVALID, "samples: samples must be 1 .. TBX_LOOKAHEAD_MAX_SAMPLES");
+        samples = TbxEditArgs::to_int(count);
+        if (!(salt >= 0.0 && salt < 4294967296.0)) return e->fail(TBX_E_INVALID, "samples: salt must be 0 .. 2^32 - 1");
+        if ((uint64_t)salt != 0 && (uint64_t)salt + (uint64_t)samples - 1 >= (1ull << 32)) return e->fail(TBX_E_INVALID, "samples: salt + samples - 1 must stay below 2^32");
+        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        frames = TbxEditArgs::to_int(a.v[0]);
+    }
+    const int chunks = tbx_search_chunks(e->n, L, samples, e->ops->search_lanes());
+    double* rows = out_dev;
+    if (chunks > 1) {
+        EHIP(e->sample_parts.reserve(sizeof(double) * 8 * (size_t)e->n * (size_t)L * (size_t)chunks, e->stream, s));
+        rows = e->sample_parts.p;
+    }
+    e->sample_chunks = chunks;
+    int rc = TBX_OK;
+    tbx_search_launches(e->n, (long long)L * chunks, samples * frames, [&](int env0, int envs) {
+        if (rc) return;
+        rc = e->ops->lookahead_sample(e, a, chunks, env0, envs, rows, s);
+        if (rc || chunks == 1) return;
+        const int groups = envs * L;
+        hipLaunchKernelGGL(tbx_sample_sum_kernel, dim3((groups + 255) / 256), dim3(256), 0, s, reinterpret_cast<const long long*>(rows), chunks, (long long)env0 * L, groups, out_dev);
+    });
+    if (rc) return rc;
+    EHIP(hipGetLastError());
+    return TBX_OK;
+}
+
 // the queries every game has (the engine's own), else the game's
 static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s)
 {
@@ -1264,6 +1322,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
         return e->ops->lookahead(e, a, query == TBX_QUERY_LOOKAHEAD_ALL, out_dev, s);
     }
     if (query == TBX_QUERY_LOOKAHEAD_PLAN || query == TBX_QUERY_LOOKAHEAD_SEARCH) return lookahead_plans(e, query, a, out_dev, s);
+    if (query == TBX_QUERY_LOOKAHEAD_SAMPLES) return lookahead_samples(e, a, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     return checkpoint_valid(e, a, out_dev, s);
 }
@@ -1436,6 +1495,7 @@ int tbx_get_option(tbx_engine* e, int option, int* value_out)
     if (value_out && option == TBX_OPT_FUSED_OVERLAP_ACTIVE) { *value_out = fused_overlap_on(e, nullptr, 3) ? 1 : 0; return TBX_OK; }
     if (value_out && option == TBX_OPT_ROLLOUT_CHUNKS_ACTIVE) { *value_out = rollout_chunks_on(e, 3) ? 1 : 0; return TBX_OK; }
     if (value_out && option == TBX_OPT_SEARCH_CHUNKS) { *value_out = e->search_chunks; return TBX_OK; }
+    if (value_out && option == TBX_OPT_SAMPLE_CHUNKS) { *value_out = e->sample_chunks; return TBX_OK; }
     if (option < 0 || option >= TBX_OPT_COUNT || !value_out) return e->fail(TBX_E_INVALID, "unknown option");
     *value_out = e->opt[option];
     return TBX_OK;

@@ -225,7 +225,7 @@ struct GwLook {
     static constexpr int GAME = TBX_GAME_GRIDWORLD, BLOCK = TBX_BLOCK;
     static constexpr bool WAVE = true;
     GwDev d;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look) const
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look, uint64_t /*salt: no game RNG*/ = 0) const
     {
         __shared__ uint32_t boards[TBX_WAVES_PER_BLOCK][CELLS / 4];
         uint32_t* const mine = boards[wave_uniform((int)(threadIdx.x >> 6))];
@@ -799,6 +799,12 @@ struct GridWorldOps : GameOps {
     int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
     {
         tbx_launch_search(GwLook{d}, a, chunks, first_env, envs, rows, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        tbx_launch_sample(GwLook{d}, a, chunks, first_env, envs, rows, s);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

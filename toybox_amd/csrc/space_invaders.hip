@@ -856,16 +856,18 @@ __global__ __launch_bounds__(TBX_BLOCK) void si_lookahead_kernel(SiDev d, SiCfg 
              [&] { return wave_uniform(s.f[F_SCORE]); }, [&] { return wave_uniform(s.f[F_LIVES]); });
 }
 
-// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (tbx_plan_kernel, tbx_search_kernel): a wave per unit, the full load, the plan as the action source
+// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH / _SAMPLES (tbx_plan_kernel, tbx_search_kernel, tbx_sample_kernel): a wave per unit, the full load,
+// the plan as the action source; salt: the game RNG of a sampled future (tbx_salt_rng)
 struct SiLook {
     static constexpr int GAME = TBX_GAME_SPACE_INVADERS, BLOCK = TBX_BLOCK;
     static constexpr bool WAVE = true;
     SiDev d;
     SiCfg c;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look) const
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look, uint64_t salt = 0) const
     {
         SiRegs s;
         si_load(d, env, lane, s);
+        tbx_salt_rng(s.rng, salt);
         return look.run_fields([&](uint32_t buttons) { si_step(c, lane, (uint32_t)wave_uniform((int)buttons), s); },
                                [&] { return wave_uniform(s.f[F_SCORE]); }, [&] { return wave_uniform(s.f[F_LIVES]); });
     }
@@ -2223,6 +2225,12 @@ struct SiOps : GameOps {
     int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
     {
         tbx_launch_search(SiLook{d, c}, a, chunks, first_env, envs, rows, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
+    int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        tbx_launch_sample(SiLook{d, c}, a, chunks, first_env, envs, rows, s);
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

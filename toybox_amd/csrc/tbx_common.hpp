@@ -449,6 +449,8 @@ struct tbx_engine {
     TbxDevBuf<double> reduce_out;   // [N][width] result staging of tbx_reduce
     TbxDevBuf<double> search_parts; // [N][n_legal][chunks][6] partial rows of TBX_QUERY_LOOKAHEAD_SEARCH cut into chunks
     int search_chunks = 0;          // chunks of the last TBX_QUERY_LOOKAHEAD_SEARCH (0: none yet)
+    TbxDevBuf<double> sample_parts; // [N][n_legal][chunks][8] partial rows of TBX_QUERY_LOOKAHEAD_SAMPLES cut into chunks (64-bit integers)
+    int sample_chunks = 0;          // chunks of the last TBX_QUERY_LOOKAHEAD_SAMPLES (0: none yet)
     TbxDevBuf<void> staging;        // device POD staging for get/set state
     struct TbxEnvCopy* envcopy = nullptr;   // TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*: the fork's scratch copy, the checkpoint store (envcopy.hip), made on first use
     GameOps* ops = nullptr;
@@ -634,6 +636,22 @@ struct TbxLookahead {
     {
         uniform();
         depth = wave_uniform(depth); code = (uint32_t)wave_uniform((int)code);
+    }
+    // SAMPLES, {frames, hold, samples, salt, rest, seed_lo, seed_hi, t, env_offset}: a plan of depth 1 whose code is the candidate.
+    // The caller reads columns 2 and 3 and sets the key of every future (seed: as the row has it, env_key: the env's part of a key).
+    __device__ __forceinline__ bool read_samples(const TbxEditArgs& a, int env, int cand, uint64_t& seed, uint64_t& env_key)
+    {
+        frames = a.geti(env, 0);
+        hold = a.n > 1 ? a.geti(env, 1) : 1;
+        depth = 1;
+        code = (uint32_t)cand;
+        first = -1;
+        rest = a.n > 4 ? a.geti(env, 4) : -1;
+        seed = (uint64_t)a.getu(env, 5) | ((uint64_t)a.getu(env, 6) << 32);
+        t = a.getu(env, 7);
+        env_key = ((uint64_t)a.getu(env, 8) + (uint64_t)env) << 32;
+        key = seed ^ env_key;
+        return frames >= 1 && frames <= TBX_LOOKAHEAD_MAX_FRAMES && hold >= 1 && playable(rest);
     }
     __device__ __forceinline__ uint32_t buttons(int period) const
     {
@@ -831,6 +849,110 @@ void tbx_search_launches(int n, long long units_per_env, long long leaf_frames_p
     for (long long e0 = 0; e0 < n; e0 += step) f((int)e0, (int)(n - e0 < step ? n - e0 : step));
 }
 
+// ---- TBX_QUERY_LOOKAHEAD_SAMPLES (include/toybox_amd.h): `samples` futures per (env, first action), summed on the device.
+
+// The game RNG of a future, between the load and the play: salt 0 leaves it as it stands, otherwise both words become
+// splitmix64(word ^ salt) -- the fork's rule (envcopy.hip: env_salt_kernel), here on the registers and never stored.  The leaf()
+// of every game policy calls it with its trailing `salt` argument; the plan and search kernels pass none and compile without it.
+__device__ __forceinline__ void tbx_salt_rng(Rng& r, uint64_t salt)
+{
+    if (salt) { r.s0 = tbx_splitmix64(r.s0 ^ salt); r.s1 = tbx_splitmix64(r.s1 ^ salt); }
+}
+
+// The eight fields of a row while they are summed: 64-bit integers, so a row does not depend on how its samples are cut up.
+struct TbxSampleSums {
+    long long n = 0, ret_sum = 0, ret_min = 0, ret_max = 0, lives_sum = 0, lost = 0, ended = 0, safe_sum = 0;
+    __device__ __forceinline__ void add(const TbxLookFields& f)
+    {
+        ret_min = n == 0 || f.ret < ret_min ? f.ret : ret_min;
+        ret_max = n == 0 || f.ret > ret_max ? f.ret : ret_max;
+        n++;
+        ret_sum += f.ret;
+        lives_sum += f.lives;
+        lost += f.lost_at >= 0 ? 1 : 0;
+        ended += f.lives <= 0 ? 1 : 0;
+        safe_sum += f.lost_at < 0 ? f.frames_run : f.lost_at;
+    }
+    // a partial row (n = 0: no sample behind it)
+    __device__ __forceinline__ void merge(const long long* p)
+    {
+        if (p[0] == 0) return;
+        ret_min = n == 0 || p[2] < ret_min ? p[2] : ret_min;
+        ret_max = n == 0 || p[3] > ret_max ? p[3] : ret_max;
+        n += p[0]; ret_sum += p[1]; lives_sum += p[4]; lost += p[5]; ended += p[6]; safe_sum += p[7];
+    }
+    // the query's own row: converted to binary64 once, here; a refused row (n = 0) is zeros
+    __device__ __forceinline__ void store(double* o) const
+    {
+        o[0] = (double)n; o[1] = (double)ret_sum; o[2] = (double)ret_min; o[3] = (double)ret_max;
+        o[4] = (double)lives_sum; o[5] = (double)lost; o[6] = (double)ended; o[7] = (double)safe_sum;
+    }
+    __device__ __forceinline__ void store_partial(long long* o) const
+    {
+        o[0] = n; o[1] = ret_sum; o[2] = ret_min; o[3] = ret_max; o[4] = lives_sum; o[5] = lost; o[6] = ended; o[7] = safe_sum;
+    }
+};
+
+// A unit is (env, first action, chunk), unit = (env * n_legal + cand) * chunks + chunk, as in the search.  It walks the samples
+// [chunk * S / chunks, (chunk + 1) * S / chunks) of its env's S one after the other -- reload, salt, play, add (wave forms: in
+// SGPRs) -- and stores ONE row of eight: with chunks = 1 the query's own output row (doubles), otherwise a partial row (the 64-bit
+// integers as they are, in the same eight words) for tbx_sample_sum_kernel.
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_sample_kernel(G g, TbxEditArgs a, int chunks, long long first_unit, int count, double* __restrict__ rows)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const int lane = threadIdx.x & 63;
+    const int rel = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (rel >= count) return;
+    const long long unit = first_unit + rel;
+    int env = (int)(unit / (L * chunks));
+    const int r = (int)(unit - (long long)env * (L * chunks));
+    int cand = r / chunks, chunk = r - cand * chunks;
+    TbxLookahead<G::GAME, true> look;
+    uint64_t seed, env_key;
+    bool ok = look.read_samples(a, env, cand, seed, env_key);
+    int S = a.n > 2 ? a.geti(env, 2) : 1;
+    const double salt_arg = a.n > 3 ? a.get(env, 3) : 0.0;
+    ok = ok && S >= 1 && S <= TBX_LOOKAHEAD_MAX_SAMPLES && salt_arg >= 0.0 && salt_arg < 4294967296.0;
+    uint64_t salt = ok ? (uint64_t)salt_arg : 0ull;
+    ok = ok && (salt == 0 || salt + (uint64_t)S - 1 < (1ull << 32));
+    if (G::WAVE) {
+        env = wave_uniform(env); cand = wave_uniform(cand); chunk = wave_uniform(chunk);
+        ok = wave_uniform(ok); S = wave_uniform(S);
+        salt = wave_uniform64(salt); seed = wave_uniform64(seed); env_key = wave_uniform64(env_key);
+        look.uniform_plan();
+    }
+    TbxSampleSums sum;
+    if (ok) {
+        const int lo = (int)((long long)chunk * S / chunks), hi = (int)((long long)(chunk + 1) * S / chunks);
+        for (int s = lo; s < hi; s++) {
+            look.key = tbx_splitmix64(seed + (uint64_t)s) ^ env_key;
+            // every sample RELOADS its env through an opaque index, as every leaf of the search does (profiles/search.md)
+            int env_now = env;
+            if (G::WAVE) asm volatile("" : "+s"(env_now));
+            else asm volatile("" : "+v"(env_now));
+            TbxLookFields f = g.leaf(env_now, lane, look, salt ? salt + (uint64_t)s : 0ull);
+            if (G::WAVE) {
+                f.ret = (long long)wave_uniform64((uint64_t)f.ret);
+                f.lives = wave_uniform(f.lives); f.frames_run = wave_uniform(f.frames_run); f.lost_at = wave_uniform(f.lost_at);
+            }
+            sum.add(f);
+        }
+    }
+    if (!G::WAVE || lane == 0) {
+        if (chunks > 1) sum.store_partial(reinterpret_cast<long long*>(rows) + unit * 8);
+        else sum.store(rows + unit * 8);
+    }
+}
+
+template <class G>
+void tbx_launch_sample(const G& g, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s)
+{
+    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_search_launches: below 2^30)
+    const long long threads = count * (G::WAVE ? 64 : 1);
+    hipLaunchKernelGGL(tbx_sample_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, chunks, per_env * first_env, (int)count, rows);
+}
+
 // One per-env array of an engine as the env-copy kernels see it (envcopy.hip: fork, checkpoint save and restore) -- `fields`
 // planes of N rows of row_bytes each, [fields][N][row_bytes].  A struct-of-arrays scalar [F][N] is F planes of 4- or 8-byte rows,
 // an env-major table [N][R] one plane of R-byte rows, the plane ring `stack` planes of out_h * out_w bytes.  rng_words > 0: every
@@ -1015,6 +1137,8 @@ struct GameOps {
     // [first_env, first_env + envs), rows[unit]; search_lanes(): the lanes one unit takes in the form the engine is in (64 or 1)
     virtual int lookahead_plan(tbx_engine* e, const TbxEditArgs&, double* /*out_dev*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     virtual int lookahead_search(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    // TBX_QUERY_LOOKAHEAD_SAMPLES: tbx_sample_kernel over the same units
+    virtual int lookahead_sample(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     virtual int search_lanes() const { return 64; }
     // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
     // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The

@@ -204,6 +204,37 @@ def search_args(game, n_envs, frames, hold=1, depth=1, objective=0, rest=None, s
     return _plan_rows("objective", name, n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
 
 
+SAMPLE_FIELDS = ("samples", "ret_sum", "ret_min", "ret_max", "lives_sum", "lost", "ended", "safe_frames_sum")
+
+
+def _splitmix64(x):
+    x = (int(x) + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return x ^ (x >> 31)
+
+
+def sample_seed(seed, s):
+    """The lookahead seed of future s of TBX_QUERY_LOOKAHEAD_SAMPLES: splitmix64((seed + s) mod 2**64).  Future s of a sampled
+    lookahead with salt 0 is lookahead_all(..., seed=sample_seed(seed, s))."""
+    return _splitmix64((int(seed) + int(s)) & 0xFFFFFFFFFFFFFFFF)
+
+
+def sample_args(game, n_envs, frames, samples, hold=1, salt=0, rest=None, seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD_SAMPLES: columns {frames, hold, samples, salt, rest, seed_lo, seed_hi, t,
+    env_offset}; (args, per_env) as lookahead_args gives them.  Shared values are range-checked here (ValueError): samples
+    1 .. LOOKAHEAD_MAX_SAMPLES, salt 0 .. 2**32 - 1 with salt + samples - 1 below 2**32 where it is not 0; per-env rows are left
+    to the device (a bad row answers zeros)."""
+    if not np.ndim(samples) and not 1 <= int(samples) <= _abi.LOOKAHEAD_MAX_SAMPLES:
+        raise ValueError("samples must be 1 .. %d, got %r" % (_abi.LOOKAHEAD_MAX_SAMPLES, samples))
+    if not np.ndim(salt):
+        if not 0 <= int(salt) < 1 << 32:
+            raise ValueError("sample salt must be 0 .. 2**32 - 1, got %r" % (salt,))
+        if int(salt) and not np.ndim(samples) and int(salt) + int(samples) - 1 >= 1 << 32:
+            raise ValueError("sample salt + samples - 1 must stay below 2**32, got %r + %r" % (salt, samples))
+    return _plan_rows("salt", game, n_envs, frames, hold, samples, salt, rest, seed, t, env_offset)
+
+
 class Engine:
     def __init__(self, game, n_envs=1, device=0, config=None, lib=None):
         self._lib = lib if lib is not None else load()
@@ -498,6 +529,26 @@ class Engine:
         plan[np.broadcast_to(np.arange(width) >= d[:, None, None], plan.shape)] = -1
         res["plan"] = plan
         return res
+
+    def lookahead_samples(self, frames, samples, hold=1, salt=0, rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_SAMPLES: for every env and every first action (self.legal_actions order) `samples` futures of
+        `frames` raw frames, summed on the device.  Future s is lookahead_all() under seed sample_seed(seed, s) -- with rest None
+        every future draws its own action stream -- and, with a salt that is not 0, with the env's game RNG salted by salt + s as
+        fork(salt=...) would salt it (in registers: nothing is written).  Returns a dict of int64 [N, n_legal] arrays: samples
+        (0: the row was refused), ret_sum, ret_min, ret_max, lives_sum, lost (futures that lost a life), ended (futures whose
+        game ended) and safe_frames_sum (frames before the first lost life, summed)."""
+        args, _ = sample_args(self.game, self.n_envs, frames, samples, hold, salt, rest, seed, t, env_offset)
+        out = self.reduce(_abi.QUERY_LOOKAHEAD_SAMPLES, args).reshape(self.n_envs, len(self.legal_actions), 8)
+        return self._samples_dict(out)
+
+    @staticmethod
+    def _samples_dict(out):
+        return {k: out[..., i].astype(np.int64) for i, k in enumerate(SAMPLE_FIELDS)}
+
+    @property
+    def sample_chunks(self):
+        """into how many chunks the last lookahead_samples cut the samples of every (env, first action) group (0: none yet)"""
+        return self.get_option(_abi.OPT_SAMPLE_CHUNKS)
 
     @property
     def search_chunks(self):

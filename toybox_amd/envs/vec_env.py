@@ -105,6 +105,33 @@ def _search(env, frames, hold, depth, objective, rest, seed, t):
     return out
 
 
+def sample_best_action(out, objective="return"):
+    """The winner among an env's rows of a sampled lookahead (arrays [num_envs, n_actions]) -> int64 [num_envs].  "return": the
+    largest ret_sum, then the smallest lost, then the largest safe_frames_sum, then the smallest index; "survival": the smallest
+    lost, then the largest safe_frames_sum, then the largest ret_sum, then the smallest index."""
+    if objective not in ("return", "survival"):
+        raise ValueError("objective is 'return' or 'survival', got %r" % (objective,))
+    ret, lost, safe = (np.asarray(out[k], np.int64) for k in ("ret_sum", "lost", "safe_frames_sum"))
+    keys = (-ret, lost, -safe) if objective == "return" else (lost, -safe, -ret)
+    index = np.broadcast_to(np.arange(ret.shape[1]), ret.shape)
+    # np.lexsort: the last key is the primary one, ascending
+    return np.lexsort((index,) + tuple(reversed(keys)), axis=1)[:, 0].astype(np.int64)
+
+
+def _samples(env, frames, hold, samples, rest, seed, t, salt, objective):
+    """Engine.lookahead_samples for an adapter: `rest` an action index going in; the rows are in action-index order (the action
+    set is the engine's legal set in its order); the means and the winner (sample_best_action) are added"""
+    if objective not in ("return", "survival"):
+        raise ValueError("objective is 'return' or 'survival', got %r" % (objective,))
+    out = env.engine.lookahead_samples(frames, int(samples), hold=hold, salt=salt, rest=_ale(env, rest), seed=seed, t=t)
+    played = np.maximum(out["samples"], 1).astype(np.float64)
+    out["ret_mean"] = out["ret_sum"] / played
+    out["lost_frac"] = out["lost"] / played
+    out["ended_frac"] = out["ended"] / played
+    out["best_action"] = sample_best_action(out, objective)
+    return out
+
+
 def _fork_map(n, src, envs):
     """(src int[N], selected bool[N]) of a fork: src an int (one source fanned out) or one index per env; envs None (every
     env), a boolean mask or indices.  Unselected envs name themselves."""
@@ -296,6 +323,17 @@ class ToyboxVecEnv:
         if self._in_flight is not None or self._pending is not None:
             self.step_wait()
         return _search(self, int(steps), 1, depth, objective, rest, seed, t)
+
+    def lookahead_samples(self, steps, samples, rest=None, seed=0, t=0, salt=0, objective="return"):
+        """`samples` random futures of `steps` steps per env and first action index, summed on the device without taking them
+        (Engine.lookahead_samples): future s draws its actions (rest None) under its own seed and, with a salt that is not 0,
+        plays with the game's randomness salted by salt + s.  Returns samples, ret_sum, ret_min, ret_max, lives_sum, lost, ended,
+        safe_frames_sum [num_envs, n_actions], the means ret_mean, lost_frac, ended_frac, and best_action [num_envs] under
+        objective "return" (ret_sum, then fewer lost, then more safe frames) or "survival" (fewer lost, then more safe frames,
+        then ret_sum); ties to the smaller index.  Nothing is touched; a pending step_async ends first, as in lookahead()."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _samples(self, int(steps), 1, samples, rest, seed, t, salt, objective)
 
     def get_images(self):
         return self.engine.render(3)
@@ -625,6 +663,13 @@ class ToyboxPreprocVecEnv:
         if self._in_flight is not None:
             self.step_wait()
         return _search(self, int(steps) * self._skip, self._skip, depth, objective, rest, seed, t)
+
+    def lookahead_samples(self, steps, samples, rest=None, seed=0, t=0, salt=0, objective="return"):
+        """ToyboxVecEnv.lookahead_samples in agent steps: steps x skip raw frames, every action held for skip frames; raw frames,
+        no wrapper, as in lookahead().  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _samples(self, int(steps) * self._skip, self._skip, samples, rest, seed, t, salt, objective)
 
     def close(self):
         if not self.closed:
