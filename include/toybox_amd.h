@@ -708,6 +708,33 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
  *   In per-env rows such an env's whole output is zeros -- field 0 = 0 -- and the other envs are answered. */
 #define TBX_LOOKAHEAD_MAX_SAMPLES 4096
 #define TBX_QUERY_LOOKAHEAD_SAMPLES 154  /* {frames, hold, samples, salt, rest, seed_lo, seed_hi, t, env_offset} -> 8 * n_legal(game) */
+/* Search over sampled futures: every plan of a depth, each judged on the same `samples` futures, and the best plan per first action
+ * by the summed outcome.  Columns 0 .. 8 stand where TBX_QUERY_LOOKAHEAD_SEARCH has them; `samples` and `salt` are appended.
+ * Trailing arguments may be left out: the search's defaults (hold 1, depth 1, objective 0, rest -1, seed 0, t 0, env_offset 0), then
+ * samples 1 and salt 0.
+ *   Plans as in the search: 1 <= depth, L^depth <= TBX_LOOKAHEAD_MAX_PLANS, code = sum of digit_p * L^p; in addition
+ *   1 <= samples <= TBX_LOOKAHEAD_MAX_SAMPLES, L^depth * samples <= TBX_LOOKAHEAD_MAX_LEAVES, and the salt ranges of
+ *   TBX_QUERY_LOOKAHEAD_SAMPLES.
+ *   Future s = 0 .. samples-1 of plan `code` is exactly TBX_QUERY_LOOKAHEAD_PLAN {frames, hold, depth, code, rest, seed_s, t,
+ *   env_offset} played from the env's state with its game RNG salted by salt_s; seed_s = splitmix64((seed + s) mod 2^64) and
+ *   salt_s = salt == 0 ? 0 : salt + s, applied in registers and never stored, are those of TBX_QUERY_LOOKAHEAD_SAMPLES.
+ *   COMMON RANDOM NUMBERS: all plans of an env are played on the SAME `samples` futures -- seed_s and salt_s depend on s alone, not
+ *   on the plan -- so two plans differ by what they play and not by the luck of their draws.  That is what makes plans comparable
+ *   at small sample counts.
+ *   Per plan the eight sums of TBX_QUERY_LOOKAHEAD_SAMPLES are kept, 64-bit integers converted to binary64 once at the final store.
+ *   Out: for each first action a in legal-set order, row out[env][a][0 .. 8] = the eight sums (samples, ret_sum, ret_min, ret_max,
+ *   lives_sum, lost, ended, safe_frames_sum) of the BEST plan with digit_0 = a, then [8] its code.  Best is a total order on the
+ *   sums: objective 0 (return) takes the larger ret_sum, then the smaller lost, then the larger safe_frames_sum, then the smaller
+ *   code; objective 1 (survival) the smaller lost, then the larger safe_frames_sum, then the larger ret_sum, then the smaller code.
+ *   With samples = 1 this is NOT the order of TBX_QUERY_LOOKAHEAD_SEARCH: the search compares `lives` after the last frame, this
+ *   query compares the lost flag (life lost at >= 0) and never reads lives.
+ *   Chunks of suffix codes and launches over env ranges cut the work; neither changes any output bit.  "Nothing in the engine
+ *   changes" is the lookahead's sentence, verbatim.
+ *   TBX_E_INVALID, nothing launched: a shared value out of the ranges above (frames, hold, depth, objective, rest, samples, salt,
+ *   L^depth * samples), more than 11 arguments.  In per-env rows such an env's whole output is zeros -- field 0 = 0 -- and the
+ *   other envs are answered. */
+#define TBX_LOOKAHEAD_MAX_LEAVES 65536
+#define TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES 155  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, samples, salt} -> 9 * n_legal(game) */
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);
@@ -1007,6 +1034,10 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
 #define TBX_OPT_SEARCH_CHUNKS 105
 /* read-only: into how many chunks the last TBX_QUERY_LOOKAHEAD_SAMPLES cut the samples of every (env, first action) group (0: none yet) */
 #define TBX_OPT_SAMPLE_CHUNKS 106
+/* read-only: into how many chunks the last TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES cut the suffix codes of every (env, first action)
+ * group, and into how many launches over env ranges it was cut (0: none yet) */
+#define TBX_OPT_SEARCH_SAMPLES_CHUNKS 107
+#define TBX_OPT_SEARCH_SAMPLES_LAUNCHES 108
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
 /* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could

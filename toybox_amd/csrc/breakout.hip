@@ -2442,6 +2442,13 @@ struct BreakoutOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+    int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        if (!custom && use_tpe) tbx_launch_search_samples(BrkTLook{d, cfg_dev}, a, chunks, first_env, envs, rows, s);
+        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_search_samples(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, chunks, first_env, envs, rows, s); });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
     int search_lanes() const override { return !custom && use_tpe ? 1 : 64; }
 
     // TBX_EDIT_COPY_ENV: the struct-of-arrays state, the per-env brick table of the custom mode and the two record slots of the

@@ -309,7 +309,7 @@ int tbx_destroy(tbx_engine* e)
     }
     pipe_free(e);
     hipFree(e->actions);
-    e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); e->sample_parts.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
+    e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); e->sample_parts.release(); e->search_samples_parts.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
     hipFree(e->mask); hipFree(e->err_flag); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
     if (e->io_host) hipHostFree(e->io_host);
     if (e->scal_host) hipHostFree(e->scal_host);
@@ -1150,6 +1150,7 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_LOOKAHEAD_PLAN: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
     default: return TBX_E_INVALID;
     }
 }
@@ -1301,6 +1302,87 @@ static int lookahead_samples(tbx_engine* e, const TbxEditArgs& a, double* out_de
     return TBX_OK;
 }
 
+// chunks > 1: the winner among the partial rows parts[group][chunks][9] (64-bit integers; word 8 the code, -1: no plan behind
+// the row) of every (env, first action) group of envs from first_env on, by the order of the search-samples kernel; a group
+// without a plan (a refused row) answers zeros
+__global__ __launch_bounds__(256) void tbx_search_samples_pick_kernel(const long long* __restrict__ parts, TbxEditArgs a, int legal, int chunks, long long first_group, int count,
+                                                                      double* __restrict__ out)
+{
+    const int rel = blockIdx.x * 256 + threadIdx.x;
+    if (rel >= count) return;
+    const long long group = first_group + rel;
+    const int env = (int)(group / legal);
+    const int objective = a.n > 3 ? a.geti(env, 3) : 0;
+    const long long* const p0 = parts + group * chunks * 9;
+    TbxSearchSamplesKey best{0, 0, 0};
+    uint32_t best_code = 0;
+    int best_chunk = -1;
+    for (int c = 0; c < chunks; c++) {
+        const long long* p = p0 + (size_t)c * 9;
+        if (p[8] < 0) continue;
+        const TbxSearchSamplesKey key{p[1], (int)p[5], (int)p[7]};
+        const uint32_t code = (uint32_t)p[8];
+        if (best_chunk < 0 || tbx_search_samples_better(objective, key, code, best, best_code)) { best = key; best_code = code; best_chunk = c; }
+    }
+    TbxSampleSums win;
+    if (best_chunk >= 0) win.merge(p0 + (size_t)best_chunk * 9);
+    tbx_search_samples_store(out + group * 9, win, best_code, best_chunk < 0, false);
+}
+
+// TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: shared values are refused here, before anything is launched; per-env rows are met by the
+// kernel.  Chunks over the suffix codes (tbx_search_chunks), launches over env ranges under the game's own leaf-frame budget
+// (tbx_search_samples_budget); per-env rows are budgeted as the largest valid row, TBX_LOOKAHEAD_MAX_LEAVES x TBX_LOOKAHEAD_MAX_FRAMES.
+static int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s)
+{
+    const int L = tbx_legal_count(e->game);
+    if (a.n < 1 || a.n > 11) return e->fail(TBX_E_INVALID, "search over samples takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, samples, salt]}");
+    long long suffixes = TBX_LOOKAHEAD_MAX_PLANS / L, leaves = TBX_LOOKAHEAD_MAX_LEAVES, frames = TBX_LOOKAHEAD_MAX_FRAMES;      // per-env rows: the most a valid row can ask for
+    if (!a.per_env) {
+        auto playable = [&](double v) {
+            if (v == -1.0) return true;
+            for (int i = 0; i < L; i++)
+                if (v == (double)tbx_legal_action(e->game, i)) return true;
+            return false;
+        };
+        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        const double depth = a.n > 2 ? a.v[2] : 1.0;
+        if (!(depth >= 1.0 && depth <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "search over samples: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
+        const uint64_t plans = tbx_plan_count(e->game, TbxEditArgs::to_int(depth));
+        if (plans > (uint64_t)TBX_LOOKAHEAD_MAX_PLANS) return e->fail(TBX_E_INVALID, "search over samples: n_legal^depth must not exceed TBX_LOOKAHEAD_MAX_PLANS");
+        if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "search over samples: objective must be 0 (return) or 1 (survival)");
+        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        const double count = a.n > 9 ? a.v[9] : 1.0, salt = a.n > 10 ? a.v[10] : 0.0;
+        if (!(count >= 1.0 && count <= (double)TBX_LOOKAHEAD_MAX_SAMPLES)) return e->fail(TBX_E_INVALID, "search over samples: samples must be 1 .. TBX_LOOKAHEAD_MAX_SAMPLES");
+        const long long samples = TbxEditArgs::to_int(count);
+        if ((long long)plans * samples > (long long)TBX_LOOKAHEAD_MAX_LEAVES) return e->fail(TBX_E_INVALID, "search over samples: n_legal^depth * samples must not exceed TBX_LOOKAHEAD_MAX_LEAVES");
+        if (!(salt >= 0.0 && salt < 4294967296.0)) return e->fail(TBX_E_INVALID, "search over samples: salt must be 0 .. 2^32 - 1");
+        if ((uint64_t)salt != 0 && (uint64_t)salt + (uint64_t)samples - 1 >= (1ull << 32)) return e->fail(TBX_E_INVALID, "search over samples: salt + samples - 1 must stay below 2^32");
+        suffixes = (long long)plans / L;
+        leaves = (long long)plans * samples;
+        frames = TbxEditArgs::to_int(a.v[0]);
+    }
+    const int lanes = e->ops->search_lanes();
+    const int chunks = tbx_search_chunks(e->n, L, suffixes, lanes);
+    double* rows = out_dev;
+    if (chunks > 1) {
+        EHIP(e->search_samples_parts.reserve(sizeof(double) * 9 * (size_t)e->n * (size_t)L * (size_t)chunks, e->stream, s));
+        rows = e->search_samples_parts.p;
+    }
+    e->search_samples_chunks = chunks;
+    int rc = TBX_OK;
+    e->search_samples_launches = tbx_search_samples_launches(e->n, (long long)L * chunks, leaves * frames, tbx_search_samples_budget(e->game, lanes), [&](int env0, int envs) {
+        if (rc) return;
+        rc = e->ops->lookahead_search_samples(e, a, chunks, env0, envs, rows, s);
+        if (rc || chunks == 1) return;
+        const int groups = envs * L;
+        hipLaunchKernelGGL(tbx_search_samples_pick_kernel, dim3((groups + 255) / 256), dim3(256), 0, s, reinterpret_cast<const long long*>(rows), a, L, chunks, (long long)env0 * L, groups, out_dev);
+    });
+    if (rc) return rc;
+    EHIP(hipGetLastError());
+    return TBX_OK;
+}
+
 // the queries every game has (the engine's own), else the game's
 static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s)
 {
@@ -1323,6 +1405,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
     }
     if (query == TBX_QUERY_LOOKAHEAD_PLAN || query == TBX_QUERY_LOOKAHEAD_SEARCH) return lookahead_plans(e, query, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_SAMPLES) return lookahead_samples(e, a, out_dev, s);
+    if (query == TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES) return lookahead_search_samples(e, a, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     return checkpoint_valid(e, a, out_dev, s);
 }
@@ -1496,6 +1579,8 @@ int tbx_get_option(tbx_engine* e, int option, int* value_out)
     if (value_out && option == TBX_OPT_ROLLOUT_CHUNKS_ACTIVE) { *value_out = rollout_chunks_on(e, 3) ? 1 : 0; return TBX_OK; }
     if (value_out && option == TBX_OPT_SEARCH_CHUNKS) { *value_out = e->search_chunks; return TBX_OK; }
     if (value_out && option == TBX_OPT_SAMPLE_CHUNKS) { *value_out = e->sample_chunks; return TBX_OK; }
+    if (value_out && option == TBX_OPT_SEARCH_SAMPLES_CHUNKS) { *value_out = e->search_samples_chunks; return TBX_OK; }
+    if (value_out && option == TBX_OPT_SEARCH_SAMPLES_LAUNCHES) { *value_out = e->search_samples_launches; return TBX_OK; }
     if (option < 0 || option >= TBX_OPT_COUNT || !value_out) return e->fail(TBX_E_INVALID, "unknown option");
     *value_out = e->opt[option];
     return TBX_OK;

@@ -808,6 +808,12 @@ struct GridWorldOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+    int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        tbx_launch_search_samples(GwLook{d}, a, chunks, first_env, envs, rows, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
 
     // TBX_EDIT_COPY_ENV: scalars (struct of arrays), the env-major tile table and grid, of the live state and of the agent
     // layer's two slots (GridWorld has no RNG of its own)

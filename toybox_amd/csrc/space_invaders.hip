@@ -2234,6 +2234,12 @@ struct SiOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+    int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
+    {
+        tbx_launch_search_samples(SiLook{d, c}, a, chunks, first_env, envs, rows, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
 
     int reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s) override
     {

@@ -451,6 +451,8 @@ struct tbx_engine {
     int search_chunks = 0;          // chunks of the last TBX_QUERY_LOOKAHEAD_SEARCH (0: none yet)
     TbxDevBuf<double> sample_parts; // [N][n_legal][chunks][8] partial rows of TBX_QUERY_LOOKAHEAD_SAMPLES cut into chunks (64-bit integers)
     int sample_chunks = 0;          // chunks of the last TBX_QUERY_LOOKAHEAD_SAMPLES (0: none yet)
+    TbxDevBuf<double> search_samples_parts;  // [N][n_legal][chunks][9] partial rows of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES (64-bit integers)
+    int search_samples_chunks = 0, search_samples_launches = 0;   // chunks and launches of the last TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES (0: none yet)
     TbxDevBuf<void> staging;        // device POD staging for get/set state
     struct TbxEnvCopy* envcopy = nullptr;   // TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*: the fork's scratch copy, the checkpoint store (envcopy.hip), made on first use
     GameOps* ops = nullptr;
@@ -733,6 +735,23 @@ __device__ __forceinline__ bool tbx_search_better(int objective, const TbxLookFi
     if (x.ret != y.ret) return x.ret > y.ret;
     return xcode < ycode;
 }
+// TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: "plan x beats plan y" on the integer sums of their S futures -- the order of
+// sample_best_action (toybox_amd/envs/vec_env.py) with the code as the last tie-break, so it is total and the winner does not
+// depend on how the plans are cut up.  objective 0 (return): larger ret_sum, smaller lost, larger safe_frames_sum; objective 1
+// (survival): smaller lost, larger safe_frames_sum, larger ret_sum; then the smaller code.  With one sample this is NOT
+// tbx_search_better: that one reads lives, this one the lost flag.
+struct TbxSearchSamplesKey {
+    long long ret_sum;
+    int lost, safe_sum;           // at most TBX_LOOKAHEAD_MAX_SAMPLES futures of at most TBX_LOOKAHEAD_MAX_FRAMES frames: below 2^23
+};
+__device__ __forceinline__ bool tbx_search_samples_better(int objective, const TbxSearchSamplesKey& x, uint32_t xcode, const TbxSearchSamplesKey& y, uint32_t ycode)
+{
+    if (objective == 0 && x.ret_sum != y.ret_sum) return x.ret_sum > y.ret_sum;
+    if (x.lost != y.lost) return x.lost < y.lost;
+    if (x.safe_sum != y.safe_sum) return x.safe_sum > y.safe_sum;
+    if (x.ret_sum != y.ret_sum) return x.ret_sum > y.ret_sum;
+    return xcode < ycode;
+}
 // a row of 6 doubles; `none`: no leaf behind it -- the final row of a refused env is zeros, a partial row carries code -1
 __device__ __forceinline__ void tbx_search_store(double* o, const TbxLookFields& f, uint32_t code, bool none, bool partial)
 {
@@ -953,6 +972,140 @@ void tbx_launch_sample(const G& g, const TbxEditArgs& a, int chunks, int first_e
     hipLaunchKernelGGL(tbx_sample_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, chunks, per_env * first_env, (int)count, rows);
 }
 
+// ---- TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES (include/toybox_amd.h): every plan of a depth on the same `samples` futures, the best
+// plan per (env, first action) by the summed outcome.
+
+// A row of 9: the eight sums, then the code.  `none`: no plan behind it -- the final row of a refused env is zeros, a partial row
+// carries code -1 (as the search's partial rows do).  Final rows are doubles, partial rows the 64-bit integers as they are.
+__device__ __forceinline__ void tbx_search_samples_store(double* o, const TbxSampleSums& sum, uint32_t code, bool none, bool partial)
+{
+    if (partial) {
+        long long* const p = reinterpret_cast<long long*>(o);
+        sum.store_partial(p);
+        p[8] = none ? -1ll : (long long)code;
+    } else {
+        sum.store(o);
+        o[8] = none ? 0.0 : (double)code;
+    }
+}
+
+// A unit is (env, first action, chunk), unit = (env * n_legal + cand) * chunks + chunk, as in the search.  It walks the suffix
+// codes [chunk * X / chunks, (chunk + 1) * X / chunks) of its env's X = n_legal^(depth - 1) one after the other; per code it runs
+// the sample loop of tbx_sample_kernel -- reload, salt, play, add -- over ALL S futures of the env (the same S for every code:
+// common random numbers) and compares the sums with the best so far by tbx_search_samples_better.  Wave forms: sums, the best's
+// eight sums and control live in SGPRs, one pass.  Thread form (Breakout, 163 VGPRs in the sample kernel, 168 for three waves): a
+// second set of sums is 32 registers, so only what the order reads is kept of the running best (TbxSearchSamplesKey and the code:
+// the other five sums of the loop are dead there) and a second, short pass replays the S futures of the unit's winner for the full
+// eight; a chunk of one code has its winner without the first pass.  The unit stores ONE row of 9: with chunks = 1 the query's own
+// output row, otherwise a partial row for tbx_search_samples_pick_kernel.
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_search_samples_kernel(G g, TbxEditArgs a, int chunks, long long first_unit, int count, double* __restrict__ rows)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const int lane = threadIdx.x & 63;
+    const int rel = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (rel >= count) return;
+    const long long unit = first_unit + rel;
+    int env = (int)(unit / (L * chunks));
+    const int r = (int)(unit - (long long)env * (L * chunks));
+    int cand = r / chunks, chunk = r - cand * chunks;
+    TbxLookahead<G::GAME, true> look;
+    bool ok = look.read_plan(a, env, 1);
+    int objective = a.n > 3 ? a.geti(env, 3) : 0;
+    ok = ok && look.depth >= 1 && (objective == 0 || objective == 1);
+    uint32_t X = ok ? (uint32_t)tbx_plan_count(G::GAME, look.depth - 1) : 0u;     // (depth <= TBX_PLAN_MAX_DEPTH: below 2^32)
+    ok = ok && (uint64_t)X * (uint64_t)L <= (uint64_t)TBX_LOOKAHEAD_MAX_PLANS;
+    int S = a.n > 9 ? a.geti(env, 9) : 1;
+    const double salt_arg = a.n > 10 ? a.get(env, 10) : 0.0;
+    ok = ok && S >= 1 && S <= TBX_LOOKAHEAD_MAX_SAMPLES && (uint64_t)X * (uint64_t)L * (uint64_t)S <= (uint64_t)TBX_LOOKAHEAD_MAX_LEAVES;
+    ok = ok && salt_arg >= 0.0 && salt_arg < 4294967296.0;
+    uint64_t salt = ok ? (uint64_t)salt_arg : 0ull;
+    ok = ok && (salt == 0 || salt + (uint64_t)S - 1 < (1ull << 32));
+    uint64_t seed = (uint64_t)a.getu(env, 5) | ((uint64_t)a.getu(env, 6) << 32);
+    uint64_t env_key = ((uint64_t)a.getu(env, 8) + (uint64_t)env) << 32;
+    if (G::WAVE) {
+        env = wave_uniform(env); cand = wave_uniform(cand); chunk = wave_uniform(chunk); objective = wave_uniform(objective);
+        ok = wave_uniform(ok); X = (uint32_t)wave_uniform((int)X); S = wave_uniform(S);
+        salt = wave_uniform64(salt); seed = wave_uniform64(seed); env_key = wave_uniform64(env_key);
+        look.uniform_plan();
+    }
+    // the S futures of one plan, summed
+    auto play = [&](uint32_t code) {
+        look.code = code;
+        TbxSampleSums sum;
+        for (int s = 0; s < S; s++) {
+            look.key = tbx_splitmix64(seed + (uint64_t)s) ^ env_key;
+            // every leaf RELOADS its env through an opaque index, as every leaf of the search does (profiles/search.md)
+            int env_now = env;
+            if (G::WAVE) asm volatile("" : "+s"(env_now));
+            else asm volatile("" : "+v"(env_now));
+            TbxLookFields f = g.leaf(env_now, lane, look, salt ? salt + (uint64_t)s : 0ull);
+            if (G::WAVE) {
+                f.ret = (long long)wave_uniform64((uint64_t)f.ret);
+                f.lives = wave_uniform(f.lives); f.frames_run = wave_uniform(f.frames_run); f.lost_at = wave_uniform(f.lost_at);
+            }
+            sum.add(f);
+        }
+        return sum;
+    };
+    TbxSearchSamplesKey best{0, 0, 0};
+    TbxSampleSums win;
+    uint32_t best_code = 0;
+    bool none = true;
+    if (ok) {
+        const uint32_t lo = (uint32_t)((uint64_t)chunk * X / (uint32_t)chunks), hi = (uint32_t)((uint64_t)(chunk + 1) * X / (uint32_t)chunks);
+        if (!G::WAVE && hi - lo == 1) { best_code = (uint32_t)cand + (uint32_t)L * lo; none = false; }
+        else
+            for (uint32_t sfx = lo; sfx < hi; sfx++) {
+                const uint32_t code = (uint32_t)cand + (uint32_t)L * sfx;
+                const TbxSampleSums sum = play(code);
+                const TbxSearchSamplesKey key{sum.ret_sum, (int)sum.lost, (int)sum.safe_sum};
+                if (none || tbx_search_samples_better(objective, key, code, best, best_code)) {
+                    best = key; best_code = code; none = false;
+                    if (G::WAVE) win = sum;
+                }
+            }
+    }
+    if (!G::WAVE && !none) win = play(best_code);
+    if (!G::WAVE || lane == 0) tbx_search_samples_store(rows + unit * 9, win, best_code, none, chunks > 1);
+}
+
+template <class G>
+void tbx_launch_search_samples(const G& g, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s)
+{
+    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_search_samples_launches: below 2^30)
+    const long long threads = count * (G::WAVE ? 64 : 1);
+    hipLaunchKernelGGL(tbx_search_samples_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, chunks, per_env * first_env, (int)count, rows);
+}
+
+// One launch of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES plays at most this many leaf-frames, counted over ALL first actions, plans and
+// samples of its envs (plans x samples x frames per env): the largest power of two that stays at or below 0.25 s at the rate
+// measured for the game's sample kernel (profiles/samples.md, M leaf-frames/s): Breakout, a thread per unit, 21 986 -> 5.50 G in
+// 0.25 s -> 2^32; SpaceInvaders 2 915 -> 729 M -> 2^29; Amidar 1 057 -> 264 M -> 2^27 (2^28 = 268 M is above it); GridWorld
+// 7 262 -> 1.82 G -> 2^30.  Breakout's wave forms (lanes = 64) have no measured rate: they get the smallest of the four.
+// profiles/search_samples.md has the derivation.  TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH and the queries 153 / 154 are left alone.
+inline long long tbx_search_samples_budget(int game, int lanes)
+{
+    switch (game) {
+    case TBX_GAME_BREAKOUT: return lanes == 1 ? 1ll << 32 : 1ll << 27;
+    case TBX_GAME_SPACE_INVADERS: return 1ll << 29;
+    case TBX_GAME_AMIDAR: return 1ll << 27;
+    default: return 1ll << 30;
+    }
+}
+// f(first_env, envs) per launch: env ranges under `budget` leaf-frames and under TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units; returns
+// the launches.  leaf_frames_per_env: plans x samples x frames of one env (per-env rows: the largest a valid row can ask for)
+template <class F>
+int tbx_search_samples_launches(int n, long long units_per_env, long long leaf_frames_per_env, long long budget, F&& f)
+{
+    long long step = budget / leaf_frames_per_env;
+    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
+    if (step < 1) step = 1;
+    int launches = 0;
+    for (long long e0 = 0; e0 < n; e0 += step, launches++) f((int)e0, (int)(n - e0 < step ? n - e0 : step));
+    return launches;
+}
+
 // One per-env array of an engine as the env-copy kernels see it (envcopy.hip: fork, checkpoint save and restore) -- `fields`
 // planes of N rows of row_bytes each, [fields][N][row_bytes].  A struct-of-arrays scalar [F][N] is F planes of 4- or 8-byte rows,
 // an env-major table [N][R] one plane of R-byte rows, the plane ring `stack` planes of out_h * out_w bytes.  rng_words > 0: every
@@ -1139,6 +1292,8 @@ struct GameOps {
     virtual int lookahead_search(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     // TBX_QUERY_LOOKAHEAD_SAMPLES: tbx_sample_kernel over the same units
     virtual int lookahead_sample(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    // TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: tbx_search_samples_kernel over the same units
+    virtual int lookahead_search_samples(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     virtual int search_lanes() const { return 64; }
     // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
     // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The

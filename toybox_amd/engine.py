@@ -235,6 +235,36 @@ def sample_args(game, n_envs, frames, samples, hold=1, salt=0, rest=None, seed=0
     return _plan_rows("salt", game, n_envs, frames, hold, samples, salt, rest, seed, t, env_offset)
 
 
+def search_samples_args(game, n_envs, frames, depth, samples, hold=1, objective=0, salt=0, rest=None, seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: columns {frames, hold, depth, objective, rest, seed_lo, seed_hi, t,
+    env_offset, samples, salt} -- search_args with samples and salt appended; (args, per_env) as lookahead_args gives them.
+    Shared values are range-checked here (ValueError): the search's, samples 1 .. LOOKAHEAD_MAX_SAMPLES,
+    n_legal ** depth * samples <= LOOKAHEAD_MAX_LEAVES and the salt ranges of sample_args; per-env rows are left to the device
+    (a bad row answers zeros)."""
+    name = _game_name(game)
+    for what, c in (("samples", samples), ("salt", salt)):
+        if np.ndim(c) > 1 or (np.ndim(c) == 1 and len(c) != int(n_envs)):
+            raise ValueError("lookahead %s is a scalar or one value per env (%d), got shape %r" % (what, n_envs, np.shape(c)))
+    if not np.ndim(samples):
+        if not 1 <= int(samples) <= _abi.LOOKAHEAD_MAX_SAMPLES:
+            raise ValueError("samples must be 1 .. %d, got %r" % (_abi.LOOKAHEAD_MAX_SAMPLES, samples))
+        if not np.ndim(depth) and int(depth) >= 1 and len(_abi.LEGAL_ACTIONS[name]) ** int(depth) * int(samples) > _abi.LOOKAHEAD_MAX_LEAVES:
+            raise ValueError("n_legal ** depth * samples must not exceed %d, got depth %r and %r samples" % (_abi.LOOKAHEAD_MAX_LEAVES, depth, samples))
+    if not np.ndim(salt):
+        if not 0 <= int(salt) < 1 << 32:
+            raise ValueError("sample salt must be 0 .. 2**32 - 1, got %r" % (salt,))
+        if int(salt) and not np.ndim(samples) and int(salt) + int(samples) - 1 >= 1 << 32:
+            raise ValueError("sample salt + samples - 1 must stay below 2**32, got %r + %r" % (salt, samples))
+    base, per_env = search_args(name, n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
+    if not per_env and not np.ndim(samples) and not np.ndim(salt):
+        return list(base) + [float(samples), float(salt)], False
+    args = np.empty((int(n_envs), 11), np.float64)
+    args[:, :9] = np.asarray(base, np.float64)
+    args[:, 9] = np.asarray(samples, np.float64)
+    args[:, 10] = np.asarray(salt, np.float64)
+    return args, True
+
+
 class Engine:
     def __init__(self, game, n_envs=1, device=0, config=None, lib=None):
         self._lib = lib if lib is not None else load()
@@ -544,6 +574,40 @@ class Engine:
     @staticmethod
     def _samples_dict(out):
         return {k: out[..., i].astype(np.int64) for i, k in enumerate(SAMPLE_FIELDS)}
+
+    def lookahead_search_samples(self, frames, depth, samples, hold=1, objective="return", salt=0, rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: all n_legal ** depth plans of every env, each played on the SAME `samples` futures
+        (future s: seed sample_seed(seed, s) and, with a salt that is not 0, the game RNG salted by salt + s, as in
+        lookahead_samples); for each first action a (self.legal_actions order) the best plan that begins with it by the summed
+        outcome -- "return": the larger ret_sum, then the smaller lost, then the larger safe_frames_sum; "survival": the smaller
+        lost, the larger safe_frames_sum, the larger ret_sum; ties to the smaller code.  The eight lookahead_samples() fields of
+        that plan, int64 [N, n_legal] (samples 0: the row was refused), plus code [N, n_legal] (uint64) and plan
+        [N, n_legal, depth] (ALE ids; per-env depths: the largest, unused periods -1).  Nothing in the engine is written."""
+        args, _ = search_samples_args(self.game, self.n_envs, frames, depth, samples, hold, objective, salt, rest, seed, t, env_offset)
+        L = len(self.legal_actions)
+        out = self.reduce(_abi.QUERY_LOOKAHEAD_SEARCH_SAMPLES, args).reshape(self.n_envs, L, 9)
+        return self._search_samples_dict(out, depth)
+
+    def _search_samples_dict(self, out, depth):
+        L = len(self.legal_actions)
+        res = self._samples_dict(out[..., :8])
+        res["code"] = out[..., 8].astype(np.uint64)
+        d = np.broadcast_to(np.clip(np.asarray(depth, np.int64), 0, _abi.PLAN_MAX_DEPTH[self.game]), (self.n_envs,))
+        width = int(d.max()) if self.n_envs else 0
+        plan = np.asarray(self.legal_actions, np.int64)[plan_digits(L, res["code"], width)]
+        plan[np.broadcast_to(np.arange(width) >= d[:, None, None], plan.shape)] = -1
+        res["plan"] = plan
+        return res
+
+    @property
+    def search_samples_chunks(self):
+        """into how many chunks the last lookahead_search_samples cut every (env, first action) group of plans (0: none yet)"""
+        return self.get_option(_abi.OPT_SEARCH_SAMPLES_CHUNKS)
+
+    @property
+    def search_samples_launches(self):
+        """into how many launches over env ranges the last lookahead_search_samples was cut (0: none yet)"""
+        return self.get_option(_abi.OPT_SEARCH_SAMPLES_LAUNCHES)
 
     @property
     def sample_chunks(self):

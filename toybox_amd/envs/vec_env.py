@@ -132,6 +132,24 @@ def _samples(env, frames, hold, samples, rest, seed, t, salt, objective):
     return out
 
 
+def _search_samples(env, frames, hold, depth, samples, objective, rest, seed, t, salt):
+    """Engine.lookahead_search_samples for an adapter: `rest` an action index going in, `plan` action indices coming out (the
+    digits of the code); the means are added as _samples adds them, best_action is sample_best_action over the rows and best_plan
+    that row's plan"""
+    from ..engine import plan_digits
+    if objective not in ("return", "survival"):
+        raise ValueError("objective is 'return' or 'survival', got %r" % (objective,))
+    out = env.engine.lookahead_search_samples(frames, int(depth), int(samples), hold=hold, objective=objective, salt=salt, rest=_ale(env, rest), seed=seed, t=t)
+    out["plan"] = plan_digits(len(env._action_set), out["code"], int(depth))
+    played = np.maximum(out["samples"], 1).astype(np.float64)
+    out["ret_mean"] = out["ret_sum"] / played
+    out["lost_frac"] = out["lost"] / played
+    out["ended_frac"] = out["ended"] / played
+    out["best_action"] = sample_best_action(out, objective)
+    out["best_plan"] = out["plan"][np.arange(out["plan"].shape[0]), out["best_action"]]
+    return out
+
+
 def _fork_map(n, src, envs):
     """(src int[N], selected bool[N]) of a fork: src an int (one source fanned out) or one index per env; envs None (every
     env), a boolean mask or indices.  Unselected envs name themselves."""
@@ -334,6 +352,17 @@ class ToyboxVecEnv:
         if self._in_flight is not None or self._pending is not None:
             self.step_wait()
         return _samples(self, int(steps), 1, samples, rest, seed, t, salt, objective)
+
+    def search_samples(self, steps, depth, samples, objective="return", rest=None, seed=0, t=0, salt=0):
+        """search() over sampled futures (Engine.lookahead_search_samples): every action sequence of `depth` steps is played on
+        the same `samples` futures -- future s its own drawn action stream after the plan (rest None) and, with a salt that is
+        not 0, its own game randomness -- and for each first action index the best plan by the summed outcome comes back: the
+        eight sums of lookahead_samples() and code [num_envs, n_actions], plan [num_envs, n_actions, depth] (action indices),
+        the means ret_mean, lost_frac, ended_frac, and the winner among the rows (the order of lookahead_samples()),
+        best_action [num_envs] and best_plan [num_envs, depth].  Nothing is touched; a pending step_async ends first."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _search_samples(self, int(steps), 1, depth, samples, objective, rest, seed, t, salt)
 
     def get_images(self):
         return self.engine.render(3)
@@ -670,6 +699,13 @@ class ToyboxPreprocVecEnv:
         if self._in_flight is not None:
             self.step_wait()
         return _samples(self, int(steps) * self._skip, self._skip, samples, rest, seed, t, salt, objective)
+
+    def search_samples(self, steps, depth, samples, objective="return", rest=None, seed=0, t=0, salt=0):
+        """ToyboxVecEnv.search_samples in agent steps: steps x skip raw frames, every action held for skip frames; raw frames,
+        no wrapper, as in lookahead().  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _search_samples(self, int(steps) * self._skip, self._skip, depth, samples, objective, rest, seed, t, salt)
 
     def close(self):
         if not self.closed:
