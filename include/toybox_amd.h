@@ -735,6 +735,27 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
  *   other envs are answered. */
 #define TBX_LOOKAHEAD_MAX_LEAVES 65536
 #define TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES 155  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, samples, salt} -> 9 * n_legal(game) */
+/* Beam search: plans deeper than full enumeration reaches.  Columns 0 .. 8 stand where TBX_QUERY_LOOKAHEAD_SEARCH has them, with the
+ * same defaults for trailing arguments left out; `width` is appended and defaults to 1 (greedy search).  The ranges are the
+ * search's except that there is no L^depth cap: 1 <= depth <= TBX_PLAN_MAX_DEPTH(game), 1 <= width <= TBX_BEAM_MAX_WIDTH.
+ *   For every env and every first action a in legal-set order, with L = n_legal(game):
+ *     B_1 = {a}, the single prefix of depth 1;
+ *     for d = 2 .. depth the candidates are C_d = { c + k * L^(d-1) : c in B_(d-1), k = 0 .. L-1 };
+ *     candidate x of level d is valued by the five fields of TBX_QUERY_LOOKAHEAD_PLAN {frames, hold, d, x, rest, seed, t,
+ *       env_offset} -- the whole horizon, with `rest` from period d on;
+ *     B_d is the min(width, |C_d|) best of C_d under the search's order for `objective` (ret / lives / loss, then the smaller
+ *       code).  Codes within a level are distinct, so the order is total and the kept set does not depend on how the work is cut.
+ *   With C_1 = {a} valued at depth 1, row out[env][a][0 .. 5] = {ret, score, lives, frames run, life lost at, code} of the best
+ *   candidate of C_depth.  It follows that with width >= L^(depth-2), or with depth = 1, the row is the row of
+ *   TBX_QUERY_LOOKAHEAD_SEARCH, and that feeding the returned code to TBX_QUERY_LOOKAHEAD_PLAN with the same depth gives the row's
+ *   five fields.
+ *   Every candidate is replayed from the env's live state in registers, level after level on the calling stream, and a select
+ *   pass between two levels ranks a group's candidates; large batches are cut into env ranges (TBX_OPT_BEAM_RANGES).  Neither
+ *   changes the answer.  "Nothing in the engine changes" is the lookahead's sentence, verbatim.
+ *   TBX_E_INVALID, nothing launched: a shared value out of the ranges above (frames, hold, depth, objective, rest, width), more
+ *   than 10 arguments.  In per-env rows such an env's output is zeros -- frames run 0 -- and the other envs are answered. */
+#define TBX_BEAM_MAX_WIDTH 64
+#define TBX_QUERY_LOOKAHEAD_BEAM 156  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width} -> 6 * n_legal(game) */
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);
@@ -1038,6 +1059,11 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
  * group, and into how many launches over env ranges it was cut (0: none yet) */
 #define TBX_OPT_SEARCH_SAMPLES_CHUNKS 107
 #define TBX_OPT_SEARCH_SAMPLES_LAUNCHES 108
+/* read-only: into how many env ranges the last TBX_QUERY_LOOKAHEAD_BEAM was cut (0: none yet; a refused query leaves it standing) */
+#define TBX_OPT_BEAM_RANGES 109
+/* at most this many envs per range of a TBX_QUERY_LOOKAHEAD_BEAM, on top of the engine's budgets; 0 (default): the engine's choice.
+ * It changes no output bit. */
+#define TBX_OPT_BEAM_RANGE_ENVS 110
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
 /* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could

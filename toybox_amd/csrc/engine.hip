@@ -309,7 +309,7 @@ int tbx_destroy(tbx_engine* e)
     }
     pipe_free(e);
     hipFree(e->actions);
-    e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); e->sample_parts.release(); e->search_samples_parts.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
+    e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); e->sample_parts.release(); e->search_samples_parts.release(); e->beam_scratch.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
     hipFree(e->mask); hipFree(e->err_flag); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
     if (e->io_host) hipHostFree(e->io_host);
     if (e->scal_host) hipHostFree(e->scal_host);
@@ -1149,6 +1149,7 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_LOOKAHEAD_ALL: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_PLAN: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_BEAM: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
     default: return TBX_E_INVALID;
@@ -1241,6 +1242,102 @@ static int lookahead_plans(tbx_engine* e, int query, const TbxEditArgs& a, doubl
         hipLaunchKernelGGL(tbx_search_pick_kernel, dim3((groups + 255) / 256), dim3(256), 0, s, rows, a, L, chunks, (long long)env0 * L, groups, out_dev);
     });
     if (rc) return rc;
+    EHIP(hipGetLastError());
+    return TBX_OK;
+}
+
+// TBX_QUERY_LOOKAHEAD_BEAM, between two levels: one wave per (env, first action) group of envs from first_env on.  It stages the
+// group's candidates of `level` (at most TBX_BEAM_MAX_WIDTH * 6 = 384) in LDS, ranks each by COUNTING the candidates that beat it
+// under tbx_search_better -- codes within a level are distinct, so the ranks are a permutation and a pure function of the
+// candidate set: no atomics, no sort network, nothing that depends on the launch shape -- and writes the candidate of rank
+// r < width to slot r of the next beam; on the env's last level rank 0 goes to the output row.  A refused env's rows are zeros,
+// written at level 1; an env whose depth is below `level` idles.
+constexpr int TBX_BEAM_MAX_CANDS = TBX_BEAM_MAX_WIDTH * 6;
+__global__ __launch_bounds__(64) void tbx_beam_select_kernel(TbxEditArgs a, int game, int level, int first_env, TbxBeamScratch sc, double* __restrict__ out)
+{
+    __shared__ TbxBeamCand lds[TBX_BEAM_MAX_CANDS];
+    const int L = tbx_legal_count(game);
+    const int group = blockIdx.x, lane = threadIdx.x;
+    const int env = first_env + group / L;
+    double* const o = out + ((size_t)first_env * L + group) * 6;
+    int depth, objective, width;
+    if (!tbx_beam_row(game, a, env, depth, objective, width)) {
+        if (level == 1 && lane < 6) o[lane] = 0.0;
+        return;
+    }
+    if (level > depth) return;
+    const int n = level == 1 ? 1 : tbx_beam_kept(L, width, level - 1) * L;       // at most width * L
+    const TbxBeamCand* const c = sc.cands + (size_t)group * sc.stride * L;
+    for (int i = lane; i < n; i += 64) lds[i] = c[i];
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) {
+        const TbxBeamCand x = lds[i];
+        int rank = 0;
+        for (int j = 0; j < n; j++) rank += j != i && tbx_search_better(objective, lds[j].f, lds[j].code, x.f, x.code) ? 1 : 0;
+        if (level < depth && rank < width) sc.beam_out[(size_t)group * sc.stride + rank] = x.code;
+        if (level == depth && rank == 0) tbx_search_store(o, x.f, x.code, false, false);
+    }
+}
+
+// One env range of a beam holds candidates plus two beams in engine-owned scratch; the ranges keep it under this, whatever N and
+// width are (a starting value: profiles/beam.md).
+constexpr size_t TBX_BEAM_SCRATCH_BYTES = 256ull << 20;
+
+// TBX_QUERY_LOOKAHEAD_BEAM: shared values are refused here, before anything is launched; per-env rows are met by the kernels.
+// Env ranges keep a launch under TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH leaf-frames and TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units and the
+// scratch under TBX_BEAM_SCRATCH_BYTES (per-env rows: budgeted as the largest valid row, and every level up to
+// TBX_PLAN_MAX_DEPTH runs -- the device form cannot see the rows; a shallower env writes its row at its own last level and idles
+// afterwards).  Within a range, per level: play, select -- all on `s`, in stream order, no host synchronisation.
+static int lookahead_beam(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s)
+{
+    const int L = tbx_legal_count(e->game);
+    if (a.n < 1 || a.n > 10) return e->fail(TBX_E_INVALID, "beam takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width]}");
+    long long frames = TBX_LOOKAHEAD_MAX_FRAMES;      // per-env rows: the most a valid row can ask for
+    int depth = tbx_plan_max_depth(e->game), width = TBX_BEAM_MAX_WIDTH;
+    if (!a.per_env) {
+        auto playable = [&](double v) {
+            if (v == -1.0) return true;
+            for (int i = 0; i < L; i++)
+                if (v == (double)tbx_legal_action(e->game, i)) return true;
+            return false;
+        };
+        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        const double dp = a.n > 2 ? a.v[2] : 1.0, w = a.n > 9 ? a.v[9] : 1.0;
+        if (!(dp >= 1.0 && dp <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "beam: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
+        if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "beam: objective must be 0 (return) or 1 (survival)");
+        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        if (!(w >= 1.0 && w <= (double)TBX_BEAM_MAX_WIDTH)) return e->fail(TBX_E_INVALID, "beam: width must be 1 .. TBX_BEAM_MAX_WIDTH");
+        frames = TbxEditArgs::to_int(a.v[0]);
+        depth = TbxEditArgs::to_int(dp);
+        width = TbxEditArgs::to_int(w);
+    }
+    // per env: L groups of at most width * L candidates, and two beams of width codes per group
+    const long long units_per_env = (long long)L * width * L;
+    const size_t bytes_per_env = (size_t)units_per_env * sizeof(TbxBeamCand) + 2 * (size_t)L * width * sizeof(uint32_t);
+    long long step = TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH / (units_per_env * frames);
+    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
+    if (step > (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env)) step = (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env);
+    if (e->beam_range_envs > 0 && step > e->beam_range_envs) step = e->beam_range_envs;
+    if (step > e->n) step = e->n;
+    if (step < 1) step = 1;
+    EHIP(e->beam_scratch.reserve(bytes_per_env * (size_t)step, e->stream, s));
+    TbxBeamScratch sc;
+    sc.stride = width;
+    sc.cands = reinterpret_cast<TbxBeamCand*>(e->beam_scratch.p);
+    sc.beam_in = reinterpret_cast<uint32_t*>(e->beam_scratch.p + (size_t)units_per_env * sizeof(TbxBeamCand) * (size_t)step);
+    sc.beam_out = sc.beam_in + (size_t)L * width * (size_t)step;
+    int ranges = 0;
+    for (long long env0 = 0; env0 < e->n; env0 += step, ranges++) {
+        const int envs = (int)(e->n - env0 < step ? e->n - env0 : step);
+        for (int level = 1; level <= depth; level++) {
+            int rc = e->ops->lookahead_beam(e, a, level, tbx_beam_kept(L, width, level - 1), (int)env0, envs, sc, s);
+            if (rc) return rc;
+            hipLaunchKernelGGL(tbx_beam_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, level, (int)env0, sc, out_dev);
+            uint32_t* const t = sc.beam_in; sc.beam_in = sc.beam_out; sc.beam_out = t;
+        }
+    }
+    e->beam_ranges = ranges;
     EHIP(hipGetLastError());
     return TBX_OK;
 }
@@ -1404,6 +1501,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
         return e->ops->lookahead(e, a, query == TBX_QUERY_LOOKAHEAD_ALL, out_dev, s);
     }
     if (query == TBX_QUERY_LOOKAHEAD_PLAN || query == TBX_QUERY_LOOKAHEAD_SEARCH) return lookahead_plans(e, query, a, out_dev, s);
+    if (query == TBX_QUERY_LOOKAHEAD_BEAM) return lookahead_beam(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_SAMPLES) return lookahead_samples(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES) return lookahead_search_samples(e, a, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
@@ -1546,6 +1644,11 @@ int tbx_device_buffer(tbx_engine* e, int which, void** out_ptr, size_t* out_byte
 int tbx_set_option(tbx_engine* e, int option, int value)
 {
     CHECK_ENGINE(e);
+    if (option == TBX_OPT_BEAM_RANGE_ENVS) {       // read by the host when a beam query is cut into ranges: nothing in flight depends on it
+        if (value < 0) return e->fail(TBX_E_INVALID, "option value out of range");
+        e->beam_range_envs = value;
+        return TBX_OK;
+    }
     bool ok = false;
     switch (option) {
     case TBX_OPT_PIPELINE: ok = value >= 0 && value <= 3; break;
@@ -1580,6 +1683,8 @@ int tbx_get_option(tbx_engine* e, int option, int* value_out)
     if (value_out && option == TBX_OPT_SEARCH_CHUNKS) { *value_out = e->search_chunks; return TBX_OK; }
     if (value_out && option == TBX_OPT_SAMPLE_CHUNKS) { *value_out = e->sample_chunks; return TBX_OK; }
     if (value_out && option == TBX_OPT_SEARCH_SAMPLES_CHUNKS) { *value_out = e->search_samples_chunks; return TBX_OK; }
+    if (value_out && option == TBX_OPT_BEAM_RANGES) { *value_out = e->beam_ranges; return TBX_OK; }
+    if (value_out && option == TBX_OPT_BEAM_RANGE_ENVS) { *value_out = e->beam_range_envs; return TBX_OK; }
     if (value_out && option == TBX_OPT_SEARCH_SAMPLES_LAUNCHES) { *value_out = e->search_samples_launches; return TBX_OK; }
     if (option < 0 || option >= TBX_OPT_COUNT || !value_out) return e->fail(TBX_E_INVALID, "unknown option");
     *value_out = e->opt[option];

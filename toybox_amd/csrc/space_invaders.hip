@@ -2228,6 +2228,12 @@ struct SiOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+    int lookahead_beam(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int first_env, int envs, const TbxBeamScratch& sc, hipStream_t s) override
+    {
+        tbx_launch_beam(SiLook{d, c}, a, level, slots, first_env, envs, sc, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
     int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
     {
         tbx_launch_sample(SiLook{d, c}, a, chunks, first_env, envs, rows, s);

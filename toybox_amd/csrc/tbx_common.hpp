@@ -453,6 +453,9 @@ struct tbx_engine {
     int sample_chunks = 0;          // chunks of the last TBX_QUERY_LOOKAHEAD_SAMPLES (0: none yet)
     TbxDevBuf<double> search_samples_parts;  // [N][n_legal][chunks][9] partial rows of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES (64-bit integers)
     int search_samples_chunks = 0, search_samples_launches = 0;   // chunks and launches of the last TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES (0: none yet)
+    TbxDevBuf<uint8_t> beam_scratch;   // candidates and two beams of one env range of TBX_QUERY_LOOKAHEAD_BEAM (at most TBX_BEAM_SCRATCH_BYTES)
+    int beam_ranges = 0;               // env ranges of the last TBX_QUERY_LOOKAHEAD_BEAM (0: none yet)
+    int beam_range_envs = 0;           // TBX_OPT_BEAM_RANGE_ENVS (0: the engine's choice)
     TbxDevBuf<void> staging;        // device POD staging for get/set state
     struct TbxEnvCopy* envcopy = nullptr;   // TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*: the fork's scratch copy, the checkpoint store (envcopy.hip), made on first use
     GameOps* ops = nullptr;
@@ -866,6 +869,85 @@ void tbx_search_launches(int n, long long units_per_env, long long leaf_frames_p
     if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
     if (step < 1) step = 1;
     for (long long e0 = 0; e0 < n; e0 += step) f((int)e0, (int)(n - e0 < step ? n - e0 : step));
+}
+
+// ---- TBX_QUERY_LOOKAHEAD_BEAM (include/toybox_amd.h): level after level, tbx_beam_kernel plays the candidates of a level and
+// tbx_beam_select_kernel (engine.hip) ranks them per (env, first action) group and writes the kept prefixes of the next level.
+
+// A row {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width} is a valid beam row; both kernels ask here,
+// so they cannot disagree about which envs play.  `game` is a constant in the play kernel and a value in the select kernel.
+__device__ __forceinline__ bool tbx_beam_row(int game, const TbxEditArgs& a, int env, int& depth, int& objective, int& width)
+{
+    const int frames = a.geti(env, 0), hold = a.n > 1 ? a.geti(env, 1) : 1, rest = a.n > 4 ? a.geti(env, 4) : -1;
+    depth = a.n > 2 ? a.geti(env, 2) : 1;
+    objective = a.n > 3 ? a.geti(env, 3) : 0;
+    width = a.n > 9 ? a.geti(env, 9) : 1;
+    bool playable = rest == -1;
+    for (int i = 0; i < tbx_legal_count(game); i++) playable = playable || rest == tbx_legal_action(game, i);
+    return frames >= 1 && frames <= TBX_LOOKAHEAD_MAX_FRAMES && hold >= 1 && depth >= 1 && depth <= tbx_plan_max_depth(game) &&
+           (objective == 0 || objective == 1) && playable && width >= 1 && width <= TBX_BEAM_MAX_WIDTH;
+}
+// |B_level|: how many prefixes a beam of `width` keeps at `level` >= 1 -- 1, then min(width, L * the level before)
+__host__ __device__ __forceinline__ int tbx_beam_kept(int legal, int width, int level)
+{
+    int kept = 1;
+    for (int d = 2; d <= level && kept < width; d++) kept = kept * legal < width ? kept * legal : width;
+    return kept;
+}
+// One played candidate: the five fields and the code, integers as the leaf leaves them (32 bytes)
+struct TbxBeamCand {
+    TbxLookFields f;
+    uint32_t code, pad;
+};
+// The scratch of one env range, indexed by the group's number WITHIN the range: cands[group][stride * L] (candidate slot * L + k
+// is child k of the prefix in slot `slot`), beam_in / beam_out[group][stride] the kept prefixes of the level before / of this
+// level in rank order.  stride: the widest beam of the range (shared arguments: the width; per-env rows: TBX_BEAM_MAX_WIDTH).
+struct TbxBeamScratch {
+    TbxBeamCand* cands;
+    uint32_t *beam_in, *beam_out;
+    int stride;
+};
+
+// A unit is (env, first action, beam slot, digit) -- ONE leaf, so at 4 096 envs and width 4 a level is 65 536 waves (or threads)
+// and needs no loop, no reload and no running best: unit = ((env - first_env) * L + cand) * slots * kids + slot * kids + k, with
+// slots = the most prefixes any env of the launch keeps at level - 1 and kids = L (level 1: one slot, one kid, the prefix {cand}
+// itself).  An env whose row is refused, whose own depth is below `level` or whose beam has no prefix in `slot` exits at once.
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_beam_kernel(G g, TbxEditArgs a, int level, int slots, int first_env, int count, TbxBeamScratch sc)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const int lane = threadIdx.x & 63;
+    const int rel = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (rel >= count) return;
+    const int kids = level == 1 ? 1 : L, per_group = slots * kids;
+    const int group = rel / per_group, r = rel - group * per_group;
+    int slot = r / kids, k = r - slot * kids;
+    int env = first_env + group / L, cand = group % L;
+    TbxLookahead<G::GAME, true> look;
+    int depth, objective, width;
+    bool ok = look.read_plan(a, env, 1);
+    ok = tbx_beam_row(G::GAME, a, env, depth, objective, width) && ok;
+    ok = ok && level <= depth && slot < tbx_beam_kept(L, width, level - 1);
+    uint32_t code = (uint32_t)cand;
+    if (ok && level > 1) code = sc.beam_in[(size_t)group * sc.stride + slot] + (uint32_t)k * (uint32_t)tbx_plan_count(G::GAME, level - 1);
+    look.depth = level;
+    look.code = code;
+    if (G::WAVE) {
+        env = wave_uniform(env); ok = wave_uniform(ok);
+        look.uniform_plan();
+    }
+    if (!ok) return;
+    const TbxLookFields f = g.leaf(env, lane, look);
+    if (!G::WAVE || lane == 0) sc.cands[((size_t)group * sc.stride + slot) * L + k] = TbxBeamCand{f, look.code, 0u};
+}
+
+template <class G>
+void tbx_launch_beam(const G& g, const TbxEditArgs& a, int level, int slots, int first_env, int envs, const TbxBeamScratch& sc, hipStream_t s)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const long long count = (long long)envs * L * slots * (level == 1 ? 1 : L);     // (lookahead_beam, engine.hip: below 2^30)
+    const long long threads = count * (G::WAVE ? 64 : 1);
+    hipLaunchKernelGGL(tbx_beam_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, level, slots, first_env, (int)count, sc);
 }
 
 // ---- TBX_QUERY_LOOKAHEAD_SAMPLES (include/toybox_amd.h): `samples` futures per (env, first action), summed on the device.
@@ -1294,6 +1376,8 @@ struct GameOps {
     virtual int lookahead_sample(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     // TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: tbx_search_samples_kernel over the same units
     virtual int lookahead_search_samples(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    // TBX_QUERY_LOOKAHEAD_BEAM: tbx_beam_kernel over the candidates of `level` of envs [first_env, first_env + envs)
+    virtual int lookahead_beam(tbx_engine* e, const TbxEditArgs&, int /*level*/, int /*slots*/, int /*first_env*/, int /*envs*/, const struct TbxBeamScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     virtual int search_lanes() const { return 64; }
     // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
     // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The

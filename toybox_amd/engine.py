@@ -204,6 +204,33 @@ def search_args(game, n_envs, frames, hold=1, depth=1, objective=0, rest=None, s
     return _plan_rows("objective", name, n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
 
 
+def beam_args(game, n_envs, frames, depth, width, hold=1, objective=0, rest=None, seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD_BEAM: columns {frames, hold, depth, objective, rest, seed_lo, seed_hi, t,
+    env_offset, width} -- the search's with width appended; (args, per_env) as lookahead_args gives them.  Shared values are
+    range-checked here (ValueError): depth 1 .. PLAN_MAX_DEPTH (no n_legal ** depth cap), width 1 .. BEAM_MAX_WIDTH, objective
+    0 / "return" or 1 / "survival"; per-env rows are left to the device (a bad row answers zeros)."""
+    name = _game_name(game)
+    if isinstance(objective, str):
+        if objective not in SEARCH_OBJECTIVES:
+            raise ValueError("beam objective is 'return' or 'survival', got %r" % (objective,))
+        objective = SEARCH_OBJECTIVES[objective]
+    if not np.ndim(objective) and int(objective) not in (0, 1):
+        raise ValueError("beam objective is 0 (return) or 1 (survival), got %r" % (objective,))
+    if not np.ndim(depth) and not 1 <= int(depth) <= _abi.PLAN_MAX_DEPTH[name]:
+        raise ValueError("beam depth must be 1 .. %d, got %r" % (_abi.PLAN_MAX_DEPTH[name], depth))
+    if np.ndim(width) > 1 or (np.ndim(width) == 1 and len(width) != int(n_envs)):
+        raise ValueError("lookahead width is a scalar or one value per env (%d), got shape %r" % (n_envs, np.shape(width)))
+    if not np.ndim(width) and not 1 <= int(width) <= _abi.BEAM_MAX_WIDTH:
+        raise ValueError("beam width must be 1 .. %d, got %r" % (_abi.BEAM_MAX_WIDTH, width))
+    base, per_env = _plan_rows("objective", name, n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
+    if not per_env and not np.ndim(width):
+        return list(base) + [float(width)], False
+    args = np.empty((int(n_envs), 10), np.float64)
+    args[:, :9] = np.asarray(base, np.float64)
+    args[:, 9] = np.asarray(width, np.float64)
+    return args, True
+
+
 SAMPLE_FIELDS = ("samples", "ret_sum", "ret_min", "ret_max", "lives_sum", "lost", "ended", "safe_frames_sum")
 
 
@@ -548,9 +575,35 @@ class Engine:
         (self.legal_actions order) the best plan that begins with it under `objective` ("return": ret, lives, the later first
         life loss; "survival": lives, the later loss, ret; ties to the smaller code).  The five lookahead() fields [N, n_legal]
         plus code [N, n_legal] (uint64) and plan [N, n_legal, depth] (ALE ids; per-env depths: the largest, unused periods -1)."""
-        args, per_env = search_args(self.game, self.n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
+        args, _ = search_args(self.game, self.n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
+        return self._best_plans_dict(self.reduce(_abi.QUERY_LOOKAHEAD_SEARCH, args), depth)
+
+    def lookahead_beam(self, frames, depth, width, hold=1, objective="return", rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_BEAM: beam search on the device, for plans deeper than lookahead_search can enumerate (depth up to
+        PLAN_MAX_DEPTH).  For each first action a, level d keeps the `width` (1 .. BEAM_MAX_WIDTH; 1 is greedy search) best
+        prefixes of depth d under `objective`, every kept prefix is extended by every action and every extension is played over
+        the whole horizon with `rest` behind it.  The dict of lookahead_search: the five fields and code [N, n_legal] of the
+        best plan found, plan [N, n_legal, depth].  With width >= n_legal ** (depth - 2) it is lookahead_search."""
+        args, _ = beam_args(self.game, self.n_envs, frames, depth, width, hold, objective, rest, seed, t, env_offset)
+        return self._best_plans_dict(self.reduce(_abi.QUERY_LOOKAHEAD_BEAM, args), depth)
+
+    @property
+    def beam_ranges(self):
+        """into how many env ranges the last lookahead_beam was cut (0: none yet)"""
+        return self.get_option(_abi.OPT_BEAM_RANGES)
+
+    @property
+    def beam_range_envs(self):
+        """at most this many envs per range of a lookahead_beam, on top of the engine's budgets (0: the engine's choice)"""
+        return self.get_option(_abi.OPT_BEAM_RANGE_ENVS)
+
+    @beam_range_envs.setter
+    def beam_range_envs(self, envs):
+        self.set_option(_abi.OPT_BEAM_RANGE_ENVS, envs)
+
+    def _best_plans_dict(self, out, depth):
         L = len(self.legal_actions)
-        out = self.reduce(_abi.QUERY_LOOKAHEAD_SEARCH, args).reshape(self.n_envs, L, 6)
+        out = out.reshape(self.n_envs, L, 6)
         res = self._lookahead_dict(out[..., :5])
         res["code"] = out[..., 5].astype(np.uint64)
         d = np.broadcast_to(np.clip(np.asarray(depth, np.int64), 0, _abi.PLAN_MAX_DEPTH[self.game]), (self.n_envs,))

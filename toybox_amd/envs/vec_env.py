@@ -93,8 +93,19 @@ def _search(env, frames, hold, depth, objective, rest, seed, t):
     """Engine.lookahead_search for an adapter: `plan` comes back as action indices (the digits of the code: the action set is the
     engine's legal set in its order), and the winner among an env's rows under the same objective -- ties to the smaller code --
     is added as best_action [num_envs] and best_plan [num_envs, depth]"""
-    from ..engine import plan_digits
     out = env.engine.lookahead_search(frames, int(depth), hold=hold, objective=objective, rest=_ale(env, rest), seed=seed, t=t)
+    return _with_best(env, out, depth, objective)
+
+
+def _beam(env, frames, hold, depth, width, objective, rest, seed, t):
+    """Engine.lookahead_beam for an adapter: as _search, with the beam's width"""
+    out = env.engine.lookahead_beam(frames, int(depth), int(width), hold=hold, objective=objective, rest=_ale(env, rest), seed=seed, t=t)
+    return _with_best(env, out, depth, objective)
+
+
+def _with_best(env, out, depth, objective):
+    """the rows of a search or a beam: plan as action indices, best_action and best_plan added (one lexsort per call)"""
+    from ..engine import plan_digits
     out["plan"] = plan_digits(len(env._action_set), out["code"], int(depth))
     loss = np.where(out["life_lost_at"] < 0, 1 << 30, out["life_lost_at"])
     keys = (out["ret"], out["lives"], loss) if objective in ("return", 0) else (out["lives"], loss, out["ret"])
@@ -341,6 +352,14 @@ class ToyboxVecEnv:
         if self._in_flight is not None or self._pending is not None:
             self.step_wait()
         return _search(self, int(steps), 1, depth, objective, rest, seed, t)
+
+    def beam_search(self, steps, depth, width, objective="return", rest=None, seed=0, t=0):
+        """search() for plans deeper than it can enumerate (Engine.lookahead_beam): per first action index and level the `width`
+        best action sequences are kept and extended by every action.  The dict of search(); with width 1 it is greedy search,
+        with width >= n_actions ** (depth - 2) it is search()."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _beam(self, int(steps), 1, depth, width, objective, rest, seed, t)
 
     def lookahead_samples(self, steps, samples, rest=None, seed=0, t=0, salt=0, objective="return"):
         """`samples` random futures of `steps` steps per env and first action index, summed on the device without taking them
@@ -692,6 +711,13 @@ class ToyboxPreprocVecEnv:
         if self._in_flight is not None:
             self.step_wait()
         return _search(self, int(steps) * self._skip, self._skip, depth, objective, rest, seed, t)
+
+    def beam_search(self, steps, depth, width, objective="return", rest=None, seed=0, t=0):
+        """ToyboxVecEnv.beam_search in agent steps: steps x skip raw frames, every action held for skip frames; raw frames, no
+        wrapper, as in lookahead().  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _beam(self, int(steps) * self._skip, self._skip, depth, width, objective, rest, seed, t)
 
     def lookahead_samples(self, steps, samples, rest=None, seed=0, t=0, salt=0, objective="return"):
         """ToyboxVecEnv.lookahead_samples in agent steps: steps x skip raw frames, every action held for skip frames; raw frames,

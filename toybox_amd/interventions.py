@@ -257,6 +257,15 @@ class BatchIntervention:
                                            rest=self._full(rest, -1), seed=self._full(seed, 0), t=self._full(t, 0), env_offset=self._full(env_offset, 0))
         return {k: v[self.first:self.first + self.count] for k, v in out.items()}
 
+    def lookahead_beam(self, frames, depth, width, hold=1, objective="return", rest=None, seed=0, t=0, env_offset=0):
+        """Engine.lookahead_beam over the range: the five fields and code [count, n_legal], plan [count, n_legal, depth]"""
+        self._flush()
+        if np.ndim(objective):
+            objective = self._full(objective, 0)
+        out = self.engine.lookahead_beam(self._full(frames, 1), self._full(depth, 1), self._full(width, 1), hold=self._full(hold, 1), objective=objective,
+                                         rest=self._full(rest, -1), seed=self._full(seed, 0), t=self._full(t, 0), env_offset=self._full(env_offset, 0))
+        return {k: v[self.first:self.first + self.count] for k, v in out.items()}
+
     def lookahead_samples(self, frames, samples, hold=1, salt=0, rest=None, seed=0, t=0, env_offset=0):
         """Engine.lookahead_samples over the range: the eight fields, each [count, n_legal]"""
         self._flush()
