@@ -756,6 +756,40 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
  *   than 10 arguments.  In per-env rows such an env's output is zeros -- frames run 0 -- and the other envs are answered. */
 #define TBX_BEAM_MAX_WIDTH 64
 #define TBX_QUERY_LOOKAHEAD_BEAM 156  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width} -> 6 * n_legal(game) */
+/* Beam search over sampled futures: the levels of TBX_QUERY_LOOKAHEAD_BEAM, every candidate judged on the same `samples` futures
+ * as TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES judges its plans -- deep plans by expected outcome.  Columns 0 .. 9 are the beam's, with the
+ * same defaults for trailing arguments left out; `samples` (default 1) and `salt` (default 0) are appended.
+ *   For every env and every first action a in legal-set order, with L = n_legal(game), the levels are the beam's:
+ *     B_1 = {a};  C_d = { c + k * L^(d-1) : c in B_(d-1), k = 0 .. L-1 } for d = 2 .. depth (C_1 = {a});
+ *     B_d = the min(width, |C_d|) best of C_d.
+ *   Candidate x of level d is valued by the eight integer sums of TBX_QUERY_LOOKAHEAD_SAMPLES over the futures s = 0 .. samples-1,
+ *   future s being exactly TBX_QUERY_LOOKAHEAD_PLAN {frames, hold, d, x, rest, seed_s, t, env_offset} played from the env's state
+ *   with its game RNG salted by salt_s; seed_s = splitmix64((seed + s) mod 2^64) and salt_s = salt == 0 ? 0 : salt + s, applied in
+ *   registers and never stored, are those of queries 154 / 155.  COMMON RANDOM NUMBERS: seed_s and salt_s depend on s alone, not on
+ *   the candidate and not on the level, so all candidates of an env, at every level, meet the same futures.
+ *   Best is the order of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: objective 0 (return) takes the larger ret_sum, then the smaller lost,
+ *   then the larger safe_frames_sum, then the smaller code; objective 1 (survival) the smaller lost, then the larger
+ *   safe_frames_sum, then the larger ret_sum, then the smaller code.  Codes within a level are distinct, so the order is total and
+ *   the kept set does not depend on how the work is cut.
+ *   Out: row out[env][a][0 .. 8] = the eight sums (samples, ret_sum, ret_min, ret_max, lives_sum, lost, ended, safe_frames_sum) of the
+ *   best candidate of C_depth, 64-bit integers converted to binary64 once at the store, then [8] its code.
+ *   It follows that with depth = 1 columns 0 .. 7 are the row of TBX_QUERY_LOOKAHEAD_SAMPLES {frames, hold, samples, salt, rest,
+ *   seed, t, env_offset}; that with width >= L^(depth-2) and the caps of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES met the row is that
+ *   query's row, bit for bit; and that with salt = 0 the returned code fed to TBX_QUERY_LOOKAHEAD_PLAN under seed_s, summed over s,
+ *   gives the row's sums.  With samples = 1 it is NOT the row of TBX_QUERY_LOOKAHEAD_BEAM: the order is another (the lost flag, not
+ *   lives) and the one future is played under splitmix64(seed), not under seed.
+ *   Ranges: the beam's (1 <= depth <= TBX_PLAN_MAX_DEPTH(game), 1 <= width <= TBX_BEAM_MAX_WIDTH), 1 <= samples <=
+ *   TBX_LOOKAHEAD_MAX_SAMPLES, the salt ranges of TBX_QUERY_LOOKAHEAD_SAMPLES, and one cap: the candidates of the widest level times
+ *   the samples, L * |B_(depth-1)| * (depth == 1 ? 1 : L) * samples with |B_0| = |B_1| = 1 and |B_d| = min(width, L * |B_(d-1)|),
+ *   must not exceed TBX_LOOKAHEAD_MAX_LEAVES.
+ *   Every future is replayed from the env's live state in registers, level after level on the calling stream; a select pass between
+ *   two levels ranks a group's candidates; the samples of a level may be cut into chunks (TBX_OPT_BEAM_SAMPLES_CHUNKS) and large
+ *   batches into env ranges (TBX_OPT_BEAM_SAMPLES_RANGES).  Neither changes any output bit.  "Nothing in the engine changes" is the
+ *   lookahead's sentence, verbatim.
+ *   TBX_E_INVALID, nothing launched: a shared value out of the ranges above (frames, hold, depth, objective, rest, width, samples,
+ *   salt, the leaf cap), more than 12 arguments.  In per-env rows such an env's whole output is nine zeros -- field 0 = 0 -- and
+ *   the other envs are answered. */
+#define TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES 157  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width, samples, salt} -> 9 * n_legal(game) */
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);
@@ -1062,8 +1096,15 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
 /* read-only: into how many env ranges the last TBX_QUERY_LOOKAHEAD_BEAM was cut (0: none yet; a refused query leaves it standing) */
 #define TBX_OPT_BEAM_RANGES 109
 /* at most this many envs per range of a TBX_QUERY_LOOKAHEAD_BEAM, on top of the engine's budgets; 0 (default): the engine's choice.
- * It changes no output bit. */
+ * It changes no output bit.  It caps the ranges of a TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES too. */
 #define TBX_OPT_BEAM_RANGE_ENVS 110
+/* read-only: into how many env ranges the last TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES was cut, and the largest number of sample chunks
+ * any of its levels used (0: none yet; a refused query leaves both standing) */
+#define TBX_OPT_BEAM_SAMPLES_RANGES 111
+#define TBX_OPT_BEAM_SAMPLES_CHUNKS 112
+/* at most this many sample chunks per level of a TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES; 0 (default): the engine's choice, 1: never cut.
+ * It changes no output bit. */
+#define TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS 113
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
 /* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could

@@ -2307,6 +2307,12 @@ struct AmiOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+    int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int chunks, int first_env, int envs, const TbxBeamSamplesScratch& sc, hipStream_t s) override
+    {
+        tbx_launch_beam_samples(AmiLook{d}, a, level, slots, chunks, first_env, envs, sc, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
     int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
     {
         tbx_launch_sample(AmiLook{d}, a, chunks, first_env, envs, rows, s);

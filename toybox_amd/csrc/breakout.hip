@@ -2442,6 +2442,13 @@ struct BreakoutOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+    int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int chunks, int first_env, int envs, const TbxBeamSamplesScratch& sc, hipStream_t s) override
+    {
+        if (!custom && use_tpe) tbx_launch_beam_samples(BrkTLook{d, cfg_dev}, a, level, slots, chunks, first_env, envs, sc, s);
+        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_beam_samples(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, level, slots, chunks, first_env, envs, sc, s); });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
     int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
     {
         if (!custom && use_tpe) tbx_launch_sample(BrkTLook{d, cfg_dev}, a, chunks, first_env, envs, rows, s);

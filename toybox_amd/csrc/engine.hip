@@ -1152,6 +1152,7 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_LOOKAHEAD_BEAM: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
     default: return TBX_E_INVALID;
     }
 }
@@ -1480,8 +1481,175 @@ static int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, double*
     return TBX_OK;
 }
 
+// TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES, between two levels: one wave per (env, first action) group of envs from first_env on, as
+// tbx_beam_select_kernel.  Per candidate it merges the `chunks` partial records of the play launch (TbxSampleSums::merge: integers,
+// so the result does not depend on the cut; a chunk without a sample is skipped) and stages in LDS only what the order reads --
+// TbxSearchSamplesKey and the code, 24 bytes a candidate -- then ranks by COUNTING under tbx_search_samples_better and writes the
+// candidate of rank r < width to slot r of the next beam; on the env's last level rank 0 merges its full eight sums from scratch
+// and stores the row of 9.  A refused env's rows are zeros, written at level 1; an env whose depth is below `level` idles.
+struct TbxBeamSamplesCand {
+    TbxSearchSamplesKey key;
+    uint32_t code;
+};
+__global__ __launch_bounds__(64) void tbx_beam_samples_select_kernel(TbxEditArgs a, int game, int level, int slots, int chunks, int first_env, TbxBeamSamplesScratch sc,
+                                                                     double* __restrict__ out)
+{
+    __shared__ TbxBeamSamplesCand lds[TBX_BEAM_MAX_CANDS];
+    const int L = tbx_legal_count(game);
+    const int group = blockIdx.x, lane = threadIdx.x;
+    const int env = first_env + group / L;
+    double* const o = out + ((size_t)first_env * L + group) * 9;
+    int depth, objective, width, S;
+    uint64_t salt;
+    if (!tbx_beam_samples_row(game, a, env, depth, objective, width, S, salt)) {
+        if (level == 1 && lane < 9) o[lane] = 0.0;
+        return;
+    }
+    if (level > depth) return;
+    const int kids = level == 1 ? 1 : L;
+    const int n = tbx_beam_kept(L, width, level - 1) * kids;                     // at most width * L
+    const long long* const recs = sc.recs + (size_t)group * slots * kids * chunks * 9;
+    for (int i = lane; i < n; i += 64) {
+        const long long* const p = recs + (size_t)i * chunks * 9;
+        TbxSampleSums sum;
+        for (int c = 0; c < chunks; c++) sum.merge(p + (size_t)c * 9);
+        lds[i] = TbxBeamSamplesCand{TbxSearchSamplesKey{sum.ret_sum, (int)sum.lost, (int)sum.safe_sum}, (uint32_t)p[8]};
+    }
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) {
+        const TbxBeamSamplesCand x = lds[i];
+        int rank = 0;
+        for (int j = 0; j < n; j++) rank += j != i && tbx_search_samples_better(objective, lds[j].key, lds[j].code, x.key, x.code) ? 1 : 0;
+        if (level < depth && rank < width) sc.beam_out[(size_t)group * sc.stride + rank] = x.code;
+        if (level == depth && rank == 0) {
+            const long long* const p = recs + (size_t)i * chunks * 9;
+            TbxSampleSums win;
+            for (int c = 0; c < chunks; c++) win.merge(p + (size_t)c * 9);
+            tbx_search_samples_store(o, win, x.code, false, false);
+        }
+    }
+}
+
+// What a TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES is budgeted for: the largest frames, depth, width and samples of a valid row and the most
+// leaves (candidates of the last level x samples) a valid row plays in one level
+struct TbxBeamSamplesBounds {
+    long long frames;
+    int depth, width, samples;
+    long long leaves;
+};
+// tbx_reduce has per-env rows on the host: the bounds of the rows that tbx_beam_samples_values accepts (none: the smallest query)
+static TbxBeamSamplesBounds beam_samples_scan(const tbx_engine* e, const double* rows, int n)
+{
+    const int L = tbx_legal_count(e->game);
+    TbxBeamSamplesBounds b{1, 1, 1, 1, 1};
+    for (int env = 0; env < e->n; env++) {
+        const double* const r = rows + (size_t)env * n;
+        auto geti = [&](int i, int otherwise) { return i < n ? TbxEditArgs::to_int(r[i]) : otherwise; };
+        const int frames = geti(0, 0), depth = geti(2, 1), width = geti(9, 1), samples = geti(10, 1);
+        if (!tbx_beam_samples_values(e->game, frames, geti(1, 1), depth, geti(3, 0), geti(4, -1), width, samples, n > 11 ? r[11] : 0.0)) continue;
+        const long long leaves = (long long)L * tbx_beam_kept(L, width, depth - 1) * (depth == 1 ? 1 : L) * samples;
+        if (frames > b.frames) b.frames = frames;
+        if (depth > b.depth) b.depth = depth;
+        if (width > b.width) b.width = width;
+        if (samples > b.samples) b.samples = samples;
+        if (leaves > b.leaves) b.leaves = leaves;
+    }
+    return b;
+}
+
+// TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: shared values are refused here, before anything is launched; per-env rows are met by the
+// kernels.  Env ranges keep a level's play launch under tbx_search_samples_budget leaf-frames (it runs the sample kernel's loop, so
+// that kernel's measured rates apply) and TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units and the scratch under TBX_BEAM_SCRATCH_BYTES
+// (beam_scratch is shared with TBX_QUERY_LOOKAHEAD_BEAM: both run in stream order).  Per-env rows are budgeted by `rows` where the
+// host form has scanned them, else as the largest valid row with every level up to TBX_PLAN_MAX_DEPTH run.  Each level cuts the
+// samples into the smallest power of two of chunks that brings its units to TBX_SEARCH_FILL_WAVES waves -- level 1 has one
+// candidate per group --, at most the largest power of two <= samples and at most TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS where set; a
+// chunked level has fewer than 2 * TBX_SEARCH_FILL_WAVES * 64 units, so its records (9.4 MB at most) stay under the scratch bound
+// too.  Within a range, per level: play, select -- all on `s`, in stream order, no host synchronisation.
+static int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, const TbxBeamSamplesBounds* rows, double* out_dev, hipStream_t s)
+{
+    const int L = tbx_legal_count(e->game);
+    if (a.n < 1 || a.n > 12) return e->fail(TBX_E_INVALID, "beam over samples takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width, samples, salt]}");
+    // per-env rows the host has not seen: the most a valid row can ask for
+    TbxBeamSamplesBounds b{TBX_LOOKAHEAD_MAX_FRAMES, tbx_plan_max_depth(e->game), TBX_BEAM_MAX_WIDTH, TBX_LOOKAHEAD_MAX_SAMPLES, TBX_LOOKAHEAD_MAX_LEAVES};
+    if (!a.per_env) {
+        auto playable = [&](double v) {
+            if (v == -1.0) return true;
+            for (int i = 0; i < L; i++)
+                if (v == (double)tbx_legal_action(e->game, i)) return true;
+            return false;
+        };
+        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        const double dp = a.n > 2 ? a.v[2] : 1.0, w = a.n > 9 ? a.v[9] : 1.0, count = a.n > 10 ? a.v[10] : 1.0, salt = a.n > 11 ? a.v[11] : 0.0;
+        if (!(dp >= 1.0 && dp <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "beam over samples: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
+        if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "beam over samples: objective must be 0 (return) or 1 (survival)");
+        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        if (!(w >= 1.0 && w <= (double)TBX_BEAM_MAX_WIDTH)) return e->fail(TBX_E_INVALID, "beam over samples: width must be 1 .. TBX_BEAM_MAX_WIDTH");
+        if (!(count >= 1.0 && count <= (double)TBX_LOOKAHEAD_MAX_SAMPLES)) return e->fail(TBX_E_INVALID, "beam over samples: samples must be 1 .. TBX_LOOKAHEAD_MAX_SAMPLES");
+        if (!(salt >= 0.0 && salt < 4294967296.0)) return e->fail(TBX_E_INVALID, "beam over samples: salt must be 0 .. 2^32 - 1");
+        b.frames = TbxEditArgs::to_int(a.v[0]);
+        b.depth = TbxEditArgs::to_int(dp);
+        b.width = TbxEditArgs::to_int(w);
+        b.samples = TbxEditArgs::to_int(count);
+        if ((uint64_t)salt != 0 && (uint64_t)salt + (uint64_t)b.samples - 1 >= (1ull << 32)) return e->fail(TBX_E_INVALID, "beam over samples: salt + samples - 1 must stay below 2^32");
+        b.leaves = (long long)L * tbx_beam_kept(L, b.width, b.depth - 1) * (b.depth == 1 ? 1 : L) * b.samples;
+        if (b.leaves > (long long)TBX_LOOKAHEAD_MAX_LEAVES)
+            return e->fail(TBX_E_INVALID, "beam over samples: the candidates of the last level x samples must not exceed TBX_LOOKAHEAD_MAX_LEAVES");
+    } else if (rows) b = *rows;
+    const int lanes = e->ops->search_lanes();
+    // per env: L groups of at most width * L candidates, and two beams of width codes per group
+    const long long units_per_env = (long long)L * b.width * L;
+    const size_t beam_bytes_per_env = 2 * (size_t)L * b.width * sizeof(uint32_t), rec_bytes = 9 * sizeof(long long);
+    const size_t bytes_per_env = (size_t)units_per_env * rec_bytes + beam_bytes_per_env;
+    long long step = tbx_search_samples_budget(e->game, lanes) / (b.leaves * b.frames);
+    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
+    if (step > (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env)) step = (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env);
+    if (e->beam_range_envs > 0 && step > e->beam_range_envs) step = e->beam_range_envs;
+    if (step > e->n) step = e->n;
+    if (step < 1) step = 1;
+    const long long want = TBX_SEARCH_FILL_WAVES * (64 / lanes);
+    auto level_units = [&](long long envs, int level) { return envs * L * tbx_beam_kept(L, b.width, level - 1) * (level == 1 ? 1 : L); };
+    auto level_chunks = [&](long long envs, int level) {
+        const long long units = level_units(envs, level);
+        int chunks = 1;
+        while (units * chunks < want && 2 * chunks <= b.samples && (e->beam_samples_max_chunks == 0 || 2 * chunks <= e->beam_samples_max_chunks)) chunks *= 2;
+        return chunks;
+    };
+    // the scratch is sized for the level where candidates x chunks is largest, over the full ranges and the last, shorter one
+    long long most_units = 0;
+    for (long long envs : {step, (long long)e->n % step})
+        for (int level = 1; envs > 0 && level <= b.depth; level++) {
+            const long long units = level_units(envs, level) * level_chunks(envs, level);
+            if (units > most_units) most_units = units;
+        }
+    const size_t recs_bytes = (size_t)most_units * rec_bytes;
+    EHIP(e->beam_scratch.reserve(recs_bytes + beam_bytes_per_env * (size_t)step, e->stream, s));
+    TbxBeamSamplesScratch sc;
+    sc.stride = b.width;
+    sc.recs = reinterpret_cast<long long*>(e->beam_scratch.p);
+    sc.beam_in = reinterpret_cast<uint32_t*>(e->beam_scratch.p + recs_bytes);
+    sc.beam_out = sc.beam_in + (size_t)L * b.width * (size_t)step;
+    int ranges = 0, most_chunks = 1;
+    for (long long env0 = 0; env0 < e->n; env0 += step, ranges++) {
+        const int envs = (int)(e->n - env0 < step ? e->n - env0 : step);
+        for (int level = 1; level <= b.depth; level++) {
+            const int slots = tbx_beam_kept(L, b.width, level - 1), chunks = level_chunks(envs, level);
+            if (chunks > most_chunks) most_chunks = chunks;
+            int rc = e->ops->lookahead_beam_samples(e, a, level, slots, chunks, (int)env0, envs, sc, s);
+            if (rc) return rc;
+            hipLaunchKernelGGL(tbx_beam_samples_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, level, slots, chunks, (int)env0, sc, out_dev);
+            uint32_t* const t = sc.beam_in; sc.beam_in = sc.beam_out; sc.beam_out = t;
+        }
+    }
+    e->beam_samples_ranges = ranges;
+    e->beam_samples_chunks = most_chunks;
+    EHIP(hipGetLastError());
+    return TBX_OK;
+}
+
 // the queries every game has (the engine's own), else the game's
-static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s)
+static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s, const TbxBeamSamplesBounds* beam_samples_rows = nullptr)
 {
     if (query == TBX_QUERY_LOOKAHEAD || query == TBX_QUERY_LOOKAHEAD_ALL) {
         // shared values are refused here, before anything is launched; per-env rows are met by the kernel (that env's row: zeros)
@@ -1504,6 +1672,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
     if (query == TBX_QUERY_LOOKAHEAD_BEAM) return lookahead_beam(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_SAMPLES) return lookahead_samples(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES) return lookahead_search_samples(e, a, out_dev, s);
+    if (query == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES) return lookahead_beam_samples(e, a, beam_samples_rows, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     return checkpoint_valid(e, a, out_dev, s);
 }
@@ -1579,7 +1748,11 @@ int tbx_reduce(tbx_engine* e, int query, const double* args, int n_args, int per
     if (rc) return rc;
     const size_t bytes = sizeof(double) * (size_t)e->n * (size_t)width;
     EHIP(e->reduce_out.reserve(bytes, e->stream));
-    rc = engine_reduce(e, query, a, e->reduce_out.p, width, e->stream);
+    // per-env rows of a beam over samples are on the host here: budget for the rows there are, not for the largest row there could be
+    TbxBeamSamplesBounds rows_seen;
+    const bool scanned = query == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES && a.per_env && n_args <= 12;
+    if (scanned) rows_seen = beam_samples_scan(e, args, n_args);
+    rc = engine_reduce(e, query, a, e->reduce_out.p, width, e->stream, scanned ? &rows_seen : nullptr);
     if (rc) return rc;
     EHIP(hipMemcpyAsync(out_host, e->reduce_out.p, bytes, hipMemcpyDeviceToHost, e->stream));
     EHIP(hipStreamSynchronize(e->stream));
@@ -1649,6 +1822,11 @@ int tbx_set_option(tbx_engine* e, int option, int value)
         e->beam_range_envs = value;
         return TBX_OK;
     }
+    if (option == TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS) {   // read by the host when a level's samples are cut: nothing in flight depends on it
+        if (value < 0 || value > TBX_LOOKAHEAD_MAX_SAMPLES) return e->fail(TBX_E_INVALID, "option value out of range");
+        e->beam_samples_max_chunks = value;
+        return TBX_OK;
+    }
     bool ok = false;
     switch (option) {
     case TBX_OPT_PIPELINE: ok = value >= 0 && value <= 3; break;
@@ -1685,6 +1863,9 @@ int tbx_get_option(tbx_engine* e, int option, int* value_out)
     if (value_out && option == TBX_OPT_SEARCH_SAMPLES_CHUNKS) { *value_out = e->search_samples_chunks; return TBX_OK; }
     if (value_out && option == TBX_OPT_BEAM_RANGES) { *value_out = e->beam_ranges; return TBX_OK; }
     if (value_out && option == TBX_OPT_BEAM_RANGE_ENVS) { *value_out = e->beam_range_envs; return TBX_OK; }
+    if (value_out && option == TBX_OPT_BEAM_SAMPLES_RANGES) { *value_out = e->beam_samples_ranges; return TBX_OK; }
+    if (value_out && option == TBX_OPT_BEAM_SAMPLES_CHUNKS) { *value_out = e->beam_samples_chunks; return TBX_OK; }
+    if (value_out && option == TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS) { *value_out = e->beam_samples_max_chunks; return TBX_OK; }
     if (value_out && option == TBX_OPT_SEARCH_SAMPLES_LAUNCHES) { *value_out = e->search_samples_launches; return TBX_OK; }
     if (option < 0 || option >= TBX_OPT_COUNT || !value_out) return e->fail(TBX_E_INVALID, "unknown option");
     *value_out = e->opt[option];

@@ -456,6 +456,8 @@ struct tbx_engine {
     TbxDevBuf<uint8_t> beam_scratch;   // candidates and two beams of one env range of TBX_QUERY_LOOKAHEAD_BEAM (at most TBX_BEAM_SCRATCH_BYTES)
     int beam_ranges = 0;               // env ranges of the last TBX_QUERY_LOOKAHEAD_BEAM (0: none yet)
     int beam_range_envs = 0;           // TBX_OPT_BEAM_RANGE_ENVS (0: the engine's choice)
+    int beam_samples_ranges = 0, beam_samples_chunks = 0;   // env ranges, and the most sample chunks of a level, of the last TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES (0: none yet)
+    int beam_samples_max_chunks = 0;   // TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS (0: the engine's choice)
     TbxDevBuf<void> staging;        // device POD staging for get/set state
     struct TbxEnvCopy* envcopy = nullptr;   // TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*: the fork's scratch copy, the checkpoint store (envcopy.hip), made on first use
     GameOps* ops = nullptr;
@@ -1188,6 +1190,114 @@ int tbx_search_samples_launches(int n, long long units_per_env, long long leaf_f
     return launches;
 }
 
+// ---- TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES (include/toybox_amd.h): the beam's levels, every candidate valued by the eight sums of its
+// `samples` futures (common random numbers: seed_s and salt_s depend on s alone) and ranked by tbx_search_samples_better.
+// tbx_beam_samples_kernel plays, tbx_beam_samples_select_kernel (engine.hip) merges, ranks and writes the next beam.
+
+// The values of a row {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width, samples, salt} are a valid row:
+// the beam's ranges, the sample count and salt ranges of TBX_QUERY_LOOKAHEAD_SAMPLES and the leaf cap -- the candidates of the
+// widest level (the last) times the samples stay at or below TBX_LOOKAHEAD_MAX_LEAVES.  Both kernels ask here through
+// tbx_beam_samples_row, and so does the host where it has the rows (tbx_reduce), so they cannot disagree about which envs play.
+__host__ __device__ __forceinline__ bool tbx_beam_samples_values(int game, int frames, int hold, int depth, int objective, int rest, int width, int samples, double salt)
+{
+    const int L = tbx_legal_count(game);
+    bool playable = rest == -1;
+    for (int i = 0; i < L; i++) playable = playable || rest == tbx_legal_action(game, i);
+    bool ok = frames >= 1 && frames <= TBX_LOOKAHEAD_MAX_FRAMES && hold >= 1 && depth >= 1 && depth <= tbx_plan_max_depth(game) &&
+              (objective == 0 || objective == 1) && playable && width >= 1 && width <= TBX_BEAM_MAX_WIDTH;
+    ok = ok && samples >= 1 && samples <= TBX_LOOKAHEAD_MAX_SAMPLES && salt >= 0.0 && salt < 4294967296.0;
+    ok = ok && ((uint64_t)salt == 0 || (uint64_t)salt + (uint64_t)samples - 1 < (1ull << 32));
+    return ok && (long long)L * tbx_beam_kept(L, width, depth - 1) * (depth == 1 ? 1 : L) * samples <= (long long)TBX_LOOKAHEAD_MAX_LEAVES;
+}
+__device__ __forceinline__ bool tbx_beam_samples_row(int game, const TbxEditArgs& a, int env, int& depth, int& objective, int& width, int& samples, uint64_t& salt)
+{
+    depth = a.n > 2 ? a.geti(env, 2) : 1;
+    objective = a.n > 3 ? a.geti(env, 3) : 0;
+    width = a.n > 9 ? a.geti(env, 9) : 1;
+    samples = a.n > 10 ? a.geti(env, 10) : 1;
+    const double salt_arg = a.n > 11 ? a.get(env, 11) : 0.0;
+    const bool ok = tbx_beam_samples_values(game, a.geti(env, 0), a.n > 1 ? a.geti(env, 1) : 1, depth, objective, a.n > 4 ? a.geti(env, 4) : -1, width, samples, salt_arg);
+    salt = ok ? (uint64_t)salt_arg : 0ull;
+    return ok;
+}
+// The scratch of one env range: recs[unit][9], one record per unit of the level's play launch in the launch's own unit order (the
+// eight sums of the unit's sample chunk as 64-bit integers, then the candidate's code); beam_in / beam_out[group][stride] as in
+// TbxBeamScratch, the group's number counted WITHIN the range.
+struct TbxBeamSamplesScratch {
+    long long* recs;
+    uint32_t *beam_in, *beam_out;
+    int stride;
+};
+
+// A unit is (env, first action, beam slot, digit, sample chunk), indexed as tbx_beam_kernel indexes its units with the chunk
+// innermost: unit = (((env - first_env) * L + cand) * slots * kids + slot * kids + k) * chunks + chunk.  It plays the futures
+// [chunk * S / chunks, (chunk + 1) * S / chunks) of ONE candidate -- the loop of tbx_sample_kernel: reload through the opaque env
+// index, salt, play, add (wave forms: in SGPRs) -- and stores ONE record at its own unit index.  No loop over candidates, no
+// running best, nothing between lanes.  A chunk without a sample (an env with fewer samples than the launch has chunks) stores an
+// empty record; an env whose row is refused, whose own depth is below `level` or whose beam has no prefix in `slot` exits at once.
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_beam_samples_kernel(G g, TbxEditArgs a, int level, int slots, int chunks, int first_env, int count, TbxBeamSamplesScratch sc)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const int lane = threadIdx.x & 63;
+    const int rel = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (rel >= count) return;
+    const int kids = level == 1 ? 1 : L, per_group = slots * kids * chunks;
+    const int group = rel / per_group, r = rel - group * per_group;
+    const int c = r / chunks;
+    int chunk = r - c * chunks;
+    const int slot = c / kids, k = c - slot * kids;
+    int env = first_env + group / L;
+    const int cand = group % L;
+    TbxLookahead<G::GAME, true> look;
+    int depth, objective, width, S;
+    uint64_t salt;
+    bool ok = look.read_plan(a, env, 1);
+    ok = tbx_beam_samples_row(G::GAME, a, env, depth, objective, width, S, salt) && ok;
+    ok = ok && level <= depth && slot < tbx_beam_kept(L, width, level - 1);
+    uint32_t code = (uint32_t)cand;
+    if (ok && level > 1) code = sc.beam_in[(size_t)group * sc.stride + slot] + (uint32_t)k * (uint32_t)tbx_plan_count(G::GAME, level - 1);
+    look.depth = level;
+    look.code = code;
+    uint64_t seed = (uint64_t)a.getu(env, 5) | ((uint64_t)a.getu(env, 6) << 32);
+    uint64_t env_key = ((uint64_t)a.getu(env, 8) + (uint64_t)env) << 32;
+    if (G::WAVE) {
+        env = wave_uniform(env); chunk = wave_uniform(chunk); ok = wave_uniform(ok); S = wave_uniform(S);
+        salt = wave_uniform64(salt); seed = wave_uniform64(seed); env_key = wave_uniform64(env_key);
+        look.uniform_plan();
+    }
+    if (!ok) return;
+    TbxSampleSums sum;
+    const int lo = (int)((long long)chunk * S / chunks), hi = (int)((long long)(chunk + 1) * S / chunks);
+    for (int s = lo; s < hi; s++) {
+        look.key = tbx_splitmix64(seed + (uint64_t)s) ^ env_key;
+        // every future RELOADS its env through an opaque index, as every sample of tbx_sample_kernel does (profiles/search.md)
+        int env_now = env;
+        if (G::WAVE) asm volatile("" : "+s"(env_now));
+        else asm volatile("" : "+v"(env_now));
+        TbxLookFields f = g.leaf(env_now, lane, look, salt ? salt + (uint64_t)s : 0ull);
+        if (G::WAVE) {
+            f.ret = (long long)wave_uniform64((uint64_t)f.ret);
+            f.lives = wave_uniform(f.lives); f.frames_run = wave_uniform(f.frames_run); f.lost_at = wave_uniform(f.lost_at);
+        }
+        sum.add(f);
+    }
+    if (!G::WAVE || lane == 0) {
+        long long* const p = sc.recs + (size_t)rel * 9;
+        sum.store_partial(p);
+        p[8] = (long long)look.code;
+    }
+}
+
+template <class G>
+void tbx_launch_beam_samples(const G& g, const TbxEditArgs& a, int level, int slots, int chunks, int first_env, int envs, const TbxBeamSamplesScratch& sc, hipStream_t s)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const long long count = (long long)envs * L * slots * (level == 1 ? 1 : L) * chunks;     // (lookahead_beam_samples, engine.hip: below 2^30)
+    const long long threads = count * (G::WAVE ? 64 : 1);
+    hipLaunchKernelGGL(tbx_beam_samples_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, level, slots, chunks, first_env, (int)count, sc);
+}
+
 // One per-env array of an engine as the env-copy kernels see it (envcopy.hip: fork, checkpoint save and restore) -- `fields`
 // planes of N rows of row_bytes each, [fields][N][row_bytes].  A struct-of-arrays scalar [F][N] is F planes of 4- or 8-byte rows,
 // an env-major table [N][R] one plane of R-byte rows, the plane ring `stack` planes of out_h * out_w bytes.  rng_words > 0: every
@@ -1378,6 +1488,8 @@ struct GameOps {
     virtual int lookahead_search_samples(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     // TBX_QUERY_LOOKAHEAD_BEAM: tbx_beam_kernel over the candidates of `level` of envs [first_env, first_env + envs)
     virtual int lookahead_beam(tbx_engine* e, const TbxEditArgs&, int /*level*/, int /*slots*/, int /*first_env*/, int /*envs*/, const struct TbxBeamScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    // TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: tbx_beam_samples_kernel over the candidates of `level`, each cut into `chunks` sample chunks
+    virtual int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs&, int /*level*/, int /*slots*/, int /*chunks*/, int /*first_env*/, int /*envs*/, const struct TbxBeamSamplesScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     virtual int search_lanes() const { return 64; }
     // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
     // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The

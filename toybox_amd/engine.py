@@ -292,6 +292,48 @@ def search_samples_args(game, n_envs, frames, depth, samples, hold=1, objective=
     return args, True
 
 
+def beam_kept(legal, width, level):
+    """|B_level| of a beam: 1, then min(width, legal * the level before) (tbx_beam_kept)"""
+    kept = 1
+    for _ in range(2, int(level) + 1):
+        kept = min(int(width), kept * int(legal))
+    return kept
+
+
+def beam_samples_args(game, n_envs, frames, depth, width, samples, hold=1, objective=0, salt=0, rest=None, seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: columns {frames, hold, depth, objective, rest, seed_lo, seed_hi, t,
+    env_offset, width, samples, salt} -- beam_args with samples and salt appended; (args, per_env) as lookahead_args gives them.
+    Shared values are range-checked here (ValueError): the beam's, samples 1 .. LOOKAHEAD_MAX_SAMPLES, the salt ranges of sample_args
+    and the leaf cap -- the candidates of the widest level times the samples, n_legal * beam_kept(n_legal, width, depth - 1) *
+    (1 if depth == 1 else n_legal) * samples, must not exceed LOOKAHEAD_MAX_LEAVES; per-env rows are left to the device (a bad
+    row answers zeros)."""
+    name = _game_name(game)
+    for what, c in (("samples", samples), ("salt", salt)):
+        if np.ndim(c) > 1 or (np.ndim(c) == 1 and len(c) != int(n_envs)):
+            raise ValueError("lookahead %s is a scalar or one value per env (%d), got shape %r" % (what, n_envs, np.shape(c)))
+    if not np.ndim(samples) and not 1 <= int(samples) <= _abi.LOOKAHEAD_MAX_SAMPLES:
+        raise ValueError("samples must be 1 .. %d, got %r" % (_abi.LOOKAHEAD_MAX_SAMPLES, samples))
+    if not np.ndim(salt):
+        if not 0 <= int(salt) < 1 << 32:
+            raise ValueError("sample salt must be 0 .. 2**32 - 1, got %r" % (salt,))
+        if int(salt) and not np.ndim(samples) and int(salt) + int(samples) - 1 >= 1 << 32:
+            raise ValueError("sample salt + samples - 1 must stay below 2**32, got %r + %r" % (salt, samples))
+    base, per_env = beam_args(name, n_envs, frames, depth, width, hold, objective, rest, seed, t, env_offset)
+    if not np.ndim(samples) and not np.ndim(depth) and not np.ndim(width):
+        L = len(_abi.LEGAL_ACTIONS[name])
+        leaves = L * beam_kept(L, width, int(depth) - 1) * (1 if int(depth) == 1 else L) * int(samples)
+        if leaves > _abi.LOOKAHEAD_MAX_LEAVES:
+            raise ValueError("the candidates of the last level x samples must not exceed %d, got %d (depth %r, width %r, %r samples)"
+                             % (_abi.LOOKAHEAD_MAX_LEAVES, leaves, depth, width, samples))
+    if not per_env and not np.ndim(samples) and not np.ndim(salt):
+        return list(base) + [float(samples), float(salt)], False
+    args = np.empty((int(n_envs), 12), np.float64)
+    args[:, :10] = np.asarray(base, np.float64)
+    args[:, 10] = np.asarray(samples, np.float64)
+    args[:, 11] = np.asarray(salt, np.float64)
+    return args, True
+
+
 class Engine:
     def __init__(self, game, n_envs=1, device=0, config=None, lib=None):
         self._lib = lib if lib is not None else load()
@@ -640,6 +682,30 @@ class Engine:
         L = len(self.legal_actions)
         out = self.reduce(_abi.QUERY_LOOKAHEAD_SEARCH_SAMPLES, args).reshape(self.n_envs, L, 9)
         return self._search_samples_dict(out, depth)
+
+    def lookahead_beam_samples(self, frames, depth, width, samples, hold=1, objective="return", salt=0, rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: lookahead_beam with every candidate judged on the SAME `samples` futures (future s:
+        seed sample_seed(seed, s) and, with a salt that is not 0, the game RNG salted by salt + s, as in lookahead_samples) -- plans
+        up to PLAN_MAX_DEPTH deep by their summed outcome.  Level d keeps the `width` best prefixes of depth d under the order of
+        lookahead_search_samples ("return": the larger ret_sum, the smaller lost, the larger safe_frames_sum; "survival": the smaller
+        lost, the larger safe_frames_sum, the larger ret_sum; ties to the smaller code).  The dict of lookahead_search_samples: the
+        eight sums, int64 [N, n_legal] (samples 0: the row was refused), code (uint64) and plan [N, n_legal, depth].  With depth 1
+        the sums are lookahead_samples'; with width >= n_legal ** (depth - 2) it is lookahead_search_samples where that accepts
+        the depth.  Nothing in the engine is written."""
+        args, _ = beam_samples_args(self.game, self.n_envs, frames, depth, width, samples, hold, objective, salt, rest, seed, t, env_offset)
+        L = len(self.legal_actions)
+        out = self.reduce(_abi.QUERY_LOOKAHEAD_BEAM_SAMPLES, args).reshape(self.n_envs, L, 9)
+        return self._search_samples_dict(out, depth)
+
+    @property
+    def beam_samples_ranges(self):
+        """into how many env ranges the last lookahead_beam_samples was cut (0: none yet)"""
+        return self.get_option(_abi.OPT_BEAM_SAMPLES_RANGES)
+
+    @property
+    def beam_samples_chunks(self):
+        """the largest number of sample chunks any level of the last lookahead_beam_samples used (0: none yet)"""
+        return self.get_option(_abi.OPT_BEAM_SAMPLES_CHUNKS)
 
     def _search_samples_dict(self, out, depth):
         L = len(self.legal_actions)

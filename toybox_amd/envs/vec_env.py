@@ -147,10 +147,15 @@ def _search_samples(env, frames, hold, depth, samples, objective, rest, seed, t,
     """Engine.lookahead_search_samples for an adapter: `rest` an action index going in, `plan` action indices coming out (the
     digits of the code); the means are added as _samples adds them, best_action is sample_best_action over the rows and best_plan
     that row's plan"""
-    from ..engine import plan_digits
     if objective not in ("return", "survival"):
         raise ValueError("objective is 'return' or 'survival', got %r" % (objective,))
     out = env.engine.lookahead_search_samples(frames, int(depth), int(samples), hold=hold, objective=objective, salt=salt, rest=_ale(env, rest), seed=seed, t=t)
+    return _with_sample_best(env, out, depth, objective)
+
+
+def _with_sample_best(env, out, depth, objective):
+    """the rows of a search or a beam over samples: plan as action indices; the means, best_action and best_plan added"""
+    from ..engine import plan_digits
     out["plan"] = plan_digits(len(env._action_set), out["code"], int(depth))
     played = np.maximum(out["samples"], 1).astype(np.float64)
     out["ret_mean"] = out["ret_sum"] / played
@@ -159,6 +164,14 @@ def _search_samples(env, frames, hold, depth, samples, objective, rest, seed, t,
     out["best_action"] = sample_best_action(out, objective)
     out["best_plan"] = out["plan"][np.arange(out["plan"].shape[0]), out["best_action"]]
     return out
+
+
+def _beam_samples(env, frames, hold, depth, width, samples, objective, rest, seed, t, salt):
+    """Engine.lookahead_beam_samples for an adapter: as _search_samples, with the beam's width"""
+    if objective not in ("return", "survival"):
+        raise ValueError("objective is 'return' or 'survival', got %r" % (objective,))
+    out = env.engine.lookahead_beam_samples(frames, int(depth), int(width), int(samples), hold=hold, objective=objective, salt=salt, rest=_ale(env, rest), seed=seed, t=t)
+    return _with_sample_best(env, out, depth, objective)
 
 
 def _fork_map(n, src, envs):
@@ -371,6 +384,15 @@ class ToyboxVecEnv:
         if self._in_flight is not None or self._pending is not None:
             self.step_wait()
         return _samples(self, int(steps), 1, samples, rest, seed, t, salt, objective)
+
+    def beam_search_samples(self, steps, depth, width, samples, objective="return", rest=None, seed=0, t=0, salt=0):
+        """beam_search() over sampled futures (Engine.lookahead_beam_samples): search_samples() for plans deeper than it can
+        enumerate.  Per first action index and level the `width` best action sequences by the summed outcome of the same
+        `samples` futures are kept and extended by every action.  The dict of search_samples(): the eight sums, code, plan
+        (action indices), the means, best_action and best_plan.  Nothing is touched; a pending step_async ends first."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _beam_samples(self, int(steps), 1, depth, width, samples, objective, rest, seed, t, salt)
 
     def search_samples(self, steps, depth, samples, objective="return", rest=None, seed=0, t=0, salt=0):
         """search() over sampled futures (Engine.lookahead_search_samples): every action sequence of `depth` steps is played on
@@ -725,6 +747,13 @@ class ToyboxPreprocVecEnv:
         if self._in_flight is not None:
             self.step_wait()
         return _samples(self, int(steps) * self._skip, self._skip, samples, rest, seed, t, salt, objective)
+
+    def beam_search_samples(self, steps, depth, width, samples, objective="return", rest=None, seed=0, t=0, salt=0):
+        """ToyboxVecEnv.beam_search_samples in agent steps: steps x skip raw frames, every action held for skip frames; raw
+        frames, no wrapper, as in lookahead().  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _beam_samples(self, int(steps) * self._skip, self._skip, depth, width, samples, objective, rest, seed, t, salt)
 
     def search_samples(self, steps, depth, samples, objective="return", rest=None, seed=0, t=0, salt=0):
         """ToyboxVecEnv.search_samples in agent steps: steps x skip raw frames, every action held for skip frames; raw frames,

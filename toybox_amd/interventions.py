@@ -273,6 +273,16 @@ class BatchIntervention:
                                             rest=self._full(rest, -1), seed=self._full(seed, 0), t=self._full(t, 0), env_offset=self._full(env_offset, 0))
         return {k: v[self.first:self.first + self.count] for k, v in out.items()}
 
+    def lookahead_beam_samples(self, frames, depth, width, samples, hold=1, objective="return", salt=0, rest=None, seed=0, t=0, env_offset=0):
+        """Engine.lookahead_beam_samples over the range: the eight fields and code [count, n_legal], plan [count, n_legal, depth]"""
+        self._flush()
+        if np.ndim(objective):
+            objective = self._full(objective, 0)
+        out = self.engine.lookahead_beam_samples(self._full(frames, 1), self._full(depth, 1), self._full(width, 1), self._full(samples, 1), hold=self._full(hold, 1),
+                                                 objective=objective, salt=self._full(salt, 0), rest=self._full(rest, -1), seed=self._full(seed, 0), t=self._full(t, 0),
+                                                 env_offset=self._full(env_offset, 0))
+        return {k: v[self.first:self.first + self.count] for k, v in out.items()}
+
     def lookahead_search_samples(self, frames, depth, samples, hold=1, objective="return", salt=0, rest=None, seed=0, t=0, env_offset=0):
         """Engine.lookahead_search_samples over the range: the eight fields and code [count, n_legal], plan [count, n_legal, depth]"""
         self._flush()
