@@ -148,6 +148,43 @@ def amidar_edit_last_lives(js, lives, jump_timer, perimeter_from_start):
     return js
 
 
+# ---------------------------------------------------------------- mid-game states: a short window is to be full of events
+# From a fresh reset a window of 30 to 100 frames (or 48 agent steps) ends no game in Breakout, SpaceInvaders or Amidar.  So every
+# env starts from the state of a donor env that has played for a while, and every second env is on its last life
+# (tests/test_gpu_agent_scale.py, tests/test_gpu_loop_events.py).  GridWorld ends games from a fresh reset by itself (0: no donor).
+DONOR_ENVS, DONOR_SEED, DONOR_ACTION_SEED = 1024, 99, 7
+DONOR_FRAMES = {"breakout": 400, "space_invaders": 600, "amidar": 600, "gridworld": 0}
+
+
+def donor_records(game, oracle_lib, donors=DONOR_ENVS):
+    """the state records of `donors` oracle envs after DONOR_FRAMES[game] raw auto-resetting frames (None: no donor)"""
+    from toybox_amd import Engine
+    if not DONOR_FRAMES[game]:
+        return None
+    with Engine(game, donors, lib=oracle_lib) as d:
+        d.seed(DONOR_SEED)
+        d.new_game()
+        for t in range(DONOR_FRAMES[game]):
+            d.step(synthetic_actions(game, donors, t, seed=DONOR_ACTION_SEED), auto_reset=True)
+        return d.get_states_np()
+
+
+def write_mid_game_states(engines, n, records):
+    """env i of every engine gets donor record i % len(records), then every even env is put on its last life (a state write
+    between steps, as in test_gpu_agent_pipeline_survives_state_writes); the simulator RNGs stay the envs' own, so no two envs
+    play the same game"""
+    from toybox_amd import _abi
+    if records is None:
+        return
+    part = 8192                                                 # (the records are 14 KB each in Breakout: not 65 536 at once)
+    for first in range(0, n, part):
+        rec = records[np.arange(first, min(n, first + part)) % len(records)]
+        for e in engines:
+            e.set_states_np(first, rec)
+    for e in engines:
+        e.edit(_abi.EDIT_SET_LIVES, [1], mask=np.arange(n) % 2 == 0)
+
+
 def read_buffer(engine, which, shape, dtype=np.uint8, stream=None):
     """host copy of an engine-owned buffer (TBX_BUF_*): device memory of the HIP library, plain memory of the CPU checker.
     stream (a toybox_amd.hip.Stream, the one the producing call named): the copy is queued on it right behind tbx_device_buffer and

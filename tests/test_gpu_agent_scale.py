@@ -17,8 +17,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from support import (FrameChecker, agent_stack_frames, amidar_edit_last_lives, engine_is_oracle, queue_read_buffer, read_buffer,
-                     synthetic_actions)
+from support import (FrameChecker, agent_stack_frames, amidar_edit_last_lives, donor_records, engine_is_oracle, queue_read_buffer,
+                     read_buffer, synthetic_actions, write_mid_game_states)
 from toybox_amd import Engine, _abi
 from toybox_amd._lib import ToyboxAmdError
 from toybox_amd.games import codec
@@ -35,9 +35,8 @@ BENCH_AGENT = dict(skip=4, out_h=84, out_w=84, stack=4, clip_reward=True, episod
 # ---------------------------------------------------------------- mid-game states: the window is to be full of events
 # From a fresh reset 48 agent steps end no game in Breakout, SpaceInvaders or Amidar: the no-op / fire reset path would never run
 # after step 0.  So every env starts from the state of a donor env that has played for a while, and every second env is on its
-# last life.  GridWorld ends games from a fresh reset by itself (DONOR_FRAMES 0: no donor, no edit).
-DONOR_ENVS, DONOR_SEED, DONOR_ACTION_SEED = 1024, 99, 7
-DONOR_FRAMES = {"breakout": 400, "space_invaders": 600, "amidar": 600, "gridworld": 0}
+# last life.  GridWorld ends games from a fresh reset by itself (DONOR_FRAMES 0: no donor, no edit).  The recipe (donor_records,
+# write_mid_game_states: 1 024 donor envs, engine seed 99, action seed 7, 400 / 600 / 600 / 0 frames) lives in tests/support.py.
 WINDOW, BLOCK = 32, 4
 # The floor under the events, as a share of the batch with a real game over (TBX_BUF_AGENT_EP_DONE) inside the window -- asserted
 # on the ORACLE's outputs: when it is missed the inputs are wrong, not the device.
@@ -64,33 +63,6 @@ def block_code(step_codes):
     if _abi.E_NEEDS_RESET in step_codes:
         return _abi.E_NEEDS_RESET
     return _abi.E_ACTION if _abi.E_ACTION in step_codes else _abi.OK
-
-
-def donor_records(game, oracle_lib):
-    """the state records of DONOR_ENVS oracle envs after DONOR_FRAMES[game] raw auto-resetting frames (None: no donor)"""
-    if not DONOR_FRAMES[game]:
-        return None
-    with Engine(game, DONOR_ENVS, lib=oracle_lib) as d:
-        d.seed(DONOR_SEED)
-        d.new_game()
-        for t in range(DONOR_FRAMES[game]):
-            d.step(synthetic_actions(game, DONOR_ENVS, t, seed=DONOR_ACTION_SEED), auto_reset=True)
-        return d.get_states_np()
-
-
-def write_mid_game_states(engines, n, records):
-    """env i of every engine gets donor record i % DONOR_ENVS, then every even env is put on its last life (a state write between
-    agent steps, as in test_gpu_agent_pipeline_survives_state_writes); the simulator RNGs stay the envs' own, so no two envs
-    play the same game"""
-    if records is None:
-        return
-    part = 8 * DONOR_ENVS                                       # (the records are 14 KB each in Breakout: not 65 536 at once)
-    for first in range(0, n, part):
-        rec = records[np.arange(first, min(n, first + part)) % DONOR_ENVS]
-        for e in engines:
-            e.set_states_np(first, rec)
-    for e in engines:
-        e.edit(_abi.EDIT_SET_LIVES, [1], mask=np.arange(n) % 2 == 0)
 
 
 def compare_stacks(chk, e, o, n, what):

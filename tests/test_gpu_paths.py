@@ -886,7 +886,8 @@ def test_fused_overlap_outputs_frames_and_gather(n, channels, K, hip_lib, oracle
     TBX_BUF_FRAME / TBX_BUF_REWARD alternate between two addresses; with a gather (K = 1: a collective per step, now beside
     the next launch; K > 1: the record ring) the gathered block equals the oracle's records of the last K steps; a call with
     out_dev given, a stream-order call (option 2) and a host step in between join and re-enter.  8 192 envs + K = 4 is the
-    per-GPU share of the strong-scaled headline batch."""
+    per-GPU share of the strong-scaled headline batch.
+    From a new game, these 64 frames contain no game end and no reward: tests/test_gpu_loop_events.py holds those."""
     from toybox_amd import hip
     from toybox_amd.parallel import pack_records
     game = "breakout"
@@ -1049,7 +1050,8 @@ def test_rollout_chunks_equal_oracle(game, n, channels, K, ring, form, hip_lib, 
     copies queued on the caller's stream right behind tbx_device_buffer (the lazy join) and therefore before the next chunk is
     issued; the two chunk buffers alternate; under a K-step ring the gathered block of every chunk; joins (a host step, a state
     write, a single fused call, the option off for a chunk) in between; final states.  8 192 envs + K = 4 ring is the per-GPU
-    share of the strong-scaled headline batch."""
+    share of the strong-scaled headline batch.
+    From a new game, these windows contain no game end and no reward: tests/test_gpu_loop_events.py holds those."""
     from toybox_amd import hip
     g, o = _pair(game, n, hip_lib, oracle_lib, seed=33)
     H, W = g.height, g.width
