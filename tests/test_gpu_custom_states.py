@@ -257,19 +257,21 @@ def run_steps(es, game, steps, action_seed=2, frames_every=0, watch=None):
             _device_frames_equal(es[0], es[1], chk, ch, "%s step %d channels %d" % (game, t, ch))
 
 
-def agent_observation(e, obs):
+def agent_observation(e, obs, stream=None):
     """the current observation: the rolled stack tbx_agent_step returned (uint8[N, h, w, stack]), or -- new_plane = 2 -- the plane ring
-    read in head order (uint8[stack, N, h, w], oldest first: slot (head + 1 + c) % stack is channel c)"""
+    read in head order (uint8[stack, N, h, w], oldest first: slot (head + 1 + c) % stack is channel c); stream: the ring is read
+    behind the producing call on that stream (read_buffer) instead of behind tbx_sync"""
     if obs is not None:
         return obs
     n, oh, ow, stack = e._agent_shape
-    ring = read_buffer(e, _abi.BUF_AGENT_RING, (stack, n, oh, ow))
+    ring = read_buffer(e, _abi.BUF_AGENT_RING, (stack, n, oh, ow), stream=stream)
     return ring[(e.agent_ring_head() + 1 + np.arange(stack)) % stack]
 
 
-def run_agent(es, game, t0, t1, action_seed=7, env_map=None):
+def run_agent(es, game, t0, t1, action_seed=7, env_map=None, tolerate_needs_reset=False):
     """agent steps t0 .. t1-1 on every engine of `es` (env i takes env env_map[i]'s action): observation, reward, done and the episode
-    monitor compared at every step; -> (done count, episode count, the last engine's rows)"""
+    monitor compared at every step; -> (done count, episode count, the last engine's rows).  tolerate_needs_reset: a step on an env
+    whose game ended inside EpisodicLifeEnv's no-op step is carried out and compared like any other (Engine.agent_step)"""
     n = es[0].n_envs
     dones = episodes = 0
     rows = []
@@ -278,7 +280,7 @@ def run_agent(es, game, t0, t1, action_seed=7, env_map=None):
         a = a if env_map is None else a[env_map]
         outs = []
         for e in es:
-            obs, reward, done = e.agent_step(a)
+            obs, reward, done = e.agent_step(a, tolerate_needs_reset=tolerate_needs_reset)
             ended, ret, length = e.agent_episodes()
             outs.append((agent_observation(e, obs), reward, done, ended, np.where(ended, ret, 0), np.where(ended, length, 0)))
         for x, y, name in zip(outs[0], outs[-1], ("observation", "reward", "done", "episode end", "episode return", "episode length")):
