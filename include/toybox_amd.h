@@ -790,6 +790,50 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
  *   salt, the leaf cap), more than 12 arguments.  In per-env rows such an env's whole output is nine zeros -- field 0 = 0 -- and
  *   the other envs are answered. */
 #define TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES 157  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width, samples, salt} -> 9 * n_legal(game) */
+/* Evolutionary plan search, warm-started: a search over WHOLE plans with a budget the caller chooses -- a population of plans of
+ * one depth per env and first action, valued, ranked and bred by mutation from its elite over a number of generations, optionally
+ * seeded with a plan the caller hands in (a rolling-horizon controller: last step's best plan, shifted by one period).  The search
+ * is deterministic and defined in integers.  Columns 0 .. 8 stand where TBX_QUERY_LOOKAHEAD_BEAM has them, with the same defaults
+ * for trailing arguments left out; appended are
+ *     population P   default 1    1 .. TBX_EVOLVE_MAX_POPULATION
+ *     generations G  default 0    0 .. TBX_EVOLVE_MAX_GENERATIONS
+ *     elite E        default 1    1 .. P
+ *     plan_seed      default 0    0 .. 2^32 - 1
+ *     mutation       default 64   0 .. 256
+ *     init           default -1   -1, or 0 .. L^depth - 1
+ *   and depth is 1 .. TBX_PLAN_MAX_DEPTH(game): there is no L^depth cap.
+ *   With L = n_legal(game) and D = depth, for every env and every first action index a in legal-set order:
+ *     Individuals: an individual is a plan code of depth D with digit_0 = a (plan codes: TBX_QUERY_LOOKAHEAD_PLAN's).
+ *     Base word: base = splitmix64(splitmix64(plan_seed ^ (a << 32)) ^ (env_offset + env)), the sum taken in 64 bits.
+ *     Draw word: w(g, i, p) = splitmix64(base ^ (g << 40) ^ (i << 8) ^ p).  It depends on nothing but its indices -- not on G, P or E.
+ *     Generation 0: individual i = 0 .. P-1 has digit_0 = a and digit_p = (w(0, i, p) >> 32) % L for p = 1 .. D-1; if init >= 0,
+ *       individual 0 instead takes digits 1 .. D-1 of init (its digit_0 is still a).
+ *     Valuation: the five fields of TBX_QUERY_LOOKAHEAD_PLAN {frames, hold, D, code, rest, seed, t, env_offset}.
+ *     Order: the search's order for `objective` (ret / lives / loss), then the smaller code.  Two individuals with one code are the
+ *       same plan with the same fields; ranks are made a permutation by the smaller index i, which no output can observe.
+ *     Generation g = 1 .. G, from the ranks of generation g-1: individual i < E is the individual of rank i (an elite: its record
+ *       may be carried, it need not be replayed); individual i >= E takes the code of the individual of rank
+ *       (w(g, i, 0) >> 32) % E, and for p = 1 .. D-1, with x = w(g, i, p): if (x & 0xff) < mutation, digit_p becomes
+ *       (x >> 32) % L, otherwise it stays the parent's.
+ *   Out: row out[env][a][0 .. 5] = {ret, score, lives, frames run, life lost at, code} of rank 0 of generation G.
+ *   It follows that
+ *     (i)   with P = 1, G = 0 and init = c the row is TBX_QUERY_LOOKAHEAD_PLAN's row for the code c - c % L + a;
+ *     (ii)  a row with G' > G and everything else equal is not worse under the order: generations 0 .. G are the same
+ *           populations, and elites persist;
+ *     (iii) feeding the returned code to TBX_QUERY_LOOKAHEAD_PLAN at depth D gives the row's five fields;
+ *     (iv)  where TBX_QUERY_LOOKAHEAD_SEARCH accepts the depth, its row is not worse than this one;
+ *     (v)   with E = P or mutation = 0 every G gives generation 0's winner;
+ *     (vi)  with depth 1 the row is TBX_QUERY_LOOKAHEAD_PLAN's row for code a.
+ *   Every individual is replayed from the env's live state in registers, generation after generation on the calling stream, and a
+ *   select pass after each ranks a group's population and breeds the next; large batches are cut into env ranges
+ *   (TBX_OPT_EVOLVE_RANGES, capped by TBX_OPT_BEAM_RANGE_ENVS).  Neither changes the answer.  "Nothing in the engine changes" is the
+ *   lookahead's sentence, verbatim.
+ *   TBX_E_INVALID, nothing launched: a shared value out of the ranges above (frames, hold, depth, objective, rest, population,
+ *   generations, elite, plan_seed, mutation, init), more than 15 arguments.  In per-env rows such an env's rows are zeros -- frames
+ *   run 0 -- and the other envs are answered. */
+#define TBX_EVOLVE_MAX_POPULATION  256
+#define TBX_EVOLVE_MAX_GENERATIONS 64
+#define TBX_QUERY_LOOKAHEAD_EVOLVE 158  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, population, generations, elite, plan_seed, mutation, init} -> 6 * n_legal(game) */
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);
@@ -1105,6 +1149,8 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
 /* at most this many sample chunks per level of a TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES; 0 (default): the engine's choice, 1: never cut.
  * It changes no output bit. */
 #define TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS 113
+/* read-only: into how many env ranges the last TBX_QUERY_LOOKAHEAD_EVOLVE was cut (0: none yet; a refused query leaves it standing) */
+#define TBX_OPT_EVOLVE_RANGES 114
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
 /* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could

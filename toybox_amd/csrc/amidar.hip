@@ -2307,6 +2307,12 @@ struct AmiOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+    int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, int gen, int first_slot, int slots, int first_env, int envs, const TbxEvolveScratch& sc, hipStream_t s) override
+    {
+        tbx_launch_evolve(AmiLook{d}, a, gen, first_slot, slots, first_env, envs, sc, s);
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
     int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int chunks, int first_env, int envs, const TbxBeamSamplesScratch& sc, hipStream_t s) override
     {
         tbx_launch_beam_samples(AmiLook{d}, a, level, slots, chunks, first_env, envs, sc, s);

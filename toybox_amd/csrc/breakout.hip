@@ -2442,6 +2442,13 @@ struct BreakoutOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
+    int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, int gen, int first_slot, int slots, int first_env, int envs, const TbxEvolveScratch& sc, hipStream_t s) override
+    {
+        if (!custom && use_tpe) tbx_launch_evolve(BrkTLook{d, cfg_dev}, a, gen, first_slot, slots, first_env, envs, sc, s);
+        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_evolve(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, gen, first_slot, slots, first_env, envs, sc, s); });
+        TBX_HIP(hipGetLastError());
+        return TBX_OK;
+    }
     int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int chunks, int first_env, int envs, const TbxBeamSamplesScratch& sc, hipStream_t s) override
     {
         if (!custom && use_tpe) tbx_launch_beam_samples(BrkTLook{d, cfg_dev}, a, level, slots, chunks, first_env, envs, sc, s);

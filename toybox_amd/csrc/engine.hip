@@ -1150,6 +1150,7 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_LOOKAHEAD_PLAN: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_BEAM: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_EVOLVE: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
@@ -1339,6 +1340,159 @@ static int lookahead_beam(tbx_engine* e, const TbxEditArgs& a, double* out_dev, 
         }
     }
     e->beam_ranges = ranges;
+    EHIP(hipGetLastError());
+    return TBX_OK;
+}
+
+// TBX_QUERY_LOOKAHEAD_EVOLVE, after the play of generation `gen`: one wave per (env, first action) group of envs from first_env on.
+// It stages the group's population (at most TBX_EVOLVE_MAX_POPULATION records, 8 KiB) in LDS and ranks each individual by COUNTING
+// those that beat it, as tbx_beam_select_kernel does -- two individuals of one code are one plan with one record, and the smaller
+// index goes first, so the ranks are a permutation and a pure function of the population.  In the env's last generation rank 0
+// goes to the output row.  Earlier it writes the next generation: the record and code of rank r < elite into slot r (nobody
+// replays them), and per child a lane that draws its parent among the elites and mutates the parent's digits, in 32-bit
+// arithmetic (a Breakout code reaches 2^32 - 1).  A refused env's rows are zeros, written at generation 0; an env whose
+// generations are below `gen` idles.
+__global__ __launch_bounds__(64) void tbx_evolve_select_kernel(TbxEditArgs a, int game, int gen, int first_env, TbxEvolveScratch sc, double* __restrict__ out)
+{
+    __shared__ TbxBeamCand lds[TBX_EVOLVE_MAX_POPULATION];
+    __shared__ uint16_t by_rank[TBX_EVOLVE_MAX_POPULATION];
+    const uint32_t L = (uint32_t)tbx_legal_count(game);
+    const int group = blockIdx.x, lane = threadIdx.x;
+    const int env = first_env + group / (int)L, cand = group % (int)L;
+    double* const o = out + ((size_t)first_env * L + group) * 6;
+    TbxEvolveRow r;
+    if (!tbx_evolve_row(game, a, env, r)) {
+        if (gen == 0 && lane < 6) o[lane] = 0.0;
+        return;
+    }
+    if (gen > r.generations) return;
+    const int n = r.population;
+    TbxBeamCand* const recs = sc.recs + (size_t)group * sc.stride;
+    uint32_t* const codes = sc.codes + (size_t)group * sc.stride;
+    for (int i = lane; i < n; i += 64) lds[i] = recs[i];
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) {
+        const TbxBeamCand x = lds[i];
+        int rank = 0;
+        for (int j = 0; j < n; j++) rank += tbx_search_better(r.objective, lds[j].f, lds[j].code, x.f, x.code) || (j < i && lds[j].code == x.code) ? 1 : 0;
+        by_rank[rank] = (uint16_t)i;
+        if (gen == r.generations && rank == 0) tbx_search_store(o, x.f, x.code, false, false);
+    }
+    if (gen == r.generations) return;
+    __syncthreads();
+    for (int k = lane; k < r.elite; k += 64) {
+        const TbxBeamCand x = lds[by_rank[k]];
+        recs[k] = x;
+        codes[k] = x.code;
+    }
+    const uint64_t base = tbx_evolve_base(r.plan_seed, cand, (uint64_t)a.getu(env, 8) + (uint64_t)env);
+    for (int i = r.elite + lane; i < n; i += 64) {
+        uint32_t c = lds[by_rank[(uint32_t)(tbx_evolve_word(base, gen + 1, i, 0) >> 32) % (uint32_t)r.elite]].code;
+        uint32_t code = c % L, pow = L;                                            // digit 0: the first action, every parent's
+        c /= L;
+        for (int p = 1; p < r.depth; p++, pow *= L, c /= L) {
+            const uint64_t x = tbx_evolve_word(base, gen + 1, i, p);
+            const uint32_t digit = (int)(x & 0xff) < r.mutation ? (uint32_t)(x >> 32) % L : c % L;
+            code += digit * pow;
+        }
+        codes[i] = code;
+    }
+}
+
+// What a TBX_QUERY_LOOKAHEAD_EVOLVE is budgeted for: the largest frames, population and generations of a valid row and the
+// smallest elite (nobody's unit after generation 0)
+struct TbxEvolveBounds {
+    long long frames;
+    int population, generations, elite;
+};
+// tbx_reduce has per-env rows on the host: the bounds of the rows that tbx_evolve_values accepts (none: the smallest query)
+static TbxEvolveBounds evolve_scan(const tbx_engine* e, const double* rows, int n)
+{
+    TbxEvolveBounds b{1, 1, 0, 1};
+    bool any = false;
+    for (int env = 0; env < e->n; env++) {
+        const double* const r = rows + (size_t)env * n;
+        auto geti = [&](int i, int otherwise) { return i < n ? TbxEditArgs::to_int(r[i]) : otherwise; };
+        const int frames = geti(0, 0), population = geti(9, 1), generations = geti(10, 0), elite = geti(11, 1);
+        if (!tbx_evolve_values(e->game, frames, geti(1, 1), geti(2, 1), geti(3, 0), geti(4, -1), population, generations, elite, n > 12 ? r[12] : 0.0, geti(13, 64),
+                               n > 14 ? r[14] : -1.0))
+            continue;
+        if (frames > b.frames) b.frames = frames;
+        if (population > b.population) b.population = population;
+        if (generations > b.generations) b.generations = generations;
+        if (!any || elite < b.elite) b.elite = elite;
+        any = true;
+    }
+    return b;
+}
+
+// TBX_QUERY_LOOKAHEAD_EVOLVE: shared values are refused here, before anything is launched; per-env rows are met by the kernels.
+// Env ranges come from the beam's three budgets -- a launch under TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH leaf-frames and
+// TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units, the scratch under TBX_BEAM_SCRATCH_BYTES (starting values here as there: profiles/beam.md,
+// profiles/evolve.md) -- and TBX_OPT_BEAM_RANGE_ENVS cuts them as it cuts the beam's.  Per env the scratch is L * population records
+// and as many codes; beam_scratch is shared with the beam queries: all run in stream order.  Per-env rows are budgeted by `rows`
+// where the host form has scanned them, else as the largest valid row with TBX_EVOLVE_MAX_GENERATIONS + 1 rounds run -- the device
+// form cannot see the rows; an env writes its row at its own last generation and idles afterwards.  Within a range, per
+// generation: play, select -- all on `s`, in stream order, no host synchronisation.
+static int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, const TbxEvolveBounds* rows, double* out_dev, hipStream_t s)
+{
+    const int L = tbx_legal_count(e->game);
+    if (a.n < 1 || a.n > 15)
+        return e->fail(TBX_E_INVALID, "evolve takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, population, generations, elite, plan_seed, mutation, init]}");
+    // per-env rows the host has not seen: the most a valid row can ask for
+    TbxEvolveBounds b{TBX_LOOKAHEAD_MAX_FRAMES, TBX_EVOLVE_MAX_POPULATION, TBX_EVOLVE_MAX_GENERATIONS, 1};
+    if (!a.per_env) {
+        auto playable = [&](double v) {
+            if (v == -1.0) return true;
+            for (int i = 0; i < L; i++)
+                if (v == (double)tbx_legal_action(e->game, i)) return true;
+            return false;
+        };
+        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        const double dp = a.n > 2 ? a.v[2] : 1.0, pop = a.n > 9 ? a.v[9] : 1.0, gens = a.n > 10 ? a.v[10] : 0.0, elite = a.n > 11 ? a.v[11] : 1.0;
+        const double plan_seed = a.n > 12 ? a.v[12] : 0.0, mutation = a.n > 13 ? a.v[13] : 64.0, init = a.n > 14 ? a.v[14] : -1.0;
+        if (!(dp >= 1.0 && dp <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "evolve: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
+        if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "evolve: objective must be 0 (return) or 1 (survival)");
+        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        if (!(pop >= 1.0 && pop <= (double)TBX_EVOLVE_MAX_POPULATION)) return e->fail(TBX_E_INVALID, "evolve: population must be 1 .. TBX_EVOLVE_MAX_POPULATION");
+        if (!(gens >= 0.0 && gens <= (double)TBX_EVOLVE_MAX_GENERATIONS)) return e->fail(TBX_E_INVALID, "evolve: generations must be 0 .. TBX_EVOLVE_MAX_GENERATIONS");
+        b.frames = TbxEditArgs::to_int(a.v[0]);
+        b.population = TbxEditArgs::to_int(pop);
+        b.generations = TbxEditArgs::to_int(gens);
+        if (!(elite >= 1.0 && elite <= (double)b.population)) return e->fail(TBX_E_INVALID, "evolve: elite must be 1 .. population");
+        b.elite = TbxEditArgs::to_int(elite);
+        if (!(plan_seed >= 0.0 && plan_seed < 4294967296.0)) return e->fail(TBX_E_INVALID, "evolve: plan_seed must be 0 .. 2^32 - 1");
+        if (!(mutation >= 0.0 && mutation <= 256.0)) return e->fail(TBX_E_INVALID, "evolve: mutation must be 0 .. 256");
+        if (!(init == -1.0 || (init >= 0.0 && init < (double)tbx_plan_count(e->game, TbxEditArgs::to_int(dp))))) return e->fail(TBX_E_INVALID, "evolve: init must be -1 or 0 .. n_legal^depth - 1");
+    } else if (rows) b = *rows;
+    // per env: L groups of `population` individuals -- a record and a code each
+    const long long units_per_env = (long long)L * b.population;
+    const size_t bytes_per_env = (size_t)units_per_env * (sizeof(TbxBeamCand) + sizeof(uint32_t));
+    long long step = TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH / (units_per_env * b.frames);
+    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
+    if (step > (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env)) step = (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env);
+    if (e->beam_range_envs > 0 && step > e->beam_range_envs) step = e->beam_range_envs;
+    if (step > e->n) step = e->n;
+    if (step < 1) step = 1;
+    EHIP(e->beam_scratch.reserve(bytes_per_env * (size_t)step, e->stream, s));
+    TbxEvolveScratch sc;
+    sc.stride = b.population;
+    sc.recs = reinterpret_cast<TbxBeamCand*>(e->beam_scratch.p);
+    sc.codes = reinterpret_cast<uint32_t*>(e->beam_scratch.p + (size_t)units_per_env * sizeof(TbxBeamCand) * (size_t)step);
+    int ranges = 0;
+    for (long long env0 = 0; env0 < e->n; env0 += step, ranges++) {
+        const int envs = (int)(e->n - env0 < step ? e->n - env0 : step);
+        for (int gen = 0; gen <= b.generations; gen++) {
+            const int first_slot = gen == 0 ? 0 : b.elite;
+            if (first_slot < b.population) {                     // (elite = population: every later generation is carried whole)
+                int rc = e->ops->lookahead_evolve(e, a, gen, first_slot, b.population - first_slot, (int)env0, envs, sc, s);
+                if (rc) return rc;
+            }
+            hipLaunchKernelGGL(tbx_evolve_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, gen, (int)env0, sc, out_dev);
+        }
+    }
+    e->evolve_ranges = ranges;
     EHIP(hipGetLastError());
     return TBX_OK;
 }
@@ -1649,7 +1803,8 @@ static int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, const Tbx
 }
 
 // the queries every game has (the engine's own), else the game's
-static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s, const TbxBeamSamplesBounds* beam_samples_rows = nullptr)
+static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s, const TbxBeamSamplesBounds* beam_samples_rows = nullptr,
+                         const TbxEvolveBounds* evolve_rows = nullptr)
 {
     if (query == TBX_QUERY_LOOKAHEAD || query == TBX_QUERY_LOOKAHEAD_ALL) {
         // shared values are refused here, before anything is launched; per-env rows are met by the kernel (that env's row: zeros)
@@ -1673,6 +1828,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
     if (query == TBX_QUERY_LOOKAHEAD_SAMPLES) return lookahead_samples(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES) return lookahead_search_samples(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES) return lookahead_beam_samples(e, a, beam_samples_rows, out_dev, s);
+    if (query == TBX_QUERY_LOOKAHEAD_EVOLVE) return lookahead_evolve(e, a, evolve_rows, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     return checkpoint_valid(e, a, out_dev, s);
 }
@@ -1752,7 +1908,11 @@ int tbx_reduce(tbx_engine* e, int query, const double* args, int n_args, int per
     TbxBeamSamplesBounds rows_seen;
     const bool scanned = query == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES && a.per_env && n_args <= 12;
     if (scanned) rows_seen = beam_samples_scan(e, args, n_args);
-    rc = engine_reduce(e, query, a, e->reduce_out.p, width, e->stream, scanned ? &rows_seen : nullptr);
+    // ... and so are those of an evolutionary search: only the rounds and the slots the rows need
+    TbxEvolveBounds evolve_seen;
+    const bool evolve_scanned = query == TBX_QUERY_LOOKAHEAD_EVOLVE && a.per_env && n_args <= 15;
+    if (evolve_scanned) evolve_seen = evolve_scan(e, args, n_args);
+    rc = engine_reduce(e, query, a, e->reduce_out.p, width, e->stream, scanned ? &rows_seen : nullptr, evolve_scanned ? &evolve_seen : nullptr);
     if (rc) return rc;
     EHIP(hipMemcpyAsync(out_host, e->reduce_out.p, bytes, hipMemcpyDeviceToHost, e->stream));
     EHIP(hipStreamSynchronize(e->stream));
@@ -1866,6 +2026,7 @@ int tbx_get_option(tbx_engine* e, int option, int* value_out)
     if (value_out && option == TBX_OPT_BEAM_SAMPLES_RANGES) { *value_out = e->beam_samples_ranges; return TBX_OK; }
     if (value_out && option == TBX_OPT_BEAM_SAMPLES_CHUNKS) { *value_out = e->beam_samples_chunks; return TBX_OK; }
     if (value_out && option == TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS) { *value_out = e->beam_samples_max_chunks; return TBX_OK; }
+    if (value_out && option == TBX_OPT_EVOLVE_RANGES) { *value_out = e->evolve_ranges; return TBX_OK; }
     if (value_out && option == TBX_OPT_SEARCH_SAMPLES_LAUNCHES) { *value_out = e->search_samples_launches; return TBX_OK; }
     if (option < 0 || option >= TBX_OPT_COUNT || !value_out) return e->fail(TBX_E_INVALID, "unknown option");
     *value_out = e->opt[option];

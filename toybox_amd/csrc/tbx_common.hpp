@@ -458,6 +458,7 @@ struct tbx_engine {
     int beam_range_envs = 0;           // TBX_OPT_BEAM_RANGE_ENVS (0: the engine's choice)
     int beam_samples_ranges = 0, beam_samples_chunks = 0;   // env ranges, and the most sample chunks of a level, of the last TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES (0: none yet)
     int beam_samples_max_chunks = 0;   // TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS (0: the engine's choice)
+    int evolve_ranges = 0;             // env ranges of the last TBX_QUERY_LOOKAHEAD_EVOLVE (0: none yet); its scratch is beam_scratch
     TbxDevBuf<void> staging;        // device POD staging for get/set state
     struct TbxEnvCopy* envcopy = nullptr;   // TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*: the fork's scratch copy, the checkpoint store (envcopy.hip), made on first use
     GameOps* ops = nullptr;
@@ -950,6 +951,118 @@ void tbx_launch_beam(const G& g, const TbxEditArgs& a, int level, int slots, int
     const long long count = (long long)envs * L * slots * (level == 1 ? 1 : L);     // (lookahead_beam, engine.hip: below 2^30)
     const long long threads = count * (G::WAVE ? 64 : 1);
     hipLaunchKernelGGL(tbx_beam_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, level, slots, first_env, (int)count, sc);
+}
+
+// ---- TBX_QUERY_LOOKAHEAD_EVOLVE (include/toybox_amd.h): generation after generation, tbx_evolve_kernel plays the individuals of a
+// population and tbx_evolve_select_kernel (engine.hip) ranks them per (env, first action) group and breeds the next generation.
+// An individual is a whole plan of the row's depth, so the leaf is the plan query's and TbxLookahead gets no branch of its own.
+
+// The values of a row {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, population, generations, elite,
+// plan_seed, mutation, init} are a valid evolve row; both kernels ask here (tbx_evolve_row), and so does the host where it has the
+// rows (tbx_reduce), so they cannot disagree about which envs play.  `game` is a constant in the play kernel, a value elsewhere.
+__host__ __device__ __forceinline__ bool tbx_evolve_values(int game, int frames, int hold, int depth, int objective, int rest, int population, int generations, int elite,
+                                                           double plan_seed, int mutation, double init)
+{
+    bool playable = rest == -1;
+    for (int i = 0; i < tbx_legal_count(game); i++) playable = playable || rest == tbx_legal_action(game, i);
+    const bool ok = frames >= 1 && frames <= TBX_LOOKAHEAD_MAX_FRAMES && hold >= 1 && depth >= 1 && depth <= tbx_plan_max_depth(game) &&
+                    (objective == 0 || objective == 1) && playable && population >= 1 && population <= TBX_EVOLVE_MAX_POPULATION &&
+                    generations >= 0 && generations <= TBX_EVOLVE_MAX_GENERATIONS && elite >= 1 && elite <= population &&
+                    plan_seed >= 0.0 && plan_seed < 4294967296.0 && mutation >= 0 && mutation <= 256;
+    return ok && (init == -1.0 || (init >= 0.0 && init < (double)tbx_plan_count(game, depth)));
+}
+// What the kernels read of a row beyond the plan query's columns
+struct TbxEvolveRow {
+    int depth, objective, population, generations, elite, mutation;
+    uint32_t plan_seed, init;     // init: read only where has_init
+    bool has_init;
+};
+__device__ __forceinline__ bool tbx_evolve_row(int game, const TbxEditArgs& a, int env, TbxEvolveRow& r)
+{
+    r.depth = a.n > 2 ? a.geti(env, 2) : 1;
+    r.objective = a.n > 3 ? a.geti(env, 3) : 0;
+    r.population = a.n > 9 ? a.geti(env, 9) : 1;
+    r.generations = a.n > 10 ? a.geti(env, 10) : 0;
+    r.elite = a.n > 11 ? a.geti(env, 11) : 1;
+    const double plan_seed = a.n > 12 ? a.get(env, 12) : 0.0, init = a.n > 14 ? a.get(env, 14) : -1.0;
+    r.mutation = a.n > 13 ? a.geti(env, 13) : 64;
+    const bool ok = tbx_evolve_values(game, a.geti(env, 0), a.n > 1 ? a.geti(env, 1) : 1, r.depth, r.objective, a.n > 4 ? a.geti(env, 4) : -1, r.population,
+                                      r.generations, r.elite, plan_seed, r.mutation, init);
+    r.plan_seed = ok ? (uint32_t)plan_seed : 0u;
+    r.has_init = ok && init >= 0.0;
+    r.init = r.has_init ? (uint32_t)init : 0u;
+    return ok;
+}
+// The words of the definition: base(plan_seed, first action, env_offset + env), then one draw per (generation, individual, period)
+__host__ __device__ __forceinline__ uint64_t tbx_evolve_base(uint32_t plan_seed, int cand, uint64_t env_key)
+{
+    return tbx_splitmix64(tbx_splitmix64((uint64_t)plan_seed ^ ((uint64_t)cand << 32)) ^ env_key);
+}
+__host__ __device__ __forceinline__ uint64_t tbx_evolve_word(uint64_t base, int g, int i, int p)
+{
+    return tbx_splitmix64(base ^ ((uint64_t)g << 40) ^ ((uint64_t)i << 8) ^ (uint64_t)p);
+}
+// Individual i of generation 0: digit_0 = cand, the others drawn -- or, for individual 0 of a row with an init, taken from it.
+// 32-bit arithmetic throughout: a Breakout code of depth 16 reaches 2^32 - 1, and `pow` wraps only after its last use.
+__device__ __forceinline__ uint32_t tbx_evolve_first_code(int game, const TbxEvolveRow& r, uint64_t base, int cand, int i)
+{
+    const uint32_t L = (uint32_t)tbx_legal_count(game);
+    if (i == 0 && r.has_init) return r.init - r.init % L + (uint32_t)cand;
+    uint32_t code = (uint32_t)cand, pow = L;
+    for (int p = 1; p < r.depth; p++, pow *= L) code += (uint32_t)((tbx_evolve_word(base, 0, i, p) >> 32) % L) * pow;
+    return code;
+}
+// The scratch of one env range, indexed by the group's number WITHIN the range: recs[group][stride] the played individuals (slots
+// 0 .. elite-1 of a later generation: the records the select pass carried), codes[group][stride] the codes of the generation about
+// to be played.  stride: the largest population of the range (shared arguments: the population; per-env rows: the largest there
+// can be, or the largest the host saw).
+struct TbxEvolveScratch {
+    TbxBeamCand* recs;
+    uint32_t* codes;
+    int stride;
+};
+
+// A unit is (env, first action, individual) -- ONE leaf: unit = ((env - first_env) * L + cand) * slots + (i - first_slot), with
+// slots individuals from first_slot on per group (generation 0: all of them from 0; later: the elites below first_slot are nobody's
+// unit).  An env whose row is refused, whose own generations are below `gen`, whose population has no individual i or whose
+// individual i is an elite of this generation (its record was carried) exits at once.
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_evolve_kernel(G g, TbxEditArgs a, int gen, int first_slot, int slots, int first_env, int count, TbxEvolveScratch sc)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const int lane = threadIdx.x & 63;
+    const int rel = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (rel >= count) return;
+    const int group = rel / slots;
+    int i = first_slot + (rel - group * slots);
+    int env = first_env + group / L, cand = group % L;
+    TbxLookahead<G::GAME, true> look;
+    TbxEvolveRow r;
+    bool ok = look.read_plan(a, env, 1);
+    ok = tbx_evolve_row(G::GAME, a, env, r) && ok;
+    ok = ok && gen <= r.generations && i < r.population && (gen == 0 || i >= r.elite);
+    uint32_t code = 0;
+    if (ok) {
+        if (gen == 0) code = tbx_evolve_first_code(G::GAME, r, tbx_evolve_base(r.plan_seed, cand, (uint64_t)a.getu(env, 8) + (uint64_t)env), cand, i);
+        else code = sc.codes[(size_t)group * sc.stride + i];
+    }
+    look.depth = r.depth;
+    look.code = code;
+    if (G::WAVE) {
+        env = wave_uniform(env); ok = wave_uniform(ok); i = wave_uniform(i);
+        look.uniform_plan();
+    }
+    if (!ok) return;
+    const TbxLookFields f = g.leaf(env, lane, look);
+    if (!G::WAVE || lane == 0) sc.recs[(size_t)group * sc.stride + i] = TbxBeamCand{f, look.code, 0u};
+}
+
+template <class G>
+void tbx_launch_evolve(const G& g, const TbxEditArgs& a, int gen, int first_slot, int slots, int first_env, int envs, const TbxEvolveScratch& sc, hipStream_t s)
+{
+    const long long count = (long long)envs * tbx_legal_count(G::GAME) * slots;     // (lookahead_evolve, engine.hip: below 2^30)
+    const long long threads = count * (G::WAVE ? 64 : 1);
+    hipLaunchKernelGGL(tbx_evolve_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, gen, first_slot, slots, first_env, (int)count, sc);
 }
 
 // ---- TBX_QUERY_LOOKAHEAD_SAMPLES (include/toybox_amd.h): `samples` futures per (env, first action), summed on the device.
@@ -1488,6 +1601,8 @@ struct GameOps {
     virtual int lookahead_search_samples(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     // TBX_QUERY_LOOKAHEAD_BEAM: tbx_beam_kernel over the candidates of `level` of envs [first_env, first_env + envs)
     virtual int lookahead_beam(tbx_engine* e, const TbxEditArgs&, int /*level*/, int /*slots*/, int /*first_env*/, int /*envs*/, const struct TbxBeamScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    // TBX_QUERY_LOOKAHEAD_EVOLVE: tbx_evolve_kernel over individuals [first_slot, first_slot + slots) of generation `gen` of envs [first_env, first_env + envs)
+    virtual int lookahead_evolve(tbx_engine* e, const TbxEditArgs&, int /*gen*/, int /*first_slot*/, int /*slots*/, int /*first_env*/, int /*envs*/, const struct TbxEvolveScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     // TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: tbx_beam_samples_kernel over the candidates of `level`, each cut into `chunks` sample chunks
     virtual int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs&, int /*level*/, int /*slots*/, int /*chunks*/, int /*first_env*/, int /*envs*/, const struct TbxBeamSamplesScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     virtual int search_lanes() const { return 64; }

@@ -231,6 +231,71 @@ def beam_args(game, n_envs, frames, depth, width, hold=1, objective=0, rest=None
     return args, True
 
 
+def evolve_args(game, n_envs, frames, depth, population=1, generations=0, elite=1, plan_seed=0, mutation=64, init=-1, hold=1, objective=0, rest=None,
+                seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD_EVOLVE: columns {frames, hold, depth, objective, rest, seed_lo, seed_hi, t,
+    env_offset, population, generations, elite, plan_seed, mutation, init} -- the beam's first nine with the six of the evolution
+    appended; (args, per_env) as lookahead_args gives them.  init: a plan code of `depth` (its digit 0 is replaced by every first
+    action in turn) or -1 / None for none.  Shared values are range-checked here (ValueError): depth 1 .. PLAN_MAX_DEPTH (no
+    n_legal ** depth cap), population 1 .. EVOLVE_MAX_POPULATION, generations 0 .. EVOLVE_MAX_GENERATIONS, elite 1 .. population,
+    plan_seed 0 .. 2**32 - 1, mutation 0 .. 256, init -1 or 0 .. n_legal ** depth - 1, objective 0 / "return" or 1 / "survival";
+    per-env rows are left to the device (a bad row answers zeros)."""
+    name = _game_name(game)
+    if isinstance(objective, str):
+        if objective not in SEARCH_OBJECTIVES:
+            raise ValueError("evolve objective is 'return' or 'survival', got %r" % (objective,))
+        objective = SEARCH_OBJECTIVES[objective]
+    if not np.ndim(objective) and int(objective) not in (0, 1):
+        raise ValueError("evolve objective is 0 (return) or 1 (survival), got %r" % (objective,))
+    if not np.ndim(depth) and not 1 <= int(depth) <= _abi.PLAN_MAX_DEPTH[name]:
+        raise ValueError("evolve depth must be 1 .. %d, got %r" % (_abi.PLAN_MAX_DEPTH[name], depth))
+    init = -1 if init is None else init
+    own = (("population", population), ("generations", generations), ("elite", elite), ("plan_seed", plan_seed), ("mutation", mutation), ("init", init))
+    for what, c in own:
+        if np.ndim(c) > 1 or (np.ndim(c) == 1 and len(c) != int(n_envs)):
+            raise ValueError("lookahead %s is a scalar or one value per env (%d), got shape %r" % (what, n_envs, np.shape(c)))
+    for what, c, lo, hi in (("population", population, 1, _abi.EVOLVE_MAX_POPULATION), ("generations", generations, 0, _abi.EVOLVE_MAX_GENERATIONS),
+                            ("plan_seed", plan_seed, 0, (1 << 32) - 1), ("mutation", mutation, 0, 256)):
+        if not np.ndim(c) and not lo <= int(c) <= hi:
+            raise ValueError("evolve %s must be %d .. %d, got %r" % (what, lo, hi, c))
+    if not np.ndim(elite) and not np.ndim(population) and not 1 <= int(elite) <= int(population):
+        raise ValueError("evolve elite must be 1 .. population (%r), got %r" % (population, elite))
+    if not np.ndim(elite) and int(elite) < 1:
+        raise ValueError("evolve elite must be at least 1, got %r" % (elite,))
+    if not np.ndim(init) and int(init) != -1:
+        if int(init) < 0 or (not np.ndim(depth) and int(init) >= len(_abi.LEGAL_ACTIONS[name]) ** int(depth)):
+            raise ValueError("evolve init must be -1 or a plan code 0 .. n_legal ** depth - 1, got %r at depth %r" % (init, depth))
+    base, per_env = _plan_rows("objective", name, n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
+    if not per_env and not any(np.ndim(c) for _, c in own):
+        return list(base) + [float(int(c)) for _, c in own], False
+    args = np.empty((int(n_envs), 15), np.float64)
+    args[:, :9] = np.asarray(base, np.float64)
+    for k, (_, c) in enumerate(own):
+        args[:, 9 + k] = np.asarray(c, np.float64)
+    return args, True
+
+
+def evolve_word(plan_seed, env, action_index, g, i, p):
+    """The draw word w(g, i, p) of TBX_QUERY_LOOKAHEAD_EVOLVE for env number `env` (env_offset + the env's index, below 2**64) and
+    first action index `action_index`: splitmix64(base ^ (g << 40) ^ (i << 8) ^ p) with
+    base = splitmix64(splitmix64(plan_seed ^ (action_index << 32)) ^ env).  With it a caller reproduces every population."""
+    base = _splitmix64(_splitmix64(int(plan_seed) ^ (int(action_index) << 32)) ^ (int(env) & 0xFFFFFFFFFFFFFFFF))
+    return _splitmix64(base ^ (int(g) << 40) ^ (int(i) << 8) ^ int(p))
+
+
+def evolve_generation0(game, depth, population, plan_seed, env, action_index, init=None):
+    """The plan codes of generation 0 of TBX_QUERY_LOOKAHEAD_EVOLVE for env number `env` (env_offset + index) and first action index
+    `action_index`: uint64 [population]; individual 0 takes digits 1 .. depth-1 of `init` where one is given."""
+    L = len(_abi.LEGAL_ACTIONS[_game_name(game)])
+    codes = np.empty(int(population), np.uint64)
+    for i in range(int(population)):
+        if i == 0 and init is not None and int(init) >= 0:
+            codes[i] = int(init) - int(init) % L + int(action_index)
+        else:
+            codes[i] = int(action_index) + sum(((evolve_word(plan_seed, env, action_index, 0, i, p) >> 32) % L) * L ** p for p in range(1, int(depth)))
+    return codes
+
+
 SAMPLE_FIELDS = ("samples", "ret_sum", "ret_min", "ret_max", "lives_sum", "lost", "ended", "safe_frames_sum")
 
 
@@ -642,6 +707,28 @@ class Engine:
     @beam_range_envs.setter
     def beam_range_envs(self, envs):
         self.set_option(_abi.OPT_BEAM_RANGE_ENVS, envs)
+
+    def lookahead_evolve(self, frames, depth, population, generations, elite=None, mutation=None, plan_seed=0, init=None, hold=1, objective="return",
+                         rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_EVOLVE: evolutionary search over WHOLE plans of `depth` periods on the device, with a budget the
+        caller chooses and an optional warm start.  Per env and first action a population of `population` plans (generation 0:
+        drawn from plan_seed; individual 0 the plan code `init`, its first action replaced, where one is given) is played, ranked
+        under `objective` and bred `generations` times: the `elite` best persist, every other individual copies a drawn elite and
+        redraws each later digit with probability mutation / 256.  Defaults: elite max(1, population // 4), mutation
+        max(1, round(256 / max(depth - 1, 1))) -- about one digit per child.  The dict of lookahead_beam: the five fields and code
+        [N, n_legal] of the best plan of the last generation, plan [N, n_legal, depth].  More generations are never worse; the
+        returned code fed to lookahead_plan gives the row.  Nothing in the engine is written."""
+        if elite is None:
+            elite = np.maximum(1, np.asarray(population) // 4) if np.ndim(population) else max(1, int(population) // 4)
+        if mutation is None:
+            mutation = np.maximum(1, np.round(256 / np.maximum(np.asarray(depth) - 1, 1))) if np.ndim(depth) else max(1, round(256 / max(int(depth) - 1, 1)))
+        args, _ = evolve_args(self.game, self.n_envs, frames, depth, population, generations, elite, plan_seed, mutation, init, hold, objective, rest, seed, t, env_offset)
+        return self._best_plans_dict(self.reduce(_abi.QUERY_LOOKAHEAD_EVOLVE, args), depth)
+
+    @property
+    def evolve_ranges(self):
+        """into how many env ranges the last lookahead_evolve was cut (0: none yet)"""
+        return self.get_option(_abi.OPT_EVOLVE_RANGES)
 
     def _best_plans_dict(self, out, depth):
         L = len(self.legal_actions)

@@ -103,6 +103,24 @@ def _beam(env, frames, hold, depth, width, objective, rest, seed, t):
     return _with_best(env, out, depth, objective)
 
 
+def _evolve(env, frames, hold, depth, population, generations, elite, mutation, plan_seed, init_plan, objective, rest, seed, t):
+    """Engine.lookahead_evolve for an adapter: as _beam; init_plan [depth] or [num_envs, depth] action indices becomes the code"""
+    init = None
+    if init_plan is not None:
+        p = np.asarray(init_plan, np.int64)
+        if p.ndim not in (1, 2) or p.shape[-1] != int(depth) or (p.ndim == 2 and p.shape[0] != env.num_envs):
+            raise ValueError("init_plan is [depth] or [num_envs, depth] action indices with depth %d, got shape %r" % (int(depth), p.shape))
+        _ale(env, p)                                         # (range check; the action set is the legal set in its order: an index is a digit)
+        L = np.uint64(len(env._action_set))
+        code = np.zeros(p.shape[:-1], np.uint64)
+        for k in range(p.shape[-1] - 1, -1, -1):
+            code = code * L + p[..., k].astype(np.uint64)
+        init = code.astype(np.float64) if p.ndim == 2 else int(code)
+    out = env.engine.lookahead_evolve(frames, int(depth), int(population), int(generations), elite=elite, mutation=mutation, plan_seed=plan_seed, init=init,
+                                      hold=hold, objective=objective, rest=_ale(env, rest), seed=seed, t=t)
+    return _with_best(env, out, depth, objective)
+
+
 def _with_best(env, out, depth, objective):
     """the rows of a search or a beam: plan as action indices, best_action and best_plan added (one lexsort per call)"""
     from ..engine import plan_digits
@@ -373,6 +391,17 @@ class ToyboxVecEnv:
         if self._in_flight is not None or self._pending is not None:
             self.step_wait()
         return _beam(self, int(steps), 1, depth, width, objective, rest, seed, t)
+
+    def evolve_search(self, steps, depth, population, generations, elite=None, mutation=None, plan_seed=0, init_plan=None, objective="return", rest=None,
+                      seed=0, t=0):
+        """Evolutionary search over whole plans of `depth` steps with a budget the caller chooses (Engine.lookahead_evolve): per
+        first action index a population of `population` action sequences is played, ranked and bred `generations` times from its
+        `elite` best by mutation.  init_plan ([depth] or [num_envs, depth] action indices; its first action is replaced by every
+        first action in turn) seeds the population -- a rolling-horizon controller hands in the last best_plan shifted by one
+        step.  The dict of search(); more generations are never worse.  Nothing is touched; a pending step_async ends first."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _evolve(self, int(steps), 1, depth, population, generations, elite, mutation, plan_seed, init_plan, objective, rest, seed, t)
 
     def lookahead_samples(self, steps, samples, rest=None, seed=0, t=0, salt=0, objective="return"):
         """`samples` random futures of `steps` steps per env and first action index, summed on the device without taking them
@@ -740,6 +769,14 @@ class ToyboxPreprocVecEnv:
         if self._in_flight is not None:
             self.step_wait()
         return _beam(self, int(steps) * self._skip, self._skip, depth, width, objective, rest, seed, t)
+
+    def evolve_search(self, steps, depth, population, generations, elite=None, mutation=None, plan_seed=0, init_plan=None, objective="return", rest=None,
+                      seed=0, t=0):
+        """ToyboxVecEnv.evolve_search in agent steps: steps x skip raw frames, every action held for skip frames; raw frames, no
+        wrapper, as in lookahead().  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _evolve(self, int(steps) * self._skip, self._skip, depth, population, generations, elite, mutation, plan_seed, init_plan, objective, rest, seed, t)
 
     def lookahead_samples(self, steps, samples, rest=None, seed=0, t=0, salt=0, objective="return"):
         """ToyboxVecEnv.lookahead_samples in agent steps: steps x skip raw frames, every action held for skip frames; raw frames,

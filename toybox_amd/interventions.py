@@ -266,6 +266,23 @@ class BatchIntervention:
                                          rest=self._full(rest, -1), seed=self._full(seed, 0), t=self._full(t, 0), env_offset=self._full(env_offset, 0))
         return {k: v[self.first:self.first + self.count] for k, v in out.items()}
 
+    def lookahead_evolve(self, frames, depth, population, generations, elite=None, mutation=None, plan_seed=0, init=None, hold=1, objective="return",
+                         rest=None, seed=0, t=0, env_offset=0):
+        """Engine.lookahead_evolve over the range: the five fields and code [count, n_legal], plan [count, n_legal, depth].  The
+        rows are always per env: the envs outside the range ask for the smallest query there is (one individual, no generation)."""
+        self._flush()
+        if np.ndim(objective):
+            objective = self._full(objective, 0)
+
+        def col(c, fill):
+            return self._full(c if np.ndim(c) else np.full(self.count, c), fill)
+        out = self.engine.lookahead_evolve(self._full(frames, 1), self._full(depth, 1), col(population, 1), col(generations, 0),
+                                           elite=None if elite is None else self._full(elite, 1), mutation=None if mutation is None else self._full(mutation, 0),
+                                           plan_seed=self._full(plan_seed, 0), init=None if init is None else self._full(init, -1), hold=self._full(hold, 1),
+                                           objective=objective, rest=self._full(rest, -1), seed=self._full(seed, 0), t=self._full(t, 0),
+                                           env_offset=self._full(env_offset, 0))
+        return {k: v[self.first:self.first + self.count] for k, v in out.items()}
+
     def lookahead_samples(self, frames, samples, hold=1, salt=0, rest=None, seed=0, t=0, env_offset=0):
         """Engine.lookahead_samples over the range: the eight fields, each [count, n_legal]"""
         self._flush()
