@@ -834,6 +834,53 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
 #define TBX_EVOLVE_MAX_POPULATION  256
 #define TBX_EVOLVE_MAX_GENERATIONS 64
 #define TBX_QUERY_LOOKAHEAD_EVOLVE 158  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, population, generations, elite, plan_seed, mutation, init} -> 6 * n_legal(game) */
+/* Closed-loop planning: pick, act and carry.  Queries 153 .. 158 answer one row per env and first action; this one runs such a
+ * planner, picks every env's winner among its L = n_legal(game) rows ON THE DEVICE, leaves the chosen action where the
+ * device-pointer steps read it and keeps the winner's plan, shifted by one period, as the next call's warm start -- so the loop
+ * plan, act, shift, plan again can be queued on one stream without the host in it.
+ *   Arguments: {planner, then the planner's own columns in its own order}.  planner is TBX_QUERY_LOOKAHEAD_SEARCH (153),
+ *   _SEARCH_SAMPLES (155), _BEAM (156), _BEAM_SAMPLES (157) or _EVOLVE (158): the five that carry an objective and answer a code
+ *   (greedy one-step choice: 153 with depth 1; over sampled futures: 155 with depth 1).  Trailing planner columns may be left out
+ *   with the planner's defaults; at most 1 + the planner's maximum (9, 11, 10, 12, 15) arguments -- for 158 that is
+ *   16 = TBX_EDIT_MAX_ARGS.  SHARED ARGUMENTS ONLY: per_env = 1 answers TBX_E_INVALID with nothing launched.  Every shared value is
+ *   range-checked exactly as the planner checks it.
+ *   Planning: the planner's query runs from the live state, unchanged; its rows [N][L][6 or 9] go to engine-owned scratch.
+ *   Pick: one winner a* per env among the L rows.  Planners 153 / 156 / 158: the search's order for `objective` on (ret, lives,
+ *   loss), then the smaller code -- codes of different first actions differ in digit 0, so the order is total.  Planners 155 / 157:
+ *   the order of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES on (ret_sum, lost, safe_frames_sum), then the smaller action index.
+ *   Out, width 11 for every game: out[env][0] = the ALE action legal[a*], [1] = the index a*, [2 ..] = the winner's planner row,
+ *   6 or 9 doubles, zero-padded to 9.
+ *   Side outputs, engine-owned (tbx_device_buffer):
+ *     TBX_BUF_PLAN_ACTION int32[N]: the ALE action of [0]; its pointer is a valid ale_actions_dev for tbx_step_device and
+ *       tbx_agent_step_device, and a step queued on the same stream behind the call reads the finished buffer.
+ *     TBX_BUF_PLAN_CARRY uint32[N]: the winner's code shifted by one period, carry = code / L + (code % L) * L^(depth-1) in 32-bit
+ *       arithmetic: the played digit wraps to the end, where the next call replaces nothing but digit 0.
+ *   The carry of an engine is zero from tbx_create on (carry 0 is the all-first-action plan, a valid code at every depth); both
+ *   arrays are made, zeroed, when this query is first asked with shared arguments and one of the five planners -- like the rollout
+ *   ids before the first chunk, the two ids answer TBX_E_INVALID until then -- and keep their addresses from there to tbx_destroy.  They are rewritten for
+ *   every env by each successful call of this query and left unchanged by a refused one.  They are NOT env state: TBX_EDIT_COPY_ENV, the
+ *   checkpoint edits, tbx_new_game and tbx_set_states leave them alone -- harmless, because an init is only one seeded individual.
+ *   Warm start from the carry: inside this query alone, planner 158 accepts init = -2: env e plays with
+ *   init = carry[e] % L^depth, the modulus taken in 64 bits (so a carry of a deeper call is cut to the depth at hand).  The rounds,
+ *   slots and env ranges are those of the shared row.  TBX_QUERY_LOOKAHEAD_EVOLVE itself keeps refusing -2.
+ *   "Nothing in the engine changes" holds for state, RNGs, step outputs, records, agent layer and checkpoint store: the two buffers
+ *   above and the scratch are the only writes.  On tbx_reduce_device everything runs on the caller's stream in order.
+ *   It follows that
+ *     (i)   out[env][2 ..] is the planner's own row for a*: feeding [1] and the code to TBX_QUERY_LOOKAHEAD_PLAN reproduces it as
+ *           the planner's consequences say;
+ *     (ii)  with 158 and init = -2, for every G the row of first action a is not worse than TBX_QUERY_LOOKAHEAD_PLAN's row for the
+ *           carried plan with digit 0 = a (it is individual 0 of generation 0, and elites persist), and it is the row of
+ *           TBX_QUERY_LOOKAHEAD_EVOLVE with per-env init = carry % L^depth;
+ *     (iii) two calls with equal arguments and no step between them give equal rows and actions whenever init != -2;
+ *     (iv)  env ranges (TBX_OPT_BEAM_RANGE_ENVS) and chunk options change no output bit.
+ *   TBX_E_INVALID, nothing launched, both buffers unchanged: per_env = 1, a planner other than the five, more arguments than
+ *   1 + the planner's maximum, whatever the planner refuses in a shared row. */
+#define TBX_QUERY_LOOKAHEAD_ACT 159  /* {planner, the planner's columns} -> 11 */
+/* ids of tbx_device_buffer that exist only once this query has run */
+enum {
+    TBX_BUF_PLAN_ACTION = 17,    /* int32[N]  the ALE action every env's winner of the last TBX_QUERY_LOOKAHEAD_ACT plays first */
+    TBX_BUF_PLAN_CARRY = 18      /* uint32[N] that winner's plan code shifted by one period: the next call's init = -2 */
+};
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
 int tbx_edit_device(tbx_engine* engine, int op, const double* args, int n_args, int per_env, const uint8_t* mask_dev, void* stream);

@@ -26,6 +26,8 @@ BUF_AGENT_PLANE = 13
 BUF_AGENT_RING = 14
 BUF_ROLLOUT_FRAMES = 15            # uint8[k][N][H][W][C] frames of the last tbx_rollout_synthetic
 BUF_ROLLOUT_PACKED = 16            # uint64[k][stride] its step records (stride = the gather's records_per_rank under a K-step ring, else N)
+BUF_PLAN_ACTION = 17               # int32[N] the ALE action every env's winner of the last TBX_QUERY_LOOKAHEAD_ACT plays first
+BUF_PLAN_CARRY = 18                # uint32[N] that winner's plan code shifted by one period (init = -2 of the next call)
 GATHER_ID_BYTES = 128
 # engine options (tbx_set_option)
 OPT_PIPELINE, OPT_STEP_FORM, OPT_RENDER_SPLIT, OPT_AGENT_GENERIC, OPT_RESIDENT_STEP, OPT_GATHER_EVERY = 0, 1, 2, 3, 4, 5
@@ -120,6 +122,7 @@ QUERY_LOOKAHEAD_BEAM_SAMPLES = 157
 EVOLVE_MAX_POPULATION = 256
 EVOLVE_MAX_GENERATIONS = 64
 QUERY_LOOKAHEAD_EVOLVE = 158
+QUERY_LOOKAHEAD_ACT = 159
 # the legal sets in the engine's order (tbx_legal_actions) and TBX_PLAN_MAX_DEPTH: the largest depth with n_legal ** depth <= 2 ** 32
 LEGAL_ACTIONS = {"breakout": (0, 1, 3, 4), "space_invaders": (0, 1, 3, 4, 11, 12), "amidar": (0, 1, 2, 3, 4, 5), "gridworld": (0, 2, 3, 4, 5)}
 PLAN_MAX_DEPTH = {"breakout": 16, "space_invaders": 12, "amidar": 12, "gridworld": 13}

@@ -309,6 +309,7 @@ int tbx_destroy(tbx_engine* e)
     }
     pipe_free(e);
     hipFree(e->actions);
+    hipFree(e->plan_action); hipFree(e->plan_carry); e->act_scratch.release();
     e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); e->sample_parts.release(); e->search_samples_parts.release(); e->beam_scratch.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
     hipFree(e->mask); hipFree(e->err_flag); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
     if (e->io_host) hipHostFree(e->io_host);
@@ -1151,6 +1152,7 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_LOOKAHEAD_SEARCH: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_BEAM: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_EVOLVE: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_ACT: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 11 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
@@ -1426,6 +1428,36 @@ static TbxEvolveBounds evolve_scan(const tbx_engine* e, const double* rows, int 
     return b;
 }
 
+// the shared row of a TBX_QUERY_LOOKAHEAD_EVOLVE: refused here, before anything is launched, else its budget in `b`
+static int evolve_shared_check(tbx_engine* e, const TbxEditArgs& a, TbxEvolveBounds& b)
+{
+    const int L = tbx_legal_count(e->game);
+    auto playable = [&](double v) {
+        if (v == -1.0) return true;
+        for (int i = 0; i < L; i++)
+            if (v == (double)tbx_legal_action(e->game, i)) return true;
+        return false;
+    };
+    if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+    if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+    const double dp = a.n > 2 ? a.v[2] : 1.0, pop = a.n > 9 ? a.v[9] : 1.0, gens = a.n > 10 ? a.v[10] : 0.0, elite = a.n > 11 ? a.v[11] : 1.0;
+    const double plan_seed = a.n > 12 ? a.v[12] : 0.0, mutation = a.n > 13 ? a.v[13] : 64.0, init = a.n > 14 ? a.v[14] : -1.0;
+    if (!(dp >= 1.0 && dp <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "evolve: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
+    if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "evolve: objective must be 0 (return) or 1 (survival)");
+    if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+    if (!(pop >= 1.0 && pop <= (double)TBX_EVOLVE_MAX_POPULATION)) return e->fail(TBX_E_INVALID, "evolve: population must be 1 .. TBX_EVOLVE_MAX_POPULATION");
+    if (!(gens >= 0.0 && gens <= (double)TBX_EVOLVE_MAX_GENERATIONS)) return e->fail(TBX_E_INVALID, "evolve: generations must be 0 .. TBX_EVOLVE_MAX_GENERATIONS");
+    b.frames = TbxEditArgs::to_int(a.v[0]);
+    b.population = TbxEditArgs::to_int(pop);
+    b.generations = TbxEditArgs::to_int(gens);
+    if (!(elite >= 1.0 && elite <= (double)b.population)) return e->fail(TBX_E_INVALID, "evolve: elite must be 1 .. population");
+    b.elite = TbxEditArgs::to_int(elite);
+    if (!(plan_seed >= 0.0 && plan_seed < 4294967296.0)) return e->fail(TBX_E_INVALID, "evolve: plan_seed must be 0 .. 2^32 - 1");
+    if (!(mutation >= 0.0 && mutation <= 256.0)) return e->fail(TBX_E_INVALID, "evolve: mutation must be 0 .. 256");
+    if (!(init == -1.0 || (init >= 0.0 && init < (double)tbx_plan_count(e->game, TbxEditArgs::to_int(dp))))) return e->fail(TBX_E_INVALID, "evolve: init must be -1 or 0 .. n_legal^depth - 1");
+    return TBX_OK;
+}
+
 // TBX_QUERY_LOOKAHEAD_EVOLVE: shared values are refused here, before anything is launched; per-env rows are met by the kernels.
 // Env ranges come from the beam's three budgets -- a launch under TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH leaf-frames and
 // TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units, the scratch under TBX_BEAM_SCRATCH_BYTES (starting values here as there: profiles/beam.md,
@@ -1442,29 +1474,8 @@ static int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, const TbxEvolve
     // per-env rows the host has not seen: the most a valid row can ask for
     TbxEvolveBounds b{TBX_LOOKAHEAD_MAX_FRAMES, TBX_EVOLVE_MAX_POPULATION, TBX_EVOLVE_MAX_GENERATIONS, 1};
     if (!a.per_env) {
-        auto playable = [&](double v) {
-            if (v == -1.0) return true;
-            for (int i = 0; i < L; i++)
-                if (v == (double)tbx_legal_action(e->game, i)) return true;
-            return false;
-        };
-        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
-        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
-        const double dp = a.n > 2 ? a.v[2] : 1.0, pop = a.n > 9 ? a.v[9] : 1.0, gens = a.n > 10 ? a.v[10] : 0.0, elite = a.n > 11 ? a.v[11] : 1.0;
-        const double plan_seed = a.n > 12 ? a.v[12] : 0.0, mutation = a.n > 13 ? a.v[13] : 64.0, init = a.n > 14 ? a.v[14] : -1.0;
-        if (!(dp >= 1.0 && dp <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "evolve: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
-        if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "evolve: objective must be 0 (return) or 1 (survival)");
-        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
-        if (!(pop >= 1.0 && pop <= (double)TBX_EVOLVE_MAX_POPULATION)) return e->fail(TBX_E_INVALID, "evolve: population must be 1 .. TBX_EVOLVE_MAX_POPULATION");
-        if (!(gens >= 0.0 && gens <= (double)TBX_EVOLVE_MAX_GENERATIONS)) return e->fail(TBX_E_INVALID, "evolve: generations must be 0 .. TBX_EVOLVE_MAX_GENERATIONS");
-        b.frames = TbxEditArgs::to_int(a.v[0]);
-        b.population = TbxEditArgs::to_int(pop);
-        b.generations = TbxEditArgs::to_int(gens);
-        if (!(elite >= 1.0 && elite <= (double)b.population)) return e->fail(TBX_E_INVALID, "evolve: elite must be 1 .. population");
-        b.elite = TbxEditArgs::to_int(elite);
-        if (!(plan_seed >= 0.0 && plan_seed < 4294967296.0)) return e->fail(TBX_E_INVALID, "evolve: plan_seed must be 0 .. 2^32 - 1");
-        if (!(mutation >= 0.0 && mutation <= 256.0)) return e->fail(TBX_E_INVALID, "evolve: mutation must be 0 .. 256");
-        if (!(init == -1.0 || (init >= 0.0 && init < (double)tbx_plan_count(e->game, TbxEditArgs::to_int(dp))))) return e->fail(TBX_E_INVALID, "evolve: init must be -1 or 0 .. n_legal^depth - 1");
+        const int rc = evolve_shared_check(e, a, b);
+        if (rc) return rc;
     } else if (rows) b = *rows;
     // per env: L groups of `population` individuals -- a record and a code each
     const long long units_per_env = (long long)L * b.population;
@@ -1802,6 +1813,138 @@ static int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, const Tbx
     return TBX_OK;
 }
 
+// ---- TBX_QUERY_LOOKAHEAD_ACT (include/toybox_amd.h): a planner's rows stay in engine-owned scratch, every env's winner is picked
+// on the device and its action left where the device-pointer steps read it.
+
+// planner 158 with init = -2: the shared row (all 15 columns: -2 can only stand in the last) spread to per-env rows [n][15] with
+// column 14 = carry % L^depth, the modulus in 64 bits (L^depth reaches 2^32).  One thread per env.
+__global__ __launch_bounds__(256) void tbx_act_spread_kernel(TbxEditArgs a, int game, int n, const uint32_t* __restrict__ carry, double* __restrict__ rows)
+{
+    const int env = blockIdx.x * 256 + threadIdx.x;
+    if (env >= n) return;
+    const uint64_t count = tbx_plan_count(game, TbxEditArgs::to_int(a.v[2]));      // (the host has checked the depth)
+    double* const r = rows + (size_t)env * 15;
+#pragma unroll
+    for (int i = 0; i < 14; i++) r[i] = a.v[i];
+    r[14] = (double)(uint32_t)((uint64_t)carry[env] % count);
+}
+
+// The winner among an env's L rows of `width` doubles, one thread per env, the running best in registers and compared in integers as
+// the select kernels compare (the rows are exact integers in binary64).  width 6, the rows of queries 153 / 156 / 158: the search's
+// order, then the smaller code -- codes of different first actions differ in digit 0.  width 9, the rows of 155 / 157: the order of
+// the sampled search on (ret_sum, lost, safe_frames_sum), then the smaller action index.  Out: {legal[a*], a*, the row zero-padded
+// to 9}, the action and the carry = code / L + (code % L) * L^(depth-1) in 32-bit arithmetic: L^(depth-1) <= 2^30 and the sum is
+// below L^depth <= 2^32.
+__global__ __launch_bounds__(256) void tbx_act_pick_kernel(const double* __restrict__ rows, int game, int n, int width, int objective, int depth, double* __restrict__ out,
+                                                           int32_t* __restrict__ action, uint32_t* __restrict__ carry)
+{
+    const int env = blockIdx.x * 256 + threadIdx.x;
+    if (env >= n) return;
+    const uint32_t L = (uint32_t)tbx_legal_count(game);
+    const bool sampled = width == 9;
+    const double* p = rows + (size_t)env * L * width;
+    double best[9];
+    TbxLookFields bf{0, 0, 0, 0, 0};
+    TbxSearchSamplesKey bk{0, 0, 0};
+    uint32_t best_tie = 0;
+    int best_a = 0;
+    for (int a = 0; a < (int)L; a++, p += width) {
+        double r[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) r[i] = i < 6 || sampled ? p[i] : 0.0;
+        const TbxLookFields f{(long long)r[0], (int)r[1], (int)r[2], (int)r[3], (int)r[4]};
+        const TbxSearchSamplesKey k{(long long)r[1], (int)r[5], (int)r[7]};
+        const uint32_t tie = sampled ? (uint32_t)a : (uint32_t)r[5];
+        const bool better = a == 0 || (sampled ? tbx_search_samples_better(objective, k, tie, bk, best_tie) : tbx_search_better(objective, f, tie, bf, best_tie));
+        if (better) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) best[i] = r[i];
+            bf = f; bk = k; best_tie = tie; best_a = a;
+        }
+    }
+    const uint32_t code = (uint32_t)(sampled ? best[8] : best[5]);
+    uint32_t pow = 1;
+    for (int i = 1; i < depth; i++) pow *= L;
+    const int ale = tbx_legal_action(game, best_a);
+    double* const o = out + (size_t)env * 11;
+    o[0] = (double)ale;
+    o[1] = (double)best_a;
+#pragma unroll
+    for (int i = 0; i < 9; i++) o[2 + i] = best[i];
+    action[env] = ale;
+    carry[env] = code / L + (code % L) * pow;
+}
+
+// TBX_BUF_PLAN_ACTION / TBX_BUF_PLAN_CARRY: made and zeroed by the first TBX_QUERY_LOOKAHEAD_ACT that names a planner
+static int act_alloc(tbx_engine* e)
+{
+    if (e->plan_action && e->plan_carry) return TBX_OK;
+    EHIP(hipSetDevice(e->device));
+    const size_t bytes = sizeof(int32_t) * (size_t)e->n;
+    if (!e->plan_action) {
+        EHIP(hipMalloc((void**)&e->plan_action, bytes));
+        EHIP(hipMemsetAsync(e->plan_action, 0, bytes, e->stream));
+    }
+    if (!e->plan_carry) {
+        EHIP(hipMalloc((void**)&e->plan_carry, bytes));
+        EHIP(hipMemsetAsync(e->plan_carry, 0, bytes, e->stream));
+    }
+    EHIP(hipStreamSynchronize(e->stream));
+    return TBX_OK;
+}
+
+// TBX_QUERY_LOOKAHEAD_ACT: {planner, the planner's columns}.  The planner's own function refuses what it refuses, before anything is
+// launched; its rows go to act_scratch, and the pick follows on `s`.  Planner 158 with init = -2: the shared row is checked with
+// init = -1, spread to per-env rows with the carry in column 14, and lookahead_evolve runs on those rows under the SHARED row's
+// bounds -- the path tbx_reduce's host scan takes, so budgets, slots and generations are those of the shared call.
+static int lookahead_act(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s)
+{
+    if (a.per_env) return e->fail(TBX_E_INVALID, "act takes shared arguments only");
+    if (a.n < 1) return e->fail(TBX_E_INVALID, "act takes {planner, the planner's arguments}");
+    const double pl = a.v[0];
+    const int most = pl == (double)TBX_QUERY_LOOKAHEAD_SEARCH ? 9 : pl == (double)TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES ? 11 : pl == (double)TBX_QUERY_LOOKAHEAD_BEAM ? 10 :
+                     pl == (double)TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES ? 12 : pl == (double)TBX_QUERY_LOOKAHEAD_EVOLVE ? 15 : -1;
+    if (most < 0) return e->fail(TBX_E_INVALID, "act: planner must be 153, 155, 156, 157 or 158");
+    if (a.n - 1 > most) return e->fail(TBX_E_INVALID, "act: more arguments than the planner takes");
+    const int planner = (int)pl;
+    TbxEditArgs b;
+    memset(&b, 0, sizeof b);
+    b.n = a.n - 1;
+    for (int i = 0; i < b.n; i++) b.v[i] = a.v[i + 1];
+    const bool sampled = planner == TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES || planner == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES;
+    const bool from_carry = planner == TBX_QUERY_LOOKAHEAD_EVOLVE && b.n > 14 && b.v[14] == -2.0;
+    TbxEvolveBounds bounds{1, 1, 0, 1};
+    if (from_carry) {
+        b.v[14] = -1.0;
+        const int rc = evolve_shared_check(e, b, bounds);
+        if (rc) return rc;
+    }
+    const int L = tbx_legal_count(e->game);
+    int rc = act_alloc(e);
+    if (rc) return rc;
+    EHIP(e->act_scratch.reserve(sizeof(double) * (size_t)e->n * ((size_t)L * 9 + 15), e->stream, s));
+    double* const rows = e->act_scratch.p;
+    const unsigned blocks = (unsigned)((e->n + 255) / 256);
+    if (from_carry) {
+        double* const own = rows + (size_t)e->n * L * 9;
+        hipLaunchKernelGGL(tbx_act_spread_kernel, dim3(blocks), dim3(256), 0, s, b, e->game, e->n, e->plan_carry, own);
+        TbxEditArgs pe;
+        memset(&pe, 0, sizeof pe);
+        pe.n = 15;
+        pe.per_env = own;
+        rc = lookahead_evolve(e, pe, &bounds, rows, s);
+    } else if (planner == TBX_QUERY_LOOKAHEAD_SEARCH) rc = lookahead_plans(e, planner, b, rows, s);
+    else if (planner == TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES) rc = lookahead_search_samples(e, b, rows, s);
+    else if (planner == TBX_QUERY_LOOKAHEAD_BEAM) rc = lookahead_beam(e, b, rows, s);
+    else if (planner == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES) rc = lookahead_beam_samples(e, b, nullptr, rows, s);
+    else rc = lookahead_evolve(e, b, nullptr, rows, s);
+    if (rc) return rc;
+    const int depth = b.n > 2 ? TbxEditArgs::to_int(b.v[2]) : 1, objective = b.n > 3 ? TbxEditArgs::to_int(b.v[3]) : 0;
+    hipLaunchKernelGGL(tbx_act_pick_kernel, dim3(blocks), dim3(256), 0, s, rows, e->game, e->n, sampled ? 9 : 6, objective, depth, out_dev, e->plan_action, e->plan_carry);
+    EHIP(hipGetLastError());
+    return TBX_OK;
+}
+
 // the queries every game has (the engine's own), else the game's
 static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s, const TbxBeamSamplesBounds* beam_samples_rows = nullptr,
                          const TbxEvolveBounds* evolve_rows = nullptr)
@@ -1829,6 +1972,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
     if (query == TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES) return lookahead_search_samples(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES) return lookahead_beam_samples(e, a, beam_samples_rows, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_EVOLVE) return lookahead_evolve(e, a, evolve_rows, out_dev, s);
+    if (query == TBX_QUERY_LOOKAHEAD_ACT) return lookahead_act(e, a, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     return checkpoint_valid(e, a, out_dev, s);
 }
@@ -1883,6 +2027,7 @@ int tbx_reduce_device(tbx_engine* e, int query, const double* args, int n_args, 
     const int width = tbx_reduce_width(e->game, query);
     if (width < 0) return e->fail(TBX_E_INVALID, "unknown query for this game");
     if (!out_dev) return e->fail(TBX_E_INVALID, "output pointer is NULL");
+    if (query == TBX_QUERY_LOOKAHEAD_ACT && per_env) return e->fail(TBX_E_INVALID, "act takes shared arguments only");
     EHIP(hipSetDevice(e->device));
     EHIP(tbx_use_stream(e, (hipStream_t)stream));
     TbxEditArgs a;
@@ -1897,6 +2042,7 @@ int tbx_reduce(tbx_engine* e, int query, const double* args, int n_args, int per
     const int width = tbx_reduce_width(e->game, query);
     if (width < 0) return e->fail(TBX_E_INVALID, "unknown query for this game");
     if (!out_host) return e->fail(TBX_E_INVALID, "output pointer is NULL");
+    if (query == TBX_QUERY_LOOKAHEAD_ACT && per_env) return e->fail(TBX_E_INVALID, "act takes shared arguments only");
     EHIP(hipSetDevice(e->device));
     EHIP(tbx_use_stream(e, e->stream));
     TbxEditArgs a;
@@ -1967,6 +2113,12 @@ int tbx_device_buffer(tbx_engine* e, int which, void** out_ptr, size_t* out_byte
     case TBX_BUF_AGENT_EP_DONE: case TBX_BUF_AGENT_EP_RETURN: case TBX_BUF_AGENT_EP_LENGTH: case TBX_BUF_AGENT_PLANE: case TBX_BUF_AGENT_RING:
         return tbx_agent_buffer(e, which, out_ptr, out_bytes);
     case TBX_BUF_GATHERED: return tbx_gather_buffer(e, out_ptr, out_bytes);
+    case TBX_BUF_PLAN_ACTION: case TBX_BUF_PLAN_CARRY: {
+        if (!e->plan_action || !e->plan_carry) return e->fail(TBX_E_INVALID, "TBX_QUERY_LOOKAHEAD_ACT has not been called");
+        p = which == TBX_BUF_PLAN_ACTION ? (void*)e->plan_action : (void*)e->plan_carry;
+        b = N * 4;
+        break;
+    }
     default: return e->fail(TBX_E_INVALID, "unknown buffer id");
     }
     *out_ptr = p;

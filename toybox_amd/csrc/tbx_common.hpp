@@ -459,6 +459,10 @@ struct tbx_engine {
     int beam_samples_ranges = 0, beam_samples_chunks = 0;   // env ranges, and the most sample chunks of a level, of the last TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES (0: none yet)
     int beam_samples_max_chunks = 0;   // TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS (0: the engine's choice)
     int evolve_ranges = 0;             // env ranges of the last TBX_QUERY_LOOKAHEAD_EVOLVE (0: none yet); its scratch is beam_scratch
+    // TBX_QUERY_LOOKAHEAD_ACT: not env state -- made and zeroed on first use (act_alloc, engine.hip), never forked or checkpointed
+    int32_t* plan_action = nullptr;    // [N] TBX_BUF_PLAN_ACTION: the ALE action of every env's winner
+    uint32_t* plan_carry = nullptr;    // [N] TBX_BUF_PLAN_CARRY: the winner's code shifted by one period
+    TbxDevBuf<double> act_scratch;     // [N][n_legal][9] the planner's rows, then [N][15] per-env evolve rows (init from the carry)
     TbxDevBuf<void> staging;        // device POD staging for get/set state
     struct TbxEnvCopy* envcopy = nullptr;   // TBX_EDIT_COPY_ENV / TBX_EDIT_CHECKPOINT_*: the fork's scratch copy, the checkpoint store (envcopy.hip), made on first use
     GameOps* ops = nullptr;

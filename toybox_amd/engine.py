@@ -296,6 +296,84 @@ def evolve_generation0(game, depth, population, plan_seed, env, action_index, in
     return codes
 
 
+ACT_PLANNERS = {"search": _abi.QUERY_LOOKAHEAD_SEARCH, "search_samples": _abi.QUERY_LOOKAHEAD_SEARCH_SAMPLES, "beam": _abi.QUERY_LOOKAHEAD_BEAM,
+                "beam_samples": _abi.QUERY_LOOKAHEAD_BEAM_SAMPLES, "evolve": _abi.QUERY_LOOKAHEAD_EVOLVE}
+ACT_SAMPLED = (_abi.QUERY_LOOKAHEAD_SEARCH_SAMPLES, _abi.QUERY_LOOKAHEAD_BEAM_SAMPLES)
+
+
+def act_planner(planner):
+    """the query id of a planner of TBX_QUERY_LOOKAHEAD_ACT: one of ACT_PLANNERS' names or ids"""
+    pid = ACT_PLANNERS.get(planner) if isinstance(planner, str) else int(planner)
+    if pid not in ACT_PLANNERS.values():
+        raise ValueError("act planner is one of %r or their query ids, got %r" % (tuple(ACT_PLANNERS), planner))
+    return pid
+
+
+def act_args(game, planner, **planner_keywords):
+    """The shared argument row of TBX_QUERY_LOOKAHEAD_ACT: {planner, then the planner's own columns} as search_args /
+    search_samples_args / beam_args / beam_samples_args / evolve_args build them from `planner_keywords` (their n_envs is not
+    asked for: the query takes shared arguments only, and a per-env value raises ValueError), range-checked there.  planner: a
+    name of ACT_PLANNERS or its query id.  With the evolution init="carry" (or -2) becomes -2: every env is seeded with the
+    plan the last call left in BUF_PLAN_CARRY."""
+    pid = act_planner(planner)
+    build = {_abi.QUERY_LOOKAHEAD_SEARCH: search_args, _abi.QUERY_LOOKAHEAD_SEARCH_SAMPLES: search_samples_args, _abi.QUERY_LOOKAHEAD_BEAM: beam_args,
+             _abi.QUERY_LOOKAHEAD_BEAM_SAMPLES: beam_samples_args, _abi.QUERY_LOOKAHEAD_EVOLVE: evolve_args}[pid]
+    kw = dict(planner_keywords)
+    carry = False
+    if pid == _abi.QUERY_LOOKAHEAD_EVOLVE and "init" in kw and not np.ndim(kw["init"]) and kw["init"] is not None:
+        if isinstance(kw["init"], str) and kw["init"] != "carry":
+            raise ValueError("evolve init is a plan code, -1 / None or 'carry', got %r" % (kw["init"],))
+        if isinstance(kw["init"], str) or int(kw["init"]) == -2:
+            carry, kw["init"] = True, -1
+    if "n_envs" in kw:
+        raise ValueError("act takes shared arguments only: no n_envs")
+    args, per_env = build(game, 1, **kw)
+    if per_env:
+        raise ValueError("act takes shared arguments only, got a per-env value")
+    args = [float(pid)] + [float(v) for v in args]
+    if carry:
+        args[15] = -2.0
+    return args
+
+
+def plan_pick(rows, objective=0, sampled=False):
+    """The pick of TBX_QUERY_LOOKAHEAD_ACT in numpy: rows [N, n_legal, 6] of a search, a beam or an evolution ({ret, score, lives,
+    frames run, life lost at, code}) or, sampled, [N, n_legal, 9] of their sampled forms (the eight sums, then the code) -> the
+    winner's action index, int64 [N].  Not sampled: the search's order for `objective` (0 / "return": the larger ret, lives,
+    loss; 1 / "survival": lives, loss, ret; loss = life lost at, none counting as later than any), then the smaller code.
+    Sampled: the larger ret_sum, the smaller lost, the larger safe_frames_sum ("survival": lost, safe_frames_sum, ret_sum), then
+    the smaller index."""
+    objective = SEARCH_OBJECTIVES.get(objective, objective) if isinstance(objective, str) else int(objective)
+    if objective not in (0, 1):
+        raise ValueError("objective is 0 / 'return' or 1 / 'survival', got %r" % (objective,))
+    r = np.asarray(rows)
+    if r.ndim != 3 or r.shape[2] != (9 if sampled else 6):
+        raise ValueError("rows are [N, n_legal, %d], got shape %r" % (9 if sampled else 6, r.shape))
+    r = r.astype(np.int64)
+    if sampled:
+        ret, k1, k2 = -r[..., 1], r[..., 5], -r[..., 7]
+        tie = np.broadcast_to(np.arange(r.shape[1]), r.shape[:2])
+    else:
+        ret, k1 = -r[..., 0], -r[..., 2]
+        k2 = -np.where(r[..., 4] < 0, 1 << 30, r[..., 4])
+        tie = r[..., 5]
+    keys = (ret, k1, k2) if objective == 0 else (k1, k2, ret)
+    # np.lexsort: the last key is the primary one, ascending
+    return np.lexsort((tie,) + tuple(reversed(keys)), axis=1)[:, 0].astype(np.int64)
+
+
+def plan_shift(game, code, depth):
+    """A plan code shifted by one period, as TBX_QUERY_LOOKAHEAD_ACT leaves it in BUF_PLAN_CARRY: code // L + (code % L) *
+    L ** (depth - 1) -- np.roll(digits, -1); an int or a uint64 array"""
+    L = len(_abi.LEGAL_ACTIONS[_game_name(game)])
+    if not 1 <= int(depth) <= _abi.PLAN_MAX_DEPTH[_game_name(game)]:
+        raise ValueError("plan depth must be 1 .. %d, got %r" % (_abi.PLAN_MAX_DEPTH[_game_name(game)], depth))
+    if not np.ndim(code):
+        return int(code) // L + (int(code) % L) * L ** (int(depth) - 1)
+    c = np.asarray(code).astype(np.uint64)
+    return c // np.uint64(L) + (c % np.uint64(L)) * np.uint64(L ** (int(depth) - 1))
+
+
 SAMPLE_FIELDS = ("samples", "ret_sum", "ret_min", "ret_max", "lives_sum", "lost", "ended", "safe_frames_sum")
 
 
@@ -729,6 +807,49 @@ class Engine:
     def evolve_ranges(self):
         """into how many env ranges the last lookahead_evolve was cut (0: none yet)"""
         return self.get_option(_abi.OPT_EVOLVE_RANGES)
+
+    def lookahead_act(self, planner, **planner_keywords):
+        """TBX_QUERY_LOOKAHEAD_ACT: the planner's query (a name of ACT_PLANNERS or its id; keywords as act_args takes them) with
+        every env's winner picked on the device (plan_pick's rule).  Returns a dict of [N] arrays: action (the ALE id, also left
+        in BUF_PLAN_ACTION for step_device / agent_step_device), action_index, the winner's fields (LOOKAHEAD_FIELDS, or
+        SAMPLE_FIELDS for the sampled planners), code (uint64) and plan [N, depth] (digits: indices into legal_actions, the first
+        being action_index).  BUF_PLAN_CARRY keeps plan_shift(code) for the evolution's init="carry" of the next call.  Nothing else
+        in the engine is written."""
+        args = act_args(self.game, planner, **planner_keywords)
+        return self._act_dict(self.reduce(_abi.QUERY_LOOKAHEAD_ACT, args), act_planner(planner), planner_keywords.get("depth", 1))
+
+    def lookahead_act_device(self, planner, out_ptr, stream=0, **planner_keywords):
+        """lookahead_act, asynchronous on `stream`: rows float64[N][11] = {action, action_index, the winner's planner row
+        zero-padded to 9} into the device buffer at out_ptr; a step_device(plan_action_ptr, stream=stream) queued behind it reads
+        the finished actions"""
+        self.reduce_device(_abi.QUERY_LOOKAHEAD_ACT, out_ptr, act_args(self.game, planner, **planner_keywords), stream=stream)
+
+    @property
+    def plan_action_ptr(self):
+        """device address of BUF_PLAN_ACTION, int32[N]; it exists from the engine's first lookahead_act / lookahead_act_device on"""
+        return self.device_buffer(_abi.BUF_PLAN_ACTION)[0]
+
+    def plan_buffers(self):
+        """(BUF_PLAN_ACTION int32[N], BUF_PLAN_CARRY uint32[N]) on the host, after everything queued has finished"""
+        from . import hip
+        action, carry = np.empty(self.n_envs, np.int32), np.empty(self.n_envs, np.uint32)
+        pa, pc = self.device_buffer(_abi.BUF_PLAN_ACTION)[0], self.device_buffer(_abi.BUF_PLAN_CARRY)[0]
+        self.sync()
+        hip.memcpy_dtoh(action, pa, action.nbytes)
+        hip.memcpy_dtoh(carry, pc, carry.nbytes)
+        return action, carry
+
+    def _act_dict(self, out, planner, depth):
+        out = np.asarray(out).reshape(self.n_envs, 11)
+        res = {"action": out[:, 0].astype(np.int64), "action_index": out[:, 1].astype(np.int64)}
+        if planner in ACT_SAMPLED:
+            res.update(self._samples_dict(out[:, 2:10]))
+            res["code"] = out[:, 10].astype(np.uint64)
+        else:
+            res.update(self._lookahead_dict(out[:, 2:7]))
+            res["code"] = out[:, 7].astype(np.uint64)
+        res["plan"] = plan_digits(len(self.legal_actions), res["code"], int(depth))
+        return res
 
     def _best_plans_dict(self, out, depth):
         L = len(self.legal_actions)

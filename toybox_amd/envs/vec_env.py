@@ -192,6 +192,81 @@ def _beam_samples(env, frames, hold, depth, width, samples, objective, rest, see
     return _with_sample_best(env, out, depth, objective)
 
 
+class _PlanLoop:
+    """What plan_step / plan_rollout of an adapter keep on the device: a stream of their own, the rows of the last rollout's
+    TBX_QUERY_LOOKAHEAD_ACT calls [k][N][11] and its per-step rewards and dones, copied device-to-device behind every step"""
+
+    def __init__(self, env):
+        from .. import hip
+        self.hip, self.env = hip, env
+        self.stream = hip.Stream()
+        self.bufs = {}                 # name -> (device address, bytes)
+        self.rows = None               # (k, planner id) of the last rollout
+        self.planned = False
+
+    def buf(self, name, nbytes):
+        p, b = self.bufs.get(name, (0, 0))
+        if b < nbytes:
+            self.stream.synchronize()
+            self.hip.free(p)
+            p, b = self.hip.malloc(nbytes), nbytes
+            self.bufs[name] = (p, b)
+        return p
+
+    def host(self, name, shape, dtype):
+        out = np.empty(shape, dtype)
+        self.hip.memcpy_dtoh(out, self.bufs[name][0], out.nbytes)
+        return out
+
+    def args(self, planner, frames, hold, depth, objective, rest, seed, t, kw):
+        """the argument row of one period: the adapter's defaults for the evolution filled in, init 'carry' once a plan is there"""
+        from ..engine import act_args, act_planner
+        pid, kw = act_planner(planner), dict(kw)
+        if pid == _abi.QUERY_LOOKAHEAD_EVOLVE:
+            kw.setdefault("population", 16)
+            kw.setdefault("generations", 2)
+            if kw.get("elite") is None:
+                kw["elite"] = max(1, int(kw["population"]) // 4)
+            if kw.get("mutation") is None:
+                kw["mutation"] = max(1, round(256 / max(int(depth) - 1, 1)))
+            if kw.get("init") is None:
+                kw["init"] = "carry" if self.planned else -1
+        return pid, act_args(self.env.game, pid, frames=frames, hold=hold, depth=int(depth), objective=objective, rest=_ale(self.env, rest), seed=seed, t=t, **kw)
+
+    def run(self, k, planner, frames, hold, depth, objective, rest, seed, t, kw, step, reward_id, reward_bytes, done_id, sub):
+        """k periods queued back to back on the stream: the query, then step(action pointer, stream) `sub` times, the reward and
+        done buffers copied behind each; ONE synchronisation at the end.  -> (reward [k, sub, N], done [k, sub, N])"""
+        env, eng, hip, n = self.env, self.env.engine, self.hip, self.env.num_envs
+        rows = self.buf("rows", 8 * 11 * n * k)
+        rew, don = self.buf("reward", reward_bytes * n * k * sub), self.buf("done", n * k * sub)
+        for i in range(k):
+            pid, args = self.args(planner, frames, hold, depth, objective, rest, seed, int(t) + i, kw)
+            eng.reduce_device(_abi.QUERY_LOOKAHEAD_ACT, rows + 8 * 11 * n * i, args, stream=self.stream.ptr)
+            self.planned = True
+            action = eng.plan_action_ptr                 # (made by the engine's first such query; its address stays)
+            for j in range(sub):
+                step(action, self.stream.ptr)
+                at = i * sub + j
+                hip.memcpy_dtod_async(rew + reward_bytes * n * at, eng.device_buffer(reward_id)[0], reward_bytes * n, self.stream)
+                hip.memcpy_dtod_async(don + n * at, eng.device_buffer(done_id)[0], n, self.stream)
+        self.stream.synchronize()
+        self.rows = (k, pid)
+        return self.host("reward", (k, sub, n), np.float32 if reward_id == _abi.BUF_AGENT_REWARD else np.int32), self.host("done", (k, sub, n), np.uint8)
+
+    def actions(self):
+        if self.rows is None:
+            raise RuntimeError("plan_actions before the first plan_step / plan_rollout")
+        k, _ = self.rows
+        return self.host("rows", (k, self.env.num_envs, 11), np.float64)[..., 1].astype(np.int64)
+
+    def close(self):
+        self.stream.synchronize()
+        for p, _ in self.bufs.values():
+            self.hip.free(p)
+        self.bufs = {}
+        self.stream.close()
+
+
 def _fork_map(n, src, envs):
     """(src int[N], selected bool[N]) of a fork: src an int (one source fanned out) or one index per env; envs None (every
     env), a boolean mask or indices.  Unselected envs name themselves."""
@@ -248,6 +323,7 @@ class ToyboxVecEnv:
         self._codec = codec(self.game)
         self._pending = None
         self._in_flight = None
+        self._plan = None                   # plan_step / plan_rollout: made by the first call
         self.closed = False
         if seed is not None:
             self.seed(seed)
@@ -403,6 +479,45 @@ class ToyboxVecEnv:
             self.step_wait()
         return _evolve(self, int(steps), 1, depth, population, generations, elite, mutation, plan_seed, init_plan, objective, rest, seed, t)
 
+    def plan_rollout(self, k, planner="evolve", steps=16, depth=4, hold=1, objective="return", rest=None, seed=0, t=0, **planner_keywords):
+        """k closed-loop steps queued back to back on a stream of the env's own, no host synchronisation in between
+        (Engine.lookahead_act_device): per step the planner ("search", "search_samples", "beam", "beam_samples" or "evolve";
+        planner_keywords: width, samples, salt, population, generations, elite, mutation, plan_seed, init) looks `steps` steps of
+        `hold` frames each ahead with plans of `depth` steps, every env's winner is picked on the device, and its first action is
+        played for `hold` frames with auto-reset, read by the step from the device buffer the pick wrote.  Step i plans with
+        counter t + i, so drawn `rest` actions line up across calls.  The evolution (default population 16, generations 2) is
+        seeded from the second planned step of this env on with the last winner's plan shifted by one step (init="carry");
+        init=-1 switches that off.  Returns what step() returns with a leading axis k on rewards (summed over the held frames)
+        and dones (any of them): (obs after the last step, float32 [k, num_envs], bool [k, num_envs], infos of the last frame,
+        without cached_state).  plan_actions() reads the chosen action indices back."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        if int(k) < 1 or int(hold) < 1:
+            raise ValueError("plan_rollout takes k >= 1 steps of hold >= 1 frames")
+        if self._plan is None:
+            self._plan = _PlanLoop(self)
+        eng = self.engine
+        reward, done = self._plan.run(int(k), planner, int(steps) * int(hold), int(hold), depth, objective, rest, seed, t, planner_keywords,
+                                      lambda action, stream: eng.step_device(action, auto_reset=True, stream=stream), _abi.BUF_REWARD, 4, _abi.BUF_DONE, int(hold))
+        lives, score = np.empty(self.num_envs, np.int32), np.empty(self.num_envs, np.int32)
+        self._plan.hip.memcpy_dtoh(lives, eng.device_buffer(_abi.BUF_LIVES)[0], lives.nbytes)
+        self._plan.hip.memcpy_dtoh(score, eng.device_buffer(_abi.BUF_SCORE)[0], score.nbytes)
+        last = done[-1, -1].astype(bool)
+        infos = LazyInfos(self.num_envs, {"lives": lives, "score": np.where(last, 0, score)}, {})
+        return self._frames(), reward.sum(axis=1).astype(np.float32), done.any(axis=1), infos
+
+    def plan_step(self, planner="evolve", steps=16, depth=4, hold=1, objective="return", rest=None, seed=0, t=0, **planner_keywords):
+        """One closed-loop step, plan_rollout(1, ...): plan on the device, pick every env's winner there and play its first action
+        for `hold` frames.  Returns what step() returns."""
+        obs, reward, done, infos = self.plan_rollout(1, planner, steps, depth, hold, objective, rest, seed, t, **planner_keywords)
+        return obs, reward[0], done[0], infos
+
+    def plan_actions(self):
+        """The action indices the last plan_step / plan_rollout chose, int64 [k, num_envs], read back from the device on demand"""
+        if self._plan is None:
+            raise RuntimeError("plan_actions before the first plan_step / plan_rollout")
+        return self._plan.actions()
+
     def lookahead_samples(self, steps, samples, rest=None, seed=0, t=0, salt=0, objective="return"):
         """`samples` random futures of `steps` steps per env and first action index, summed on the device without taking them
         (Engine.lookahead_samples): future s draws its actions (rest None) under its own seed and, with a salt that is not 0,
@@ -447,6 +562,9 @@ class ToyboxVecEnv:
         if not self.closed:
             if self._in_flight is not None:
                 self.step_wait()
+            if self._plan is not None:
+                self._plan.close()
+                self._plan = None
             self.engine.close()                 # (the page-locked arrays live on while a caller holds an observation)
             self.closed = True
 
@@ -555,6 +673,7 @@ class ToyboxPreprocVecEnv:
                                new_plane=0 if obs_layout == "device_stack" else 2)     # host layouts: no stack on the device at all
         self._pending = None
         self._in_flight = None
+        self._plan = None                   # plan_step / plan_rollout: made by the first call
         self.closed = False
         self.tstart = time.time()                # Monitor.tstart (bench/monitor.py:19), VecMonitor.tstart (vec_monitor.py:12)
         n = self.num_envs
@@ -778,6 +897,44 @@ class ToyboxPreprocVecEnv:
             self.step_wait()
         return _evolve(self, int(steps) * self._skip, self._skip, depth, population, generations, elite, mutation, plan_seed, init_plan, objective, rest, seed, t)
 
+    def plan_rollout(self, k, planner="evolve", steps=16, depth=4, objective="return", rest=None, seed=0, t=0, **planner_keywords):
+        """ToyboxVecEnv.plan_rollout in agent steps: per step the planner looks steps x skip raw frames ahead with hold = skip
+        (on the engine pass hold = skip yourself: Engine.lookahead_act_device plans in raw frames) and ONE agent step
+        (tbx_agent_step_device) plays the winner's first action, read from the device buffer the pick wrote; raw frames, no
+        wrapper in the plan, as in lookahead().  k > 1 needs obs_layout="device_stack" (the host-side stacks of the other layouts
+        take one plane per step).  Returns (obs after the last step, rewards float32 [k, num_envs], dones bool [k, num_envs],
+        infos of the last step)."""
+        if self._in_flight is not None:
+            self.step_wait()
+        if int(k) < 1:
+            raise ValueError("plan_rollout takes k >= 1 steps")
+        if int(k) > 1 and self.obs_layout != "device_stack":
+            raise ValueError("plan_rollout with k > 1 needs obs_layout='device_stack'")
+        if self._plan is None:
+            self._plan = _PlanLoop(self)
+        eng = self.engine
+        reward, done = self._plan.run(int(k), planner, int(steps) * self._skip, self._skip, depth, objective, rest, seed, t, planner_keywords,
+                                      lambda action, stream: eng.agent_step_device(action, stream=stream), _abi.BUF_AGENT_REWARD, 4, _abi.BUF_AGENT_DONE, 1)
+        landed, key = self._landing()
+        st = self._st
+        eng.agent_fetch(ep_done=st["ep_done"], ep_return=st["ep_return"], ep_length=st["ep_length"], **{key: landed})
+        last = done[-1, 0].astype(bool)
+        ended = np.flatnonzero(st["ep_done"])
+        ts = round(time.time() - self.tstart, 6) if len(ended) else 0.0
+        extras = {int(i): {"episode": {"r": float(st["ep_return"][i]), "l": int(st["ep_length"][i]), "t": ts}} for i in ended}
+        return self._obs(self._stacked_obs(landed, last, False)), reward[:, 0], done[:, 0].astype(bool), LazyInfos(self.num_envs, None, extras)
+
+    def plan_step(self, planner="evolve", steps=16, depth=4, objective="return", rest=None, seed=0, t=0, **planner_keywords):
+        """One closed-loop agent step, plan_rollout(1, ...).  Returns what step() returns."""
+        obs, reward, done, infos = self.plan_rollout(1, planner, steps, depth, objective, rest, seed, t, **planner_keywords)
+        return obs, reward[0], done[0], infos
+
+    def plan_actions(self):
+        """The action indices the last plan_step / plan_rollout chose, int64 [k, num_envs], read back from the device on demand"""
+        if self._plan is None:
+            raise RuntimeError("plan_actions before the first plan_step / plan_rollout")
+        return self._plan.actions()
+
     def lookahead_samples(self, steps, samples, rest=None, seed=0, t=0, salt=0, objective="return"):
         """ToyboxVecEnv.lookahead_samples in agent steps: steps x skip raw frames, every action held for skip frames; raw frames,
         no wrapper, as in lookahead().  Between step_async and step_wait the step ends first."""
@@ -806,5 +963,8 @@ class ToyboxPreprocVecEnv:
                     self.step_wait()
                 except Exception:
                     pass
+            if self._plan is not None:
+                self._plan.close()
+                self._plan = None
             self.engine.close()
             self.closed = True
