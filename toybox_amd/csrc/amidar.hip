@@ -2289,45 +2289,9 @@ struct AmiOps : GameOps {
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
-    int lookahead_plan(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s) override
+    int lookahead_play(tbx_engine* e, const TbxEditArgs& a, const TbxPlanLaunch& l, hipStream_t s) override
     {
-        tbx_launch_plan(AmiLook{d}, a, e->n, out_dev, s);
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
-    {
-        tbx_launch_search(AmiLook{d}, a, chunks, first_env, envs, rows, s);
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_beam(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int first_env, int envs, const TbxBeamScratch& sc, hipStream_t s) override
-    {
-        tbx_launch_beam(AmiLook{d}, a, level, slots, first_env, envs, sc, s);
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, int gen, int first_slot, int slots, int first_env, int envs, const TbxEvolveScratch& sc, hipStream_t s) override
-    {
-        tbx_launch_evolve(AmiLook{d}, a, gen, first_slot, slots, first_env, envs, sc, s);
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int chunks, int first_env, int envs, const TbxBeamSamplesScratch& sc, hipStream_t s) override
-    {
-        tbx_launch_beam_samples(AmiLook{d}, a, level, slots, chunks, first_env, envs, sc, s);
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
-    {
-        tbx_launch_sample(AmiLook{d}, a, chunks, first_env, envs, rows, s);
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
-    {
-        tbx_launch_search_samples(AmiLook{d}, a, chunks, first_env, envs, rows, s);
+        if (!tbx_launch_planner(AmiLook{d}, a, l, s)) return e->fail(TBX_E_UNSUPPORTED, "lookahead_play: no play kernel for this query");
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

@@ -2421,52 +2421,12 @@ struct BreakoutOps : GameOps {
         return TBX_OK;
     }
 
-    int lookahead_plan(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s) override
+    int lookahead_play(tbx_engine* e, const TbxEditArgs& a, const TbxPlanLaunch& l, hipStream_t s) override
     {
-        if (!custom && use_tpe) tbx_launch_plan(BrkTLook{d, cfg_dev}, a, e->n, out_dev, s);
-        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_plan(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, e->n, out_dev, s); });
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_search(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
-    {
-        if (!custom && use_tpe) tbx_launch_search(BrkTLook{d, cfg_dev}, a, chunks, first_env, envs, rows, s);
-        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_search(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, chunks, first_env, envs, rows, s); });
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_beam(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int first_env, int envs, const TbxBeamScratch& sc, hipStream_t s) override
-    {
-        if (!custom && use_tpe) tbx_launch_beam(BrkTLook{d, cfg_dev}, a, level, slots, first_env, envs, sc, s);
-        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_beam(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, level, slots, first_env, envs, sc, s); });
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, int gen, int first_slot, int slots, int first_env, int envs, const TbxEvolveScratch& sc, hipStream_t s) override
-    {
-        if (!custom && use_tpe) tbx_launch_evolve(BrkTLook{d, cfg_dev}, a, gen, first_slot, slots, first_env, envs, sc, s);
-        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_evolve(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, gen, first_slot, slots, first_env, envs, sc, s); });
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, int level, int slots, int chunks, int first_env, int envs, const TbxBeamSamplesScratch& sc, hipStream_t s) override
-    {
-        if (!custom && use_tpe) tbx_launch_beam_samples(BrkTLook{d, cfg_dev}, a, level, slots, chunks, first_env, envs, sc, s);
-        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_beam_samples(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, level, slots, chunks, first_env, envs, sc, s); });
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_sample(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
-    {
-        if (!custom && use_tpe) tbx_launch_sample(BrkTLook{d, cfg_dev}, a, chunks, first_env, envs, rows, s);
-        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_sample(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, chunks, first_env, envs, rows, s); });
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
-    int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s) override
-    {
-        if (!custom && use_tpe) tbx_launch_search_samples(BrkTLook{d, cfg_dev}, a, chunks, first_env, envs, rows, s);
-        else tbx_dispatch<0, 1>(custom, [&](auto cu) { tbx_launch_search_samples(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, chunks, first_env, envs, rows, s); });
+        bool known = false;
+        if (!custom && use_tpe) known = tbx_launch_planner(BrkTLook{d, cfg_dev}, a, l, s);
+        else tbx_dispatch<0, 1>(custom, [&](auto cu) { known = tbx_launch_planner(BrkWaveLook<decltype(cu)::value != 0>{d, c}, a, l, s); });
+        if (!known) return e->fail(TBX_E_UNSUPPORTED, "lookahead_play: no play kernel for this query");
         TBX_HIP(hipGetLastError());
         return TBX_OK;
     }

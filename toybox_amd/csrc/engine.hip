@@ -1128,6 +1128,7 @@ int tbx_set_config(tbx_engine* e, const void* pod, size_t size)
 
 int tbx_reduce_width(int game, int query)
 {
+    const bool every_game = game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD;
     switch (query) {
     case TBX_QUERY_BRK_BRICKS_REMAINING: case TBX_QUERY_BRK_NUM_BRICKS: case TBX_QUERY_BRK_IS_CHANNEL: case TBX_QUERY_BRK_CHANNEL_COUNT:
     case TBX_QUERY_BRK_FIND_CHANNEL: return game == TBX_GAME_BREAKOUT ? 1 : TBX_E_INVALID;
@@ -1145,17 +1146,14 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_AMI_TILES_MASK: return game == TBX_GAME_AMIDAR ? 32 : TBX_E_INVALID;
     case TBX_QUERY_AMI_RANDOM_TILE: return game == TBX_GAME_AMIDAR ? 4 : TBX_E_INVALID;
     case TBX_QUERY_AMI_RANDOM_DIR: return game == TBX_GAME_AMIDAR ? 2 : TBX_E_INVALID;
-    case TBX_QUERY_CHECKPOINT_VALID: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 1 : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_ALL: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 * tbx_legal_count(game) : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_PLAN: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 5 : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_SEARCH: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_BEAM: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_EVOLVE: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_ACT: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 11 : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
-    case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: return game >= TBX_GAME_BREAKOUT && game <= TBX_GAME_GRIDWORLD ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
+    // the engine's own queries: every game has them
+    case TBX_QUERY_CHECKPOINT_VALID: return every_game ? 1 : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD: case TBX_QUERY_LOOKAHEAD_PLAN: return every_game ? 5 : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_ALL: return every_game ? 5 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_SEARCH: case TBX_QUERY_LOOKAHEAD_BEAM: case TBX_QUERY_LOOKAHEAD_EVOLVE: return every_game ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_ACT: return every_game ? 11 : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_SAMPLES: return every_game ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: return every_game ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
     default: return TBX_E_INVALID;
     }
 }
@@ -1177,6 +1175,63 @@ static int edit_args(tbx_engine* e, const double* args, int n_args, int per_env,
     a.per_env = e->edit_args.p;
     return TBX_OK;
 }
+
+// ---- The shared row of a lookahead query is refused on the host, before anything is launched (per-env rows are met by the kernels).
+// These are the only copies of the checks.  Every query calls them top to bottom in its own order -- the first fault of a row
+// decides the message -- with its own word in front of the colon.
+static bool playable(int game, double v)
+{
+    if (v == -1.0) return true;
+    for (int i = 0; i < tbx_legal_count(game); i++)
+        if (v == (double)tbx_legal_action(game, i)) return true;
+    return false;
+}
+// columns 0 and 1
+static int shared_frames_hold(tbx_engine* e, const TbxEditArgs& a)
+{
+    if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
+    if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+    return TBX_OK;
+}
+// column `col`, where the row has it: `name` ("first", "rest") is -1 or an action the game plays
+static int shared_action(tbx_engine* e, const TbxEditArgs& a, int col, const char* name)
+{
+    if (a.n > col && !playable(e->game, a.v[col])) return e->fail(TBX_E_INVALID, std::string("lookahead: ") + name + " is neither -1 nor a legal action of this game");
+    return TBX_OK;
+}
+// columns 2 and 3 of the planners that rank plans (a search checks its plan count between the two)
+static int shared_depth(tbx_engine* e, const char* word, double depth, int least)
+{
+    if (!(depth >= (double)least && depth <= (double)tbx_plan_max_depth(e->game)))
+        return e->fail(TBX_E_INVALID, std::string(word) + ": depth must be " + std::to_string(least) + " .. TBX_PLAN_MAX_DEPTH(game)");
+    return TBX_OK;
+}
+static int shared_objective(tbx_engine* e, const char* word, const TbxEditArgs& a)
+{
+    if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, std::string(word) + ": objective must be 0 (return) or 1 (survival)");
+    return TBX_OK;
+}
+static int shared_width(tbx_engine* e, const char* word, double width)
+{
+    if (!(width >= 1.0 && width <= (double)TBX_BEAM_MAX_WIDTH)) return e->fail(TBX_E_INVALID, std::string(word) + ": width must be 1 .. TBX_BEAM_MAX_WIDTH");
+    return TBX_OK;
+}
+static int shared_samples(tbx_engine* e, const char* word, double count)
+{
+    if (!(count >= 1.0 && count <= (double)TBX_LOOKAHEAD_MAX_SAMPLES)) return e->fail(TBX_E_INVALID, std::string(word) + ": samples must be 1 .. TBX_LOOKAHEAD_MAX_SAMPLES");
+    return TBX_OK;
+}
+// the salt of `samples` futures (the count is checked): sample s draws with salt + s, in 32 bits
+static int shared_salt(tbx_engine* e, const char* word, double salt, long long samples)
+{
+    if (!(salt >= 0.0 && salt < 4294967296.0)) return e->fail(TBX_E_INVALID, std::string(word) + ": salt must be 0 .. 2^32 - 1");
+    if ((uint64_t)salt != 0 && (uint64_t)salt + (uint64_t)samples - 1 >= (1ull << 32)) return e->fail(TBX_E_INVALID, std::string(word) + ": salt + samples - 1 must stay below 2^32");
+    return TBX_OK;
+}
+// The most arguments each lookahead query takes: its own "takes {...}" refusal, tbx_reduce's scan of host rows and TBX_QUERY_LOOKAHEAD_ACT
+// read it here (150 / 151, 152, 153, 154, 155, 156, 157, 158)
+static constexpr int MAX_ARGS_LOOKAHEAD = 8, MAX_ARGS_PLAN = 9, MAX_ARGS_SEARCH = 9, MAX_ARGS_SAMPLES = 9, MAX_ARGS_SEARCH_SAMPLES = 11, MAX_ARGS_BEAM = 10,
+                     MAX_ARGS_BEAM_SAMPLES = 12, MAX_ARGS_EVOLVE = 15;
 
 // chunks > 1: the winner among the partial rows parts[group][chunks][6] of every (env, first action) group of envs from
 // first_env on, by the order of the search kernel; a group without a leaf (a refused row) answers zeros
@@ -1202,34 +1257,32 @@ __global__ __launch_bounds__(256) void tbx_search_pick_kernel(const double* __re
 }
 
 // TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH: shared values are refused here, before anything is launched; per-env rows are met by the
-// kernels.  The search is cut into chunks (tbx_search_chunks) and into launches over env ranges (tbx_search_launches).
+// kernels.  The search is cut into chunks (tbx_search_chunks) and into launches over env ranges (tbx_range_step).
 static int lookahead_plans(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, hipStream_t s)
 {
     const bool search = query == TBX_QUERY_LOOKAHEAD_SEARCH;
     const int L = tbx_legal_count(e->game);
-    if (a.n < 1 || a.n > 9)
+    if (a.n < 1 || a.n > (search ? MAX_ARGS_SEARCH : MAX_ARGS_PLAN))
         return e->fail(TBX_E_INVALID, search ? "search takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset]}" : "plan takes {frames[, hold, depth, code, rest, seed_lo, seed_hi, t, env_offset]}");
     long long plans = TBX_LOOKAHEAD_MAX_PLANS, frames = TBX_LOOKAHEAD_MAX_FRAMES;      // per-env rows: the most a valid row can ask for
     if (!a.per_env) {
-        auto playable = [&](double v) {
-            if (v == -1.0) return true;
-            for (int i = 0; i < L; i++)
-                if (v == (double)tbx_legal_action(e->game, i)) return true;
-            return false;
-        };
-        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
-        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        if (int rc = shared_frames_hold(e, a)) return rc;
         const double depth = a.n > 2 ? a.v[2] : search ? 1.0 : 0.0;
         if (!(depth >= (search ? 1.0 : 0.0) && depth <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "lookahead: depth must be 0 (search: 1) .. TBX_PLAN_MAX_DEPTH(game)");
         const uint64_t count = tbx_plan_count(e->game, TbxEditArgs::to_int(depth));
         if (search && count > (uint64_t)TBX_LOOKAHEAD_MAX_PLANS) return e->fail(TBX_E_INVALID, "search: n_legal^depth must not exceed TBX_LOOKAHEAD_MAX_PLANS");
-        if (search && a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "search: objective must be 0 (return) or 1 (survival)");
+        if (search)
+            if (int rc = shared_objective(e, "search", a)) return rc;
         if (!search && a.n > 3 && !(a.v[3] >= 0.0 && a.v[3] < (double)count)) return e->fail(TBX_E_INVALID, "plan: code must be 0 .. n_legal^depth - 1");
-        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        if (int rc = shared_action(e, a, 4, "rest")) return rc;
         plans = (long long)count;
         frames = TbxEditArgs::to_int(a.v[0]);
     }
-    if (!search) return e->ops->lookahead_plan(e, a, out_dev, s);
+    TbxPlanLaunch l{};
+    l.query = query;
+    l.envs = e->n;
+    l.rows = out_dev;
+    if (!search) return e->ops->lookahead_play(e, a, l, s);
     const int chunks = tbx_search_chunks(e->n, L, plans / L, e->ops->search_lanes());
     double* rows = out_dev;
     if (chunks > 1) {
@@ -1237,10 +1290,14 @@ static int lookahead_plans(tbx_engine* e, int query, const TbxEditArgs& a, doubl
         rows = e->search_parts.p;
     }
     e->search_chunks = chunks;
+    l.chunks = chunks;
+    l.rows = rows;
     int rc = TBX_OK;
-    tbx_search_launches(e->n, (long long)L * chunks, plans * frames, [&](int env0, int envs) {
+    tbx_each_range(e->n, tbx_range_step(e->n, TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH, plans * frames, (long long)L * chunks), [&](int env0, int envs) {
         if (rc) return;
-        rc = e->ops->lookahead_search(e, a, chunks, env0, envs, rows, s);
+        l.first_env = env0;
+        l.envs = envs;
+        rc = e->ops->lookahead_play(e, a, l, s);
         if (rc || chunks == 1) return;
         const int groups = envs * L;
         hipLaunchKernelGGL(tbx_search_pick_kernel, dim3((groups + 255) / 256), dim3(256), 0, s, rows, a, L, chunks, (long long)env0 * L, groups, out_dev);
@@ -1283,10 +1340,6 @@ __global__ __launch_bounds__(64) void tbx_beam_select_kernel(TbxEditArgs a, int 
     }
 }
 
-// One env range of a beam holds candidates plus two beams in engine-owned scratch; the ranges keep it under this, whatever N and
-// width are (a starting value: profiles/beam.md).
-constexpr size_t TBX_BEAM_SCRATCH_BYTES = 256ull << 20;
-
 // TBX_QUERY_LOOKAHEAD_BEAM: shared values are refused here, before anything is launched; per-env rows are met by the kernels.
 // Env ranges keep a launch under TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH leaf-frames and TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units and the
 // scratch under TBX_BEAM_SCRATCH_BYTES (per-env rows: budgeted as the largest valid row, and every level up to
@@ -1295,23 +1348,16 @@ constexpr size_t TBX_BEAM_SCRATCH_BYTES = 256ull << 20;
 static int lookahead_beam(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s)
 {
     const int L = tbx_legal_count(e->game);
-    if (a.n < 1 || a.n > 10) return e->fail(TBX_E_INVALID, "beam takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width]}");
+    if (a.n < 1 || a.n > MAX_ARGS_BEAM) return e->fail(TBX_E_INVALID, "beam takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width]}");
     long long frames = TBX_LOOKAHEAD_MAX_FRAMES;      // per-env rows: the most a valid row can ask for
     int depth = tbx_plan_max_depth(e->game), width = TBX_BEAM_MAX_WIDTH;
     if (!a.per_env) {
-        auto playable = [&](double v) {
-            if (v == -1.0) return true;
-            for (int i = 0; i < L; i++)
-                if (v == (double)tbx_legal_action(e->game, i)) return true;
-            return false;
-        };
-        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
-        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
         const double dp = a.n > 2 ? a.v[2] : 1.0, w = a.n > 9 ? a.v[9] : 1.0;
-        if (!(dp >= 1.0 && dp <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "beam: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
-        if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "beam: objective must be 0 (return) or 1 (survival)");
-        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
-        if (!(w >= 1.0 && w <= (double)TBX_BEAM_MAX_WIDTH)) return e->fail(TBX_E_INVALID, "beam: width must be 1 .. TBX_BEAM_MAX_WIDTH");
+        if (int rc = shared_frames_hold(e, a)) return rc;
+        if (int rc = shared_depth(e, "beam", dp, 1)) return rc;
+        if (int rc = shared_objective(e, "beam", a)) return rc;
+        if (int rc = shared_action(e, a, 4, "rest")) return rc;
+        if (int rc = shared_width(e, "beam", w)) return rc;
         frames = TbxEditArgs::to_int(a.v[0]);
         depth = TbxEditArgs::to_int(dp);
         width = TbxEditArgs::to_int(w);
@@ -1319,28 +1365,30 @@ static int lookahead_beam(tbx_engine* e, const TbxEditArgs& a, double* out_dev, 
     // per env: L groups of at most width * L candidates, and two beams of width codes per group
     const long long units_per_env = (long long)L * width * L;
     const size_t bytes_per_env = (size_t)units_per_env * sizeof(TbxBeamCand) + 2 * (size_t)L * width * sizeof(uint32_t);
-    long long step = TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH / (units_per_env * frames);
-    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
-    if (step > (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env)) step = (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env);
-    if (e->beam_range_envs > 0 && step > e->beam_range_envs) step = e->beam_range_envs;
-    if (step > e->n) step = e->n;
-    if (step < 1) step = 1;
+    const long long step = tbx_range_step(e->n, TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH, units_per_env * frames, units_per_env, bytes_per_env, e->beam_range_envs);
     EHIP(e->beam_scratch.reserve(bytes_per_env * (size_t)step, e->stream, s));
     TbxBeamScratch sc;
     sc.stride = width;
     sc.cands = reinterpret_cast<TbxBeamCand*>(e->beam_scratch.p);
     sc.beam_in = reinterpret_cast<uint32_t*>(e->beam_scratch.p + (size_t)units_per_env * sizeof(TbxBeamCand) * (size_t)step);
     sc.beam_out = sc.beam_in + (size_t)L * width * (size_t)step;
-    int ranges = 0;
-    for (long long env0 = 0; env0 < e->n; env0 += step, ranges++) {
-        const int envs = (int)(e->n - env0 < step ? e->n - env0 : step);
-        for (int level = 1; level <= depth; level++) {
-            int rc = e->ops->lookahead_beam(e, a, level, tbx_beam_kept(L, width, level - 1), (int)env0, envs, sc, s);
-            if (rc) return rc;
-            hipLaunchKernelGGL(tbx_beam_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, level, (int)env0, sc, out_dev);
+    TbxPlanLaunch l{};
+    l.query = TBX_QUERY_LOOKAHEAD_BEAM;
+    int rc = TBX_OK;
+    const int ranges = tbx_each_range(e->n, step, [&](int env0, int envs) {
+        l.first_env = env0;
+        l.envs = envs;
+        for (int level = 1; !rc && level <= depth; level++) {
+            l.level = level;
+            l.slots = tbx_beam_kept(L, width, level - 1);
+            l.beam = sc;
+            rc = e->ops->lookahead_play(e, a, l, s);
+            if (rc) return;
+            hipLaunchKernelGGL(tbx_beam_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, level, env0, sc, out_dev);
             uint32_t* const t = sc.beam_in; sc.beam_in = sc.beam_out; sc.beam_out = t;
         }
-    }
+    });
+    if (rc) return rc;
     e->beam_ranges = ranges;
     EHIP(hipGetLastError());
     return TBX_OK;
@@ -1431,20 +1479,12 @@ static TbxEvolveBounds evolve_scan(const tbx_engine* e, const double* rows, int 
 // the shared row of a TBX_QUERY_LOOKAHEAD_EVOLVE: refused here, before anything is launched, else its budget in `b`
 static int evolve_shared_check(tbx_engine* e, const TbxEditArgs& a, TbxEvolveBounds& b)
 {
-    const int L = tbx_legal_count(e->game);
-    auto playable = [&](double v) {
-        if (v == -1.0) return true;
-        for (int i = 0; i < L; i++)
-            if (v == (double)tbx_legal_action(e->game, i)) return true;
-        return false;
-    };
-    if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
-    if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
     const double dp = a.n > 2 ? a.v[2] : 1.0, pop = a.n > 9 ? a.v[9] : 1.0, gens = a.n > 10 ? a.v[10] : 0.0, elite = a.n > 11 ? a.v[11] : 1.0;
     const double plan_seed = a.n > 12 ? a.v[12] : 0.0, mutation = a.n > 13 ? a.v[13] : 64.0, init = a.n > 14 ? a.v[14] : -1.0;
-    if (!(dp >= 1.0 && dp <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "evolve: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
-    if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "evolve: objective must be 0 (return) or 1 (survival)");
-    if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+    if (int rc = shared_frames_hold(e, a)) return rc;
+    if (int rc = shared_depth(e, "evolve", dp, 1)) return rc;
+    if (int rc = shared_objective(e, "evolve", a)) return rc;
+    if (int rc = shared_action(e, a, 4, "rest")) return rc;
     if (!(pop >= 1.0 && pop <= (double)TBX_EVOLVE_MAX_POPULATION)) return e->fail(TBX_E_INVALID, "evolve: population must be 1 .. TBX_EVOLVE_MAX_POPULATION");
     if (!(gens >= 0.0 && gens <= (double)TBX_EVOLVE_MAX_GENERATIONS)) return e->fail(TBX_E_INVALID, "evolve: generations must be 0 .. TBX_EVOLVE_MAX_GENERATIONS");
     b.frames = TbxEditArgs::to_int(a.v[0]);
@@ -1469,7 +1509,7 @@ static int evolve_shared_check(tbx_engine* e, const TbxEditArgs& a, TbxEvolveBou
 static int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, const TbxEvolveBounds* rows, double* out_dev, hipStream_t s)
 {
     const int L = tbx_legal_count(e->game);
-    if (a.n < 1 || a.n > 15)
+    if (a.n < 1 || a.n > MAX_ARGS_EVOLVE)
         return e->fail(TBX_E_INVALID, "evolve takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, population, generations, elite, plan_seed, mutation, init]}");
     // per-env rows the host has not seen: the most a valid row can ask for
     TbxEvolveBounds b{TBX_LOOKAHEAD_MAX_FRAMES, TBX_EVOLVE_MAX_POPULATION, TBX_EVOLVE_MAX_GENERATIONS, 1};
@@ -1480,29 +1520,31 @@ static int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, const TbxEvolve
     // per env: L groups of `population` individuals -- a record and a code each
     const long long units_per_env = (long long)L * b.population;
     const size_t bytes_per_env = (size_t)units_per_env * (sizeof(TbxBeamCand) + sizeof(uint32_t));
-    long long step = TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH / (units_per_env * b.frames);
-    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
-    if (step > (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env)) step = (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env);
-    if (e->beam_range_envs > 0 && step > e->beam_range_envs) step = e->beam_range_envs;
-    if (step > e->n) step = e->n;
-    if (step < 1) step = 1;
+    const long long step = tbx_range_step(e->n, TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH, units_per_env * b.frames, units_per_env, bytes_per_env, e->beam_range_envs);
     EHIP(e->beam_scratch.reserve(bytes_per_env * (size_t)step, e->stream, s));
     TbxEvolveScratch sc;
     sc.stride = b.population;
     sc.recs = reinterpret_cast<TbxBeamCand*>(e->beam_scratch.p);
     sc.codes = reinterpret_cast<uint32_t*>(e->beam_scratch.p + (size_t)units_per_env * sizeof(TbxBeamCand) * (size_t)step);
-    int ranges = 0;
-    for (long long env0 = 0; env0 < e->n; env0 += step, ranges++) {
-        const int envs = (int)(e->n - env0 < step ? e->n - env0 : step);
-        for (int gen = 0; gen <= b.generations; gen++) {
-            const int first_slot = gen == 0 ? 0 : b.elite;
-            if (first_slot < b.population) {                     // (elite = population: every later generation is carried whole)
-                int rc = e->ops->lookahead_evolve(e, a, gen, first_slot, b.population - first_slot, (int)env0, envs, sc, s);
-                if (rc) return rc;
+    TbxPlanLaunch l{};
+    l.query = TBX_QUERY_LOOKAHEAD_EVOLVE;
+    l.evolve = sc;
+    int rc = TBX_OK;
+    const int ranges = tbx_each_range(e->n, step, [&](int env0, int envs) {
+        l.first_env = env0;
+        l.envs = envs;
+        for (int gen = 0; !rc && gen <= b.generations; gen++) {
+            l.level = gen;
+            l.first_slot = gen == 0 ? 0 : b.elite;
+            l.slots = b.population - l.first_slot;
+            if (l.slots > 0) {                                   // (elite = population: every later generation is carried whole)
+                rc = e->ops->lookahead_play(e, a, l, s);
+                if (rc) return;
             }
-            hipLaunchKernelGGL(tbx_evolve_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, gen, (int)env0, sc, out_dev);
+            hipLaunchKernelGGL(tbx_evolve_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, gen, env0, sc, out_dev);
         }
-    }
+    });
+    if (rc) return rc;
     e->evolve_ranges = ranges;
     EHIP(hipGetLastError());
     return TBX_OK;
@@ -1526,23 +1568,15 @@ __global__ __launch_bounds__(256) void tbx_sample_sum_kernel(const long long* __
 static int lookahead_samples(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s)
 {
     const int L = tbx_legal_count(e->game);
-    if (a.n < 1 || a.n > 9) return e->fail(TBX_E_INVALID, "samples takes {frames[, hold, samples, salt, rest, seed_lo, seed_hi, t, env_offset]}");
+    if (a.n < 1 || a.n > MAX_ARGS_SAMPLES) return e->fail(TBX_E_INVALID, "samples takes {frames[, hold, samples, salt, rest, seed_lo, seed_hi, t, env_offset]}");
     long long samples = TBX_LOOKAHEAD_MAX_SAMPLES, frames = TBX_LOOKAHEAD_MAX_FRAMES;      // per-env rows: the most a valid row can ask for
     if (!a.per_env) {
-        auto playable = [&](double v) {
-            if (v == -1.0) return true;
-            for (int i = 0; i < L; i++)
-                if (v == (double)tbx_legal_action(e->game, i)) return true;
-            return false;
-        };
-        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
-        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        if (int rc = shared_frames_hold(e, a)) return rc;
         const double count = a.n > 2 ? a.v[2] : 1.0, salt = a.n > 3 ? a.v[3] : 0.0;
-        if (!(count >= 1.0 && count <= (double)TBX_LOOKAHEAD_MAX_SAMPLES)) return e->fail(TBX_E_INVALID, "samples: samples must be 1 .. TBX_LOOKAHEAD_MAX_SAMPLES");
+        if (int rc = shared_samples(e, "samples", count)) return rc;
         samples = TbxEditArgs::to_int(count);
-        if (!(salt >= 0.0 && salt < 4294967296.0)) return e->fail(TBX_E_INVALID, "samples: salt must be 0 .. 2^32 - 1");
-        if ((uint64_t)salt != 0 && (uint64_t)salt + (uint64_t)samples - 1 >= (1ull << 32)) return e->fail(TBX_E_INVALID, "samples: salt + samples - 1 must stay below 2^32");
-        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        if (int rc = shared_salt(e, "samples", salt, samples)) return rc;
+        if (int rc = shared_action(e, a, 4, "rest")) return rc;
         frames = TbxEditArgs::to_int(a.v[0]);
     }
     const int chunks = tbx_search_chunks(e->n, L, samples, e->ops->search_lanes());
@@ -1552,10 +1586,16 @@ static int lookahead_samples(tbx_engine* e, const TbxEditArgs& a, double* out_de
         rows = e->sample_parts.p;
     }
     e->sample_chunks = chunks;
+    TbxPlanLaunch l{};
+    l.query = TBX_QUERY_LOOKAHEAD_SAMPLES;
+    l.chunks = chunks;
+    l.rows = rows;
     int rc = TBX_OK;
-    tbx_search_launches(e->n, (long long)L * chunks, samples * frames, [&](int env0, int envs) {
+    tbx_each_range(e->n, tbx_range_step(e->n, TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH, samples * frames, (long long)L * chunks), [&](int env0, int envs) {
         if (rc) return;
-        rc = e->ops->lookahead_sample(e, a, chunks, env0, envs, rows, s);
+        l.first_env = env0;
+        l.envs = envs;
+        rc = e->ops->lookahead_play(e, a, l, s);
         if (rc || chunks == 1) return;
         const int groups = envs * L;
         hipLaunchKernelGGL(tbx_sample_sum_kernel, dim3((groups + 255) / 256), dim3(256), 0, s, reinterpret_cast<const long long*>(rows), chunks, (long long)env0 * L, groups, out_dev);
@@ -1598,29 +1638,21 @@ __global__ __launch_bounds__(256) void tbx_search_samples_pick_kernel(const long
 static int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s)
 {
     const int L = tbx_legal_count(e->game);
-    if (a.n < 1 || a.n > 11) return e->fail(TBX_E_INVALID, "search over samples takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, samples, salt]}");
+    if (a.n < 1 || a.n > MAX_ARGS_SEARCH_SAMPLES) return e->fail(TBX_E_INVALID, "search over samples takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, samples, salt]}");
     long long suffixes = TBX_LOOKAHEAD_MAX_PLANS / L, leaves = TBX_LOOKAHEAD_MAX_LEAVES, frames = TBX_LOOKAHEAD_MAX_FRAMES;      // per-env rows: the most a valid row can ask for
     if (!a.per_env) {
-        auto playable = [&](double v) {
-            if (v == -1.0) return true;
-            for (int i = 0; i < L; i++)
-                if (v == (double)tbx_legal_action(e->game, i)) return true;
-            return false;
-        };
-        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
-        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        if (int rc = shared_frames_hold(e, a)) return rc;
         const double depth = a.n > 2 ? a.v[2] : 1.0;
-        if (!(depth >= 1.0 && depth <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "search over samples: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
+        if (int rc = shared_depth(e, "search over samples", depth, 1)) return rc;
         const uint64_t plans = tbx_plan_count(e->game, TbxEditArgs::to_int(depth));
         if (plans > (uint64_t)TBX_LOOKAHEAD_MAX_PLANS) return e->fail(TBX_E_INVALID, "search over samples: n_legal^depth must not exceed TBX_LOOKAHEAD_MAX_PLANS");
-        if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "search over samples: objective must be 0 (return) or 1 (survival)");
-        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+        if (int rc = shared_objective(e, "search over samples", a)) return rc;
+        if (int rc = shared_action(e, a, 4, "rest")) return rc;
         const double count = a.n > 9 ? a.v[9] : 1.0, salt = a.n > 10 ? a.v[10] : 0.0;
-        if (!(count >= 1.0 && count <= (double)TBX_LOOKAHEAD_MAX_SAMPLES)) return e->fail(TBX_E_INVALID, "search over samples: samples must be 1 .. TBX_LOOKAHEAD_MAX_SAMPLES");
+        if (int rc = shared_samples(e, "search over samples", count)) return rc;
         const long long samples = TbxEditArgs::to_int(count);
         if ((long long)plans * samples > (long long)TBX_LOOKAHEAD_MAX_LEAVES) return e->fail(TBX_E_INVALID, "search over samples: n_legal^depth * samples must not exceed TBX_LOOKAHEAD_MAX_LEAVES");
-        if (!(salt >= 0.0 && salt < 4294967296.0)) return e->fail(TBX_E_INVALID, "search over samples: salt must be 0 .. 2^32 - 1");
-        if ((uint64_t)salt != 0 && (uint64_t)salt + (uint64_t)samples - 1 >= (1ull << 32)) return e->fail(TBX_E_INVALID, "search over samples: salt + samples - 1 must stay below 2^32");
+        if (int rc = shared_salt(e, "search over samples", salt, samples)) return rc;
         suffixes = (long long)plans / L;
         leaves = (long long)plans * samples;
         frames = TbxEditArgs::to_int(a.v[0]);
@@ -1633,10 +1665,16 @@ static int lookahead_search_samples(tbx_engine* e, const TbxEditArgs& a, double*
         rows = e->search_samples_parts.p;
     }
     e->search_samples_chunks = chunks;
+    TbxPlanLaunch l{};
+    l.query = TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES;
+    l.chunks = chunks;
+    l.rows = rows;
     int rc = TBX_OK;
-    e->search_samples_launches = tbx_search_samples_launches(e->n, (long long)L * chunks, leaves * frames, tbx_search_samples_budget(e->game, lanes), [&](int env0, int envs) {
+    e->search_samples_launches = tbx_each_range(e->n, tbx_range_step(e->n, tbx_search_samples_budget(e->game, lanes), leaves * frames, (long long)L * chunks), [&](int env0, int envs) {
         if (rc) return;
-        rc = e->ops->lookahead_search_samples(e, a, chunks, env0, envs, rows, s);
+        l.first_env = env0;
+        l.envs = envs;
+        rc = e->ops->lookahead_play(e, a, l, s);
         if (rc || chunks == 1) return;
         const int groups = envs * L;
         hipLaunchKernelGGL(tbx_search_samples_pick_kernel, dim3((groups + 255) / 256), dim3(256), 0, s, reinterpret_cast<const long long*>(rows), a, L, chunks, (long long)env0 * L, groups, out_dev);
@@ -1734,30 +1772,22 @@ static TbxBeamSamplesBounds beam_samples_scan(const tbx_engine* e, const double*
 static int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, const TbxBeamSamplesBounds* rows, double* out_dev, hipStream_t s)
 {
     const int L = tbx_legal_count(e->game);
-    if (a.n < 1 || a.n > 12) return e->fail(TBX_E_INVALID, "beam over samples takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width, samples, salt]}");
+    if (a.n < 1 || a.n > MAX_ARGS_BEAM_SAMPLES) return e->fail(TBX_E_INVALID, "beam over samples takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, width, samples, salt]}");
     // per-env rows the host has not seen: the most a valid row can ask for
     TbxBeamSamplesBounds b{TBX_LOOKAHEAD_MAX_FRAMES, tbx_plan_max_depth(e->game), TBX_BEAM_MAX_WIDTH, TBX_LOOKAHEAD_MAX_SAMPLES, TBX_LOOKAHEAD_MAX_LEAVES};
     if (!a.per_env) {
-        auto playable = [&](double v) {
-            if (v == -1.0) return true;
-            for (int i = 0; i < L; i++)
-                if (v == (double)tbx_legal_action(e->game, i)) return true;
-            return false;
-        };
-        if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
-        if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
+        if (int rc = shared_frames_hold(e, a)) return rc;
         const double dp = a.n > 2 ? a.v[2] : 1.0, w = a.n > 9 ? a.v[9] : 1.0, count = a.n > 10 ? a.v[10] : 1.0, salt = a.n > 11 ? a.v[11] : 0.0;
-        if (!(dp >= 1.0 && dp <= (double)tbx_plan_max_depth(e->game))) return e->fail(TBX_E_INVALID, "beam over samples: depth must be 1 .. TBX_PLAN_MAX_DEPTH(game)");
-        if (a.n > 3 && !(a.v[3] == 0.0 || a.v[3] == 1.0)) return e->fail(TBX_E_INVALID, "beam over samples: objective must be 0 (return) or 1 (survival)");
-        if (a.n > 4 && !playable(a.v[4])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
-        if (!(w >= 1.0 && w <= (double)TBX_BEAM_MAX_WIDTH)) return e->fail(TBX_E_INVALID, "beam over samples: width must be 1 .. TBX_BEAM_MAX_WIDTH");
-        if (!(count >= 1.0 && count <= (double)TBX_LOOKAHEAD_MAX_SAMPLES)) return e->fail(TBX_E_INVALID, "beam over samples: samples must be 1 .. TBX_LOOKAHEAD_MAX_SAMPLES");
-        if (!(salt >= 0.0 && salt < 4294967296.0)) return e->fail(TBX_E_INVALID, "beam over samples: salt must be 0 .. 2^32 - 1");
+        if (int rc = shared_depth(e, "beam over samples", dp, 1)) return rc;
+        if (int rc = shared_objective(e, "beam over samples", a)) return rc;
+        if (int rc = shared_action(e, a, 4, "rest")) return rc;
+        if (int rc = shared_width(e, "beam over samples", w)) return rc;
+        if (int rc = shared_samples(e, "beam over samples", count)) return rc;
         b.frames = TbxEditArgs::to_int(a.v[0]);
         b.depth = TbxEditArgs::to_int(dp);
         b.width = TbxEditArgs::to_int(w);
         b.samples = TbxEditArgs::to_int(count);
-        if ((uint64_t)salt != 0 && (uint64_t)salt + (uint64_t)b.samples - 1 >= (1ull << 32)) return e->fail(TBX_E_INVALID, "beam over samples: salt + samples - 1 must stay below 2^32");
+        if (int rc = shared_salt(e, "beam over samples", salt, b.samples)) return rc;
         b.leaves = (long long)L * tbx_beam_kept(L, b.width, b.depth - 1) * (b.depth == 1 ? 1 : L) * b.samples;
         if (b.leaves > (long long)TBX_LOOKAHEAD_MAX_LEAVES)
             return e->fail(TBX_E_INVALID, "beam over samples: the candidates of the last level x samples must not exceed TBX_LOOKAHEAD_MAX_LEAVES");
@@ -1767,12 +1797,7 @@ static int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, const Tbx
     const long long units_per_env = (long long)L * b.width * L;
     const size_t beam_bytes_per_env = 2 * (size_t)L * b.width * sizeof(uint32_t), rec_bytes = 9 * sizeof(long long);
     const size_t bytes_per_env = (size_t)units_per_env * rec_bytes + beam_bytes_per_env;
-    long long step = tbx_search_samples_budget(e->game, lanes) / (b.leaves * b.frames);
-    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
-    if (step > (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env)) step = (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env);
-    if (e->beam_range_envs > 0 && step > e->beam_range_envs) step = e->beam_range_envs;
-    if (step > e->n) step = e->n;
-    if (step < 1) step = 1;
+    const long long step = tbx_range_step(e->n, tbx_search_samples_budget(e->game, lanes), b.leaves * b.frames, units_per_env, bytes_per_env, e->beam_range_envs);
     const long long want = TBX_SEARCH_FILL_WAVES * (64 / lanes);
     auto level_units = [&](long long envs, int level) { return envs * L * tbx_beam_kept(L, b.width, level - 1) * (level == 1 ? 1 : L); };
     auto level_chunks = [&](long long envs, int level) {
@@ -1795,18 +1820,25 @@ static int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs& a, const Tbx
     sc.recs = reinterpret_cast<long long*>(e->beam_scratch.p);
     sc.beam_in = reinterpret_cast<uint32_t*>(e->beam_scratch.p + recs_bytes);
     sc.beam_out = sc.beam_in + (size_t)L * b.width * (size_t)step;
-    int ranges = 0, most_chunks = 1;
-    for (long long env0 = 0; env0 < e->n; env0 += step, ranges++) {
-        const int envs = (int)(e->n - env0 < step ? e->n - env0 : step);
-        for (int level = 1; level <= b.depth; level++) {
-            const int slots = tbx_beam_kept(L, b.width, level - 1), chunks = level_chunks(envs, level);
-            if (chunks > most_chunks) most_chunks = chunks;
-            int rc = e->ops->lookahead_beam_samples(e, a, level, slots, chunks, (int)env0, envs, sc, s);
-            if (rc) return rc;
-            hipLaunchKernelGGL(tbx_beam_samples_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, level, slots, chunks, (int)env0, sc, out_dev);
+    TbxPlanLaunch l{};
+    l.query = TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES;
+    int rc = TBX_OK, most_chunks = 1;
+    const int ranges = tbx_each_range(e->n, step, [&](int env0, int envs) {
+        l.first_env = env0;
+        l.envs = envs;
+        for (int level = 1; !rc && level <= b.depth; level++) {
+            l.level = level;
+            l.slots = tbx_beam_kept(L, b.width, level - 1);
+            l.chunks = level_chunks(envs, level);
+            l.beam_samples = sc;
+            if (l.chunks > most_chunks) most_chunks = l.chunks;
+            rc = e->ops->lookahead_play(e, a, l, s);
+            if (rc) return;
+            hipLaunchKernelGGL(tbx_beam_samples_select_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, a, e->game, level, l.slots, l.chunks, env0, sc, out_dev);
             uint32_t* const t = sc.beam_in; sc.beam_in = sc.beam_out; sc.beam_out = t;
         }
-    }
+    });
+    if (rc) return rc;
     e->beam_samples_ranges = ranges;
     e->beam_samples_chunks = most_chunks;
     EHIP(hipGetLastError());
@@ -1902,8 +1934,9 @@ static int lookahead_act(tbx_engine* e, const TbxEditArgs& a, double* out_dev, h
     if (a.per_env) return e->fail(TBX_E_INVALID, "act takes shared arguments only");
     if (a.n < 1) return e->fail(TBX_E_INVALID, "act takes {planner, the planner's arguments}");
     const double pl = a.v[0];
-    const int most = pl == (double)TBX_QUERY_LOOKAHEAD_SEARCH ? 9 : pl == (double)TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES ? 11 : pl == (double)TBX_QUERY_LOOKAHEAD_BEAM ? 10 :
-                     pl == (double)TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES ? 12 : pl == (double)TBX_QUERY_LOOKAHEAD_EVOLVE ? 15 : -1;
+    const int most = pl == (double)TBX_QUERY_LOOKAHEAD_SEARCH ? MAX_ARGS_SEARCH : pl == (double)TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES ? MAX_ARGS_SEARCH_SAMPLES :
+                     pl == (double)TBX_QUERY_LOOKAHEAD_BEAM ? MAX_ARGS_BEAM : pl == (double)TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES ? MAX_ARGS_BEAM_SAMPLES :
+                     pl == (double)TBX_QUERY_LOOKAHEAD_EVOLVE ? MAX_ARGS_EVOLVE : -1;
     if (most < 0) return e->fail(TBX_E_INVALID, "act: planner must be 153, 155, 156, 157 or 158");
     if (a.n - 1 > most) return e->fail(TBX_E_INVALID, "act: more arguments than the planner takes");
     const int planner = (int)pl;
@@ -1945,24 +1978,18 @@ static int lookahead_act(tbx_engine* e, const TbxEditArgs& a, double* out_dev, h
     return TBX_OK;
 }
 
-// the queries every game has (the engine's own), else the game's
-static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s, const TbxBeamSamplesBounds* beam_samples_rows = nullptr,
-                         const TbxEvolveBounds* evolve_rows = nullptr)
+// the queries every game has (the engine's own), else the game's.  rows_host: tbx_reduce has the per-env rows on the host, a.n doubles
+// an env -- queries 157 and 158 then budget for the rows there are, not for the largest row there could be
+static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s, const double* rows_host = nullptr)
 {
     if (query == TBX_QUERY_LOOKAHEAD || query == TBX_QUERY_LOOKAHEAD_ALL) {
         // shared values are refused here, before anything is launched; per-env rows are met by the kernel (that env's row: zeros)
-        if (a.n < 1 || a.n > 8) return e->fail(TBX_E_INVALID, "lookahead takes {frames[, hold, first, rest, seed_lo, seed_hi, t, env_offset]}");
+        if (a.n < 1 || a.n > MAX_ARGS_LOOKAHEAD) return e->fail(TBX_E_INVALID, "lookahead takes {frames[, hold, first, rest, seed_lo, seed_hi, t, env_offset]}");
         if (!a.per_env) {
-            auto playable = [&](double v) {
-                if (v == -1.0) return true;
-                for (int i = 0; i < tbx_legal_count(e->game); i++)
-                    if (v == (double)tbx_legal_action(e->game, i)) return true;
-                return false;
-            };
-            if (!(a.v[0] >= 1.0 && a.v[0] <= (double)TBX_LOOKAHEAD_MAX_FRAMES)) return e->fail(TBX_E_INVALID, "lookahead: frames must be 1 .. TBX_LOOKAHEAD_MAX_FRAMES");
-            if (a.n > 1 && !(a.v[1] >= 1.0)) return e->fail(TBX_E_INVALID, "lookahead: hold must be at least 1");
-            if (a.n > 2 && query == TBX_QUERY_LOOKAHEAD && !playable(a.v[2])) return e->fail(TBX_E_INVALID, "lookahead: first is neither -1 nor a legal action of this game");
-            if (a.n > 3 && !playable(a.v[3])) return e->fail(TBX_E_INVALID, "lookahead: rest is neither -1 nor a legal action of this game");
+            if (int rc = shared_frames_hold(e, a)) return rc;
+            if (query == TBX_QUERY_LOOKAHEAD)                    // (_ALL tries every first action and ignores the column)
+                if (int rc = shared_action(e, a, 2, "first")) return rc;
+            if (int rc = shared_action(e, a, 3, "rest")) return rc;
         }
         return e->ops->lookahead(e, a, query == TBX_QUERY_LOOKAHEAD_ALL, out_dev, s);
     }
@@ -1970,8 +1997,18 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
     if (query == TBX_QUERY_LOOKAHEAD_BEAM) return lookahead_beam(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_SAMPLES) return lookahead_samples(e, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES) return lookahead_search_samples(e, a, out_dev, s);
-    if (query == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES) return lookahead_beam_samples(e, a, beam_samples_rows, out_dev, s);
-    if (query == TBX_QUERY_LOOKAHEAD_EVOLVE) return lookahead_evolve(e, a, evolve_rows, out_dev, s);
+    if (query == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES) {
+        TbxBeamSamplesBounds seen;
+        const bool scanned = rows_host && a.per_env && a.n <= MAX_ARGS_BEAM_SAMPLES;
+        if (scanned) seen = beam_samples_scan(e, rows_host, a.n);
+        return lookahead_beam_samples(e, a, scanned ? &seen : nullptr, out_dev, s);
+    }
+    if (query == TBX_QUERY_LOOKAHEAD_EVOLVE) {
+        TbxEvolveBounds seen;
+        const bool scanned = rows_host && a.per_env && a.n <= MAX_ARGS_EVOLVE;
+        if (scanned) seen = evolve_scan(e, rows_host, a.n);
+        return lookahead_evolve(e, a, scanned ? &seen : nullptr, out_dev, s);
+    }
     if (query == TBX_QUERY_LOOKAHEAD_ACT) return lookahead_act(e, a, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     return checkpoint_valid(e, a, out_dev, s);
@@ -2050,15 +2087,7 @@ int tbx_reduce(tbx_engine* e, int query, const double* args, int n_args, int per
     if (rc) return rc;
     const size_t bytes = sizeof(double) * (size_t)e->n * (size_t)width;
     EHIP(e->reduce_out.reserve(bytes, e->stream));
-    // per-env rows of a beam over samples are on the host here: budget for the rows there are, not for the largest row there could be
-    TbxBeamSamplesBounds rows_seen;
-    const bool scanned = query == TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES && a.per_env && n_args <= 12;
-    if (scanned) rows_seen = beam_samples_scan(e, args, n_args);
-    // ... and so are those of an evolutionary search: only the rounds and the slots the rows need
-    TbxEvolveBounds evolve_seen;
-    const bool evolve_scanned = query == TBX_QUERY_LOOKAHEAD_EVOLVE && a.per_env && n_args <= 15;
-    if (evolve_scanned) evolve_seen = evolve_scan(e, args, n_args);
-    rc = engine_reduce(e, query, a, e->reduce_out.p, width, e->stream, scanned ? &rows_seen : nullptr, evolve_scanned ? &evolve_seen : nullptr);
+    rc = engine_reduce(e, query, a, e->reduce_out.p, width, e->stream, args);      // (the host's rows: queries 157 and 158 scan them)
     if (rc) return rc;
     EHIP(hipMemcpyAsync(out_host, e->reduce_out.p, bytes, hipMemcpyDeviceToHost, e->stream));
     EHIP(hipStreamSynchronize(e->stream));

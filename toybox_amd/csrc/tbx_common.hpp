@@ -847,7 +847,7 @@ __global__ __launch_bounds__(G::BLOCK) void tbx_search_kernel(G g, TbxEditArgs a
 template <class G>
 void tbx_launch_search(const G& g, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s)
 {
-    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_search_launches: below 2^30)
+    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_range_step: below 2^30)
     const long long threads = count * (G::WAVE ? 64 : 1);
     hipLaunchKernelGGL(tbx_search_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, chunks, per_env * first_env, (int)count, rows);
 }
@@ -867,15 +867,30 @@ inline int tbx_search_chunks(int n, int legal, long long suffixes, int lanes)
 // One launch of a search plays at most this many leaf-frames (plans x frames), so that a single kernel on a shared card stays
 // near half a second: profiles/search.md has the rate behind the number.
 constexpr long long TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH = 1ll << 31;
-// f(first_env, envs) per launch: env ranges under the leaf-frame budget and under TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units;
-// leaf_frames_per_env: plans x frames of one env (per-env rows: the largest a valid row can ask for)
-template <class F>
-void tbx_search_launches(int n, long long units_per_env, long long leaf_frames_per_env, F&& f)
+// One env range of a beam holds candidates plus two beams in engine-owned scratch; the ranges keep it under this, whatever N and
+// width are (a starting value: profiles/beam.md).
+constexpr size_t TBX_BEAM_SCRATCH_BYTES = 256ull << 20;
+// How every planner query cuts its n envs into ranges, the one copy of the rule: the envs of a range stay under `budget`
+// leaf-frames (leaf_frames_per_env: leaves x frames of one env; per-env rows: the largest a valid row can ask for) and under
+// TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units, where the range keeps scratch (bytes_per_env > 0) under TBX_BEAM_SCRATCH_BYTES, and where
+// TBX_OPT_BEAM_RANGE_ENVS is set (range_envs > 0) under that; at most n, at least 1.
+inline long long tbx_range_step(int n, long long budget, long long leaf_frames_per_env, long long units_per_env, size_t bytes_per_env = 0, int range_envs = 0)
 {
-    long long step = TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH / leaf_frames_per_env;
+    long long step = budget / leaf_frames_per_env;
     if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
+    if (bytes_per_env > 0 && step > (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env)) step = (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env);
+    if (range_envs > 0 && step > range_envs) step = range_envs;
+    if (step > n) step = n;
     if (step < 1) step = 1;
-    for (long long e0 = 0; e0 < n; e0 += step) f((int)e0, (int)(n - e0 < step ? n - e0 : step));
+    return step;
+}
+// f(first_env, envs) per range of `step` envs, the last one shorter; returns the ranges
+template <class F>
+int tbx_each_range(int n, long long step, F&& f)
+{
+    int ranges = 0;
+    for (long long e0 = 0; e0 < n; e0 += step, ranges++) f((int)e0, (int)(n - e0 < step ? n - e0 : step));
+    return ranges;
 }
 
 // ---- TBX_QUERY_LOOKAHEAD_BEAM (include/toybox_amd.h): level after level, tbx_beam_kernel plays the candidates of a level and
@@ -1168,7 +1183,7 @@ __global__ __launch_bounds__(G::BLOCK) void tbx_sample_kernel(G g, TbxEditArgs a
 template <class G>
 void tbx_launch_sample(const G& g, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s)
 {
-    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_search_launches: below 2^30)
+    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_range_step: below 2^30)
     const long long threads = count * (G::WAVE ? 64 : 1);
     hipLaunchKernelGGL(tbx_sample_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, chunks, per_env * first_env, (int)count, rows);
 }
@@ -1274,7 +1289,7 @@ __global__ __launch_bounds__(G::BLOCK) void tbx_search_samples_kernel(G g, TbxEd
 template <class G>
 void tbx_launch_search_samples(const G& g, const TbxEditArgs& a, int chunks, int first_env, int envs, double* rows, hipStream_t s)
 {
-    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_search_samples_launches: below 2^30)
+    const long long per_env = (long long)tbx_legal_count(G::GAME) * chunks, count = per_env * envs;     // (tbx_range_step: below 2^30)
     const long long threads = count * (G::WAVE ? 64 : 1);
     hipLaunchKernelGGL(tbx_search_samples_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, chunks, per_env * first_env, (int)count, rows);
 }
@@ -1293,18 +1308,6 @@ inline long long tbx_search_samples_budget(int game, int lanes)
     case TBX_GAME_AMIDAR: return 1ll << 27;
     default: return 1ll << 30;
     }
-}
-// f(first_env, envs) per launch: env ranges under `budget` leaf-frames and under TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units; returns
-// the launches.  leaf_frames_per_env: plans x samples x frames of one env (per-env rows: the largest a valid row can ask for)
-template <class F>
-int tbx_search_samples_launches(int n, long long units_per_env, long long leaf_frames_per_env, long long budget, F&& f)
-{
-    long long step = budget / leaf_frames_per_env;
-    if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
-    if (step < 1) step = 1;
-    int launches = 0;
-    for (long long e0 = 0; e0 < n; e0 += step, launches++) f((int)e0, (int)(n - e0 < step ? n - e0 : step));
-    return launches;
 }
 
 // ---- TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES (include/toybox_amd.h): the beam's levels, every candidate valued by the eight sums of its
@@ -1413,6 +1416,37 @@ void tbx_launch_beam_samples(const G& g, const TbxEditArgs& a, int level, int sl
     const long long count = (long long)envs * L * slots * (level == 1 ? 1 : L) * chunks;     // (lookahead_beam_samples, engine.hip: below 2^30)
     const long long threads = count * (G::WAVE ? 64 : 1);
     hipLaunchKernelGGL(tbx_beam_samples_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, level, slots, chunks, first_env, (int)count, sc);
+}
+
+// One play launch of a planner query as the engine hands it to the game (GameOps::lookahead_play): which query, the env range, and
+// of the rest what that query's tbx_launch_* above takes.  TBX_QUERY_LOOKAHEAD_PLAN: every env, first_env = 0, rows = the output.
+struct TbxPlanLaunch {
+    int query;                       // TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH / _SAMPLES / _SEARCH_SAMPLES / _BEAM / _EVOLVE / _BEAM_SAMPLES
+    int first_env, envs, chunks;
+    int level, first_slot, slots;    // level: the beam's level or the generation
+    double* rows;
+    union {                          // the scratch view of the query
+        TbxBeamScratch beam;
+        TbxEvolveScratch evolve;
+        TbxBeamSamplesScratch beam_samples;
+    };
+};
+// the play kernel of l.query with the game's leaf policy g; false: no arm for that query, nothing launched.  A plain switch: every
+// arm is instantiated for every policy handed in.
+template <class G>
+bool tbx_launch_planner(const G& g, const TbxEditArgs& a, const TbxPlanLaunch& l, hipStream_t s)
+{
+    switch (l.query) {
+    case TBX_QUERY_LOOKAHEAD_PLAN: tbx_launch_plan(g, a, l.envs, l.rows, s); break;
+    case TBX_QUERY_LOOKAHEAD_SEARCH: tbx_launch_search(g, a, l.chunks, l.first_env, l.envs, l.rows, s); break;
+    case TBX_QUERY_LOOKAHEAD_SAMPLES: tbx_launch_sample(g, a, l.chunks, l.first_env, l.envs, l.rows, s); break;
+    case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: tbx_launch_search_samples(g, a, l.chunks, l.first_env, l.envs, l.rows, s); break;
+    case TBX_QUERY_LOOKAHEAD_BEAM: tbx_launch_beam(g, a, l.level, l.slots, l.first_env, l.envs, l.beam, s); break;
+    case TBX_QUERY_LOOKAHEAD_EVOLVE: tbx_launch_evolve(g, a, l.level, l.first_slot, l.slots, l.first_env, l.envs, l.evolve, s); break;
+    case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: tbx_launch_beam_samples(g, a, l.level, l.slots, l.chunks, l.first_env, l.envs, l.beam_samples, s); break;
+    default: return false;
+    }
+    return true;
 }
 
 // One per-env array of an engine as the env-copy kernels see it (envcopy.hip: fork, checkpoint save and restore) -- `fields`
@@ -1595,20 +1629,9 @@ struct GameOps {
     // TBX_QUERY_LOOKAHEAD (cands = 1, the first action from the arguments) / _ALL (cands = the game's legal count): one launch over
     // the (env, candidate) pairs, out_dev[env][candidate][5]; the arguments' shared values are already checked (engine.hip)
     virtual int lookahead(tbx_engine* e, const TbxEditArgs&, bool /*all*/, double* /*out_dev*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
-    // TBX_QUERY_LOOKAHEAD_PLAN: tbx_plan_kernel over every env.  TBX_QUERY_LOOKAHEAD_SEARCH: tbx_search_kernel over the units of envs
-    // [first_env, first_env + envs), rows[unit]; search_lanes(): the lanes one unit takes in the form the engine is in (64 or 1)
-    virtual int lookahead_plan(tbx_engine* e, const TbxEditArgs&, double* /*out_dev*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
-    virtual int lookahead_search(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
-    // TBX_QUERY_LOOKAHEAD_SAMPLES: tbx_sample_kernel over the same units
-    virtual int lookahead_sample(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
-    // TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: tbx_search_samples_kernel over the same units
-    virtual int lookahead_search_samples(tbx_engine* e, const TbxEditArgs&, int /*chunks*/, int /*first_env*/, int /*envs*/, double* /*rows*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
-    // TBX_QUERY_LOOKAHEAD_BEAM: tbx_beam_kernel over the candidates of `level` of envs [first_env, first_env + envs)
-    virtual int lookahead_beam(tbx_engine* e, const TbxEditArgs&, int /*level*/, int /*slots*/, int /*first_env*/, int /*envs*/, const struct TbxBeamScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
-    // TBX_QUERY_LOOKAHEAD_EVOLVE: tbx_evolve_kernel over individuals [first_slot, first_slot + slots) of generation `gen` of envs [first_env, first_env + envs)
-    virtual int lookahead_evolve(tbx_engine* e, const TbxEditArgs&, int /*gen*/, int /*first_slot*/, int /*slots*/, int /*first_env*/, int /*envs*/, const struct TbxEvolveScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
-    // TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: tbx_beam_samples_kernel over the candidates of `level`, each cut into `chunks` sample chunks
-    virtual int lookahead_beam_samples(tbx_engine* e, const TbxEditArgs&, int /*level*/, int /*slots*/, int /*chunks*/, int /*first_env*/, int /*envs*/, const struct TbxBeamSamplesScratch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
+    // TBX_QUERY_LOOKAHEAD_PLAN .. _EVOLVE: the play kernel of l.query with the game's leaf policy (tbx_launch_planner) over the units of
+    // envs [l.first_env, l.first_env + l.envs); search_lanes(): the lanes one unit takes in the form the engine is in (64 or 1)
+    virtual int lookahead_play(tbx_engine* e, const TbxEditArgs&, const TbxPlanLaunch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     virtual int search_lanes() const { return 64; }
     // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
     // device-only mirrors and (once tbx_agent_init has made them) MaxAndSkipEnv's two buffer slots -- appended to the plan.  The
