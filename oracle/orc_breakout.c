@@ -143,7 +143,7 @@ void orc_breakout_step(const tbx_breakout_config_t* c, tbx_breakout_state_t* s, 
                 x + r >= pl && x - r <= pr) {
                 int S = c->paddle_discrete_segments;
                 double t = (x - pl) / s->paddle_width;
-                if (t < 0.0) t = 0.0;
+                if (!(t >= 0.0)) t = 0.0;            /* also 0/0 (paddle_width 0, ball on the paddle's edge): segment 0 */
                 if (t > 1.0) t = 1.0;
                 int seg = (int)(t * (double)S);
                 if (seg > S - 1) seg = S - 1;

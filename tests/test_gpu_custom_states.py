@@ -19,8 +19,10 @@ import numpy as np
 import pytest
 
 from fork_replay import effective, sim_rngs, states_bytes
+import rule_inputs
+from rule_inputs import BRK_H, BRK_N_BRICKS, BRK_RADII, BRK_W, SI_N_ENEMIES, _random_colors, gen_breakout, gen_si
 from support import FrameChecker, device_frames, oracle_frames, read_buffer, synthetic_actions
-from test_gpu_parity import _fuzz_si
+from rule_inputs import fuzz_si as _fuzz_si
 from toybox_amd import Engine, ToyboxAmdError, _abi
 
 ACTIVE_OPTIONS = {"records": _abi.OPT_RECORDS_ACTIVE, "pipeline": _abi.OPT_PIPELINE_ACTIVE, "fused overlap": _abi.OPT_FUSED_OVERLAP_ACTIVE,
@@ -35,141 +37,6 @@ def fuzz_seed():
 
 
 # ---------------------------------------------------------------- generators
-
-BRK_N_BRICKS = [0, 1, 63, 64, 65, 108, 127, 128, 129, 192, 255, 256]     # both sides of the 64-brick words of the alive masks
-BRK_W = [-3.0, 0.0, 0.75, 2.0, 12.0, 17.5, 60.0]
-BRK_H = [-1.0, 0.0, 1.0, 4.0, 6.25, 20.0]
-BRK_RADII = [0.0, 0.5, 2.0, 5.5]
-
-
-def _random_colors(color, rows, rng, shape):
-    for ch in "rgb":
-        color[ch][rows] = rng.integers(0, 256, shape)
-    color["a"][rows] = 255
-
-
-def gen_breakout(st, rng, kind=None):
-    """Breakout records (canonical walls) -> written states whose brick table is, by `kind` (default env index % 4): 0 the canonical
-    wall with six bricks moved / resized / recoloured / made indestructible / given other points and depth; 1 a random table; 2 a
-    random table of indestructible bricks (enough lives that no game ends: the score must never move); 3 one destructible brick of
-    40 x 8 at (100, 60) (a level per hit).  Every brick slot of a random table is filled, also those past n_bricks.  Half the envs of
-    every kind get 1-4 launched balls inside the field and a radius from BRK_RADII."""
-    st = st.copy()
-    n = len(st)
-    kind = np.arange(n) % 4 if kind is None else np.asarray(kind)
-    B = st["bricks"]
-    st["lives"] = np.where(kind == 2, rng.integers(8, 12, n), rng.integers(1, 4, n))
-    st["score"] = rng.integers(0, 99000, n)
-
-    r = np.flatnonzero(kind == 0)
-    m = len(r)
-    for edit in range(6):
-        b = rng.integers(0, 108, m)
-        if edit == 0:
-            B["x"][r, b] += rng.choice([-7.5, -1.0, 0.25, 3.0, 30.0], m)
-            B["y"][r, b] += rng.choice([-20.0, -0.5, 2.0, 40.0], m)
-        elif edit == 1:
-            B["w"][r, b] = rng.choice(BRK_W, m)
-            B["h"][r, b] = rng.choice(BRK_H, m)
-        elif edit == 2:
-            _random_colors(B["color"], (r, b), rng, m)
-        elif edit == 3:
-            B["destructible"][r, b] = 0
-        elif edit == 4:
-            B["points"][r, b] = rng.integers(8, 200, m)               # (never a canonical value: the engine must leave canonical mode)
-        else:
-            B["depth"][r, b] = rng.integers(0, 7, m)
-
-    r = np.flatnonzero((kind == 1) | (kind == 2))
-    m = len(r)
-    shape = (m, _abi.BRK_MAX_BRICKS)
-    st["n_bricks"][r] = rng.choice(BRK_N_BRICKS, m)
-    for name, lo, hi in (("x", -20.0, 245.0), ("y", -8.0, 175.0)):
-        v = rng.uniform(lo, hi, shape)
-        B[name][r] = np.where(rng.random(shape) < 0.5, np.floor(v), v)
-    B["w"][r] = rng.choice(BRK_W, shape)
-    B["h"][r] = rng.choice(BRK_H, shape)
-    B["points"][r] = rng.integers(0, 60, shape)
-    B["depth"][r] = rng.integers(0, 7, shape)
-    B["row"][r] = rng.integers(0, 14, shape)
-    B["col"][r] = rng.integers(0, 18, shape)
-    _random_colors(B["color"], r, rng, shape)
-    B["alive"][r] = rng.random(shape) < 0.75
-    B["destructible"][r] = (rng.random(shape) < 0.8) & (kind[r] == 1)[:, None]
-
-    r = np.flatnonzero(kind == 3)
-    m = len(r)
-    st["n_bricks"][r] = 1
-    for name, v in (("x", 100.0), ("y", 60.0), ("w", 40.0), ("h", 8.0), ("points", 5), ("row", 0), ("col", 0), ("alive", 1), ("destructible", 1)):
-        B[name][r, 0] = v
-    B["depth"][r, 0] = rng.integers(0, 7, m)
-    _random_colors(B["color"], (r, np.zeros(m, np.int64)), rng, m)
-
-    r = np.flatnonzero((np.arange(n) // 4) % 2 == 0)                  # half the envs of every kind
-    m = len(r)
-    balls = rng.integers(1, 5, m)
-    live = np.arange(_abi.BRK_MAX_BALLS)[None, :] < balls[:, None]
-    speed, angle = rng.uniform(1.0, 4.0, (m, 4)), rng.uniform(0.0, 2.0 * np.pi, (m, 4))
-    st["n_balls"][r] = balls
-    st["ball_x"][r] = np.where(live, rng.uniform(20.0, 220.0, (m, 4)), 0.0)
-    st["ball_y"][r] = np.where(live, rng.uniform(40.0, 135.0, (m, 4)), 0.0)
-    st["ball_vx"][r] = np.where(live, speed * np.cos(angle), 0.0)
-    st["ball_vy"][r] = np.where(live, speed * np.sin(angle), 0.0)
-    st["is_dead"][r] = 0
-    st["reset"][r] = 0
-    st["ball_radius"][r] = rng.choice(BRK_RADII, m)
-    return st
-
-
-SI_N_ENEMIES = [0, 1, 35, 36, 37, 64]
-
-
-def gen_si(records, rng, kind=None):
-    """SpaceInvaders records (a ctypes array) -> written states: _fuzz_si on every env (which takes every formation off its grid), then
-    by `kind` (default env index % 4): 0 n_enemies from SI_N_ENEMIES with random row / col (0..255), id and points, 1 all eight enemy
-    lasers, some flying LEFT or RIGHT, 2 a ship's laser of another size and speed, 3 0-3 shields.  Everything stays inside what
-    tbx_set_states accepts."""
-    n = len(records)
-    for i in range(n):
-        _fuzz_si(records[i], rng)
-    st = np.frombuffer(records, dtype=np.dtype(_abi.SIState)).copy()
-    kind = np.arange(n) % 4 if kind is None else np.asarray(kind)
-
-    r = np.flatnonzero(kind == 0)
-    shape = (len(r), _abi.SI_MAX_ENEMIES)
-    E = st["enemies"]
-    st["n_enemies"][r] = rng.choice(SI_N_ENEMIES, len(r))
-    E["x"][r] = rng.integers(-20, 330, shape)
-    E["y"][r] = rng.integers(0, 150, shape)
-    E["row"][r] = rng.integers(0, 256, shape)
-    E["col"][r] = rng.integers(0, 256, shape)
-    E["id"][r] = rng.integers(0, 65536, shape)
-    E["points"][r] = rng.integers(0, 200, shape)
-    alive = rng.random(shape) < 0.7
-    E["alive"][r] = alive
-    E["death_counter"][r] = np.where(alive | (rng.random(shape) < 0.7), -1, rng.integers(0, 17, shape))
-
-    def lasers(L, rows, shape, movement, w, h, speed):
-        L["x"][rows] = rng.integers(0, 320, shape)
-        L["y"][rows] = rng.integers(20, 180, shape)
-        L["w"][rows], L["h"][rows], L["speed"][rows] = w, h, speed
-        L["t"][rows] = 0
-        L["movement"][rows] = movement
-        _random_colors(L["color"], rows, rng, shape)
-
-    r = np.flatnonzero(kind == 1)
-    shape = (len(r), _abi.SI_MAX_LASERS)
-    st["n_enemy_lasers"][r] = _abi.SI_MAX_LASERS
-    lasers(st["enemy_lasers"], r, shape, rng.choice([1, 1, 2, 3], shape), rng.integers(1, 5, shape), rng.integers(1, 12, shape), rng.integers(1, 6, shape))
-
-    r = np.flatnonzero(kind == 2)
-    st["has_ship_laser"][r] = 1
-    lasers(st["ship_laser"], r, len(r), 0, rng.choice([1, 3, 6], len(r)), rng.choice([1, 4, 12], len(r)), rng.choice([2, 6, 9], len(r)))
-
-    r = np.flatnonzero(kind == 3)
-    st["n_shields"][r] = rng.integers(0, 4, len(r))
-    return st
-
 
 def generate(game, o, rng, kind=None):
     """the generated states of the whole batch, from the oracle engine's current ones"""
@@ -188,16 +55,7 @@ def one_generated_state(game, o, seed):
 
 # ---------------------------------------------------------------- shared loops (one engine: the checker alone; two: device, checker)
 
-def _engines(game, n, libs, seed=1234, preroll=30, options=()):
-    es = [Engine(game, n, lib=lib) for lib in libs]
-    for e in es:
-        for option, value in options:
-            e.set_option(option, value)
-        e.seed(seed)
-        e.new_game()
-        for t in range(preroll):
-            e.step_synthetic(99, t, auto_reset=True)
-    return es
+_engines = rule_inputs.custom_batch_engines
 
 
 def _close(es):
@@ -339,23 +197,32 @@ def test_custom_batch_parity(game, fuzz_seed, hip_lib, oracle_lib):
     from toybox_amd import hip
     n = 1027
     es = g, o = _engines(game, n, (hip_lib, oracle_lib))
-    _write_all(es, generate(game, o, np.random.default_rng(fuzz_seed)))
-    _assert_stream_order(g, "after the write")
-    _same_states(es, "records read back")                                    # (a)
     H, W = g.height, g.width
-    for ch in (1, 3, 4):                                                     # (b)
-        want = o.render(ch)
-        chk = FrameChecker((H, W, ch))
-        for split in (0, 1, 2, 7, 16):
-            g.set_option(_abi.OPT_RENDER_SPLIT, split)
-            g.render_device(0, ch)
-            g.sync()
-            p, nbytes = g.device_buffer(_abi.BUF_FRAME)
-            assert nbytes >= n * H * W * ch
-            chk.compare(device_frames(p, H * W * ch), lambda lo, hi, out: np.copyto(out, want[lo:hi]), n,
-                        what="%s channels %d split %d" % (game, ch, split))
-    g.set_option(_abi.OPT_RENDER_SPLIT, 0)
-    run_steps(es, game, 300, frames_every=50)                                # (c)
+    chks = {}
+    for ev in rule_inputs.custom_batch(es, n, game, fuzz_seed, steps=300):
+        if ev[0] == "written":
+            _assert_stream_order(g, "after the write")
+            _same_states(es, "records read back")                            # (a)
+        elif ev[0] == "frames":                                              # (b)
+            ch, want = ev[1], ev[2][0]
+            chk = FrameChecker((H, W, ch))
+            for split in (0, 1, 2, 7, 16):
+                g.set_option(_abi.OPT_RENDER_SPLIT, split)
+                g.render_device(0, ch)
+                g.sync()
+                p, nbytes = g.device_buffer(_abi.BUF_FRAME)
+                assert nbytes >= n * H * W * ch
+                chk.compare(device_frames(p, H * W * ch), lambda lo, hi, out: np.copyto(out, want[lo:hi]), n,
+                            what="%s channels %d split %d" % (game, ch, split))
+            g.set_option(_abi.OPT_RENDER_SPLIT, 0)
+        elif ev[0] == "step":                                                # (c)
+            t = ev[1]
+            for x, y, name in zip(ev[2][0], ev[2][-1], ("reward", "done", "lives", "score")):
+                assert np.array_equal(x, y), "%s differs at step %d (envs %s)" % (name, t, np.flatnonzero(x != y)[:8])
+            if t % 50 == 49:
+                ch = (3, 1, 4)[(t // 50) % 3]
+                chk = chks.setdefault(ch, FrameChecker((H, W, ch)))
+                _device_frames_equal(g, o, chk, ch, "%s step %d channels %d" % (game, t, ch))
     _same_states(es, "after 300 steps")
     _assert_stream_order(g, "after 300 steps")
     s = hip.Stream()                                                         # (d)
@@ -576,62 +443,22 @@ def test_flip_under_reset_time_wrappers_is_refused_and_changes_nothing(new_plane
 
 # ---------------------------------------------------------------- 5. directed Amidar states
 
-AMI_DEAD_END_ROW, AMI_CUT_X = 12, 6          # row 12 is track from wall to wall; without tile 6 the junctions at 4 and 9 end in stubs
-AMI_CUT_COLUMN = (6, 3)                      # and the corridor from (6, 0) down to (6, 6) without its tile 3 in two more
-AI_PERIMETER, AI_AMIDAR, AI_TARGET, AI_RANDOM = (_abi.AI_NAMES.index(k) for k in ("EnemyPerimeterAI", "EnemyAmidarMvmt", "EnemyTargetPlayer", "EnemyRandomMvmt"))
-UP, DOWN, LEFT, RIGHT = range(4)
-
-
-def directed_amidar(st):
-    """Amidar records (new games) -> six enemies per env on arms random play does not reach: perimeter walkers started on the bottom
-    row, on the left column and off the perimeter; an Amidar-movement enemy, a player hunter and a random walker each at the end of a
-    dead end (the default board has none: two tiles are taken out of it)."""
-    st = st.copy()
-    n = len(st)
-    i = np.arange(n)
-    st["tiles"][:, AMI_DEAD_END_ROW, AMI_CUT_X] = 0
-    st["tiles"][:, AMI_CUT_COLUMN[1], AMI_CUT_COLUMN[0]] = 0
-    st["n_enemies"] = 6
-    E = st["enemies"]
-    A = E["ai"]
-    for name in A.dtype.names:
-        A[name][:, :6] = 0
-    place = [  # kind, tx, ty
-        (AI_PERIMETER, 9 + i % 5, np.full(n, 30)),                    # bottom row: LEFT
-        (AI_PERIMETER, np.zeros(n, np.int64), 13 + i % 5),            # left column: UP
-        (AI_PERIMETER, 13 + i % 6, np.full(n, 12)),                   # off the perimeter: the first open direction
-        (AI_AMIDAR, np.full(n, 5), np.full(n, 12)),                   # end of the stub right of junction 4: neither way, then back
-        (AI_TARGET, np.full(n, 7), np.full(n, 12)),                   # end of the stub left of junction 9, the player out of sight
-        (AI_RANDOM, np.full(n, 6), np.full(n, 2)),                    # end of the stub below (6, 0)
-    ]
-    for k, (kind, tx, ty) in enumerate(place):
-        E["x"][:, k], E["y"][:, k] = _abi.AMI_TILE_WX * tx, _abi.AMI_TILE_WY * ty
-        E["step_tx"][:, k] = E["step_ty"][:, k] = -1
-        E["n_history"][:, k] = 0
-        E["caught"][:, k] = 0
-        E["speed"][:, k] = np.where(i % 4 == 3, 5, 8)
-        A["kind"][:, k] = kind
-        A["start_tx"][:, k], A["start_ty"][:, k] = tx, ty
-    A["vert"][:, 3] = A["start_vert"][:, 3] = np.where(i % 2 == 0, DOWN, UP)
-    A["horiz"][:, 3] = A["start_horiz"][:, 3] = RIGHT
-    A["dir"][:, 4] = A["start_dir"][:, 4] = LEFT
-    A["vision_distance"][:, 4] = 0
-    A["seen_tx"][:, 4] = A["seen_ty"][:, 4] = -1
-    A["dir"][:, 5] = A["start_dir"][:, 5] = DOWN
-    st["chase_timer"] = np.where(i % 8 == 5, 40, 0)
-    return st
-
-
 def run_directed_amidar(es):
-    """200 frames from the directed states; -> (those states, the checker's states after 6 frames)"""
-    game = "amidar"
-    o = es[-1]
-    start = directed_amidar(o.get_states_np())
-    _write_all(es, start)
-    _same_states(es, "records read back")
+    """rule_inputs.directed_amidar_run on one engine or two; -> (the directed states, the checker's states after 6 frames)"""
     early = []
-    run_steps(es, game, 200, action_seed=4, watch=lambda t, out, e: early.append(e.get_states_np()) if t == 5 else None)
-    _same_states(es, "after 200 frames")
+    for ev in rule_inputs.directed_amidar_run(es, es[0].n_envs):
+        if ev[0] == "written":
+            start = ev[1]
+            _same_states(es, "records read back")
+        elif ev[0] == "step":
+            for x, y, name in zip(ev[2][0], ev[2][-1], ("reward", "done", "lives", "score")):
+                assert np.array_equal(x, y), "%s differs at step %d (envs %s)" % (name, ev[1], np.flatnonzero(x != y)[:8])
+            if ev[1] == 5:
+                early.append(es[-1].get_states_np())
+        elif ev[0] == "states":
+            _same_states(es, "after 200 frames")
+        elif ev[0] == "frames":
+            assert np.array_equal(ev[2][0], ev[2][-1]), ev[1]
     return start, early[0]
 
 
@@ -642,8 +469,6 @@ def test_directed_amidar_enemy_arms(form, hip_lib, oracle_lib):
     es = g, o = _engines("amidar", 64, (hip_lib, oracle_lib), preroll=0, options=[(_abi.OPT_STEP_FORM, form)])
     run_directed_amidar(es)
     chk = FrameChecker((g.height, g.width, 3))
-    for ch in (1, 3, 4):
-        assert np.array_equal(g.render(ch), o.render(ch)), ch
     _device_frames_equal(g, o, chk, 3, "directed amidar form %d" % form)
     _close(es)
 

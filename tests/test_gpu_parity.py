@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import rule_inputs
+from rule_inputs import fuzz_amidar as _fuzz_amidar, fuzz_breakout as _fuzz_breakout, fuzz_si as _fuzz_si
 from support import synthetic_actions
 from toybox_amd import Engine, _abi
 from toybox_amd.games import codec
@@ -32,6 +34,22 @@ def _assert_states_equal(g, o, envs):
             raise AssertionError("env %d differs: %r" % (i, diff))
 
 
+def _check(ev, g, o):
+    """one event of a tests/rule_inputs.py script played over (g, o): the two engines' results are equal"""
+    kind = ev[0]
+    if kind == "step":
+        for x, y, name in zip(ev[2][0], ev[2][1], ("reward", "done", "lives", "score")):
+            assert np.array_equal(x, y), "%s differs at step %d (envs %s)" % (name, ev[1], np.nonzero(x != y)[0][:8])
+    elif kind == "frames":
+        fg, fo = ev[2]
+        assert np.array_equal(fg, fo), (ev[1], np.argwhere(fg != fo)[:3])
+    elif kind == "states":
+        _assert_states_equal(g, o, ev[1])
+    elif kind == "agent":
+        for p, q in zip(*ev[2]):
+            assert np.array_equal(p, q), ev[1]
+
+
 @pytest.mark.parametrize("game", ["breakout", "space_invaders", "amidar"])
 def test_rollout_parity(game, hip_lib, oracle_lib):
     """4096 envs, seeds 1234+i, 1500 random-action frames with auto-reset: outputs equal every step,
@@ -42,13 +60,10 @@ def test_rollout_parity(game, hip_lib, oracle_lib):
     sample = rng.choice(n, 64, replace=False)
     _assert_states_equal(g, o, sample)
     n_done = 0
-    for t in range(steps):
-        a = synthetic_actions(game, n, t)
-        rg = g.step(a, auto_reset=True)
-        ro = o.step(a, auto_reset=True)
-        for x, y, name in zip(rg, ro, ("reward", "done", "lives", "score")):
-            assert np.array_equal(x, y), "%s differs at step %d (envs %s)" % (name, t, np.nonzero(x != y)[0][:8])
-        n_done += int(rg[1].sum())
+    for ev in rule_inputs.rollout([g, o], n, game, steps):
+        _check(ev, g, o)
+        t = ev[1]
+        n_done += int(ev[2][0][1].sum())
         if t % 250 == 249:
             _assert_states_equal(g, o, sample)
     _assert_states_equal(g, o, range(n))
@@ -81,11 +96,9 @@ def test_synthetic_device_path(game, hip_lib, oracle_lib):
     """tbx_step_synthetic (actions generated in-kernel) == host-generated actions with the same rule."""
     n = 1024
     g, o = _pair(game, n, hip_lib, oracle_lib)
-    for t in range(300):
-        g.step_synthetic(1337, t, env_offset=7, auto_reset=True)
-        o.step(synthetic_actions(game, n, t, seed=1337, env_offset=7), auto_reset=True)
-    g.sync()
-    _assert_states_equal(g, o, range(0, n, 3))
+    for ev in rule_inputs.synthetic_path([g, o], n, game):
+        g.sync()
+        _check(ev, g, o)
     # the packed {reward, done, lives} record of the last step
     p, nbytes = g.device_buffer(_abi.BUF_PACKED)
     assert p and nbytes == 8 * n
@@ -106,69 +119,18 @@ def test_breakout_interventions_parity(hip_lib, oracle_lib):
     device engine into its per-env brick-table mode."""
     n = 8
     g, o = _pair("breakout", n, hip_lib, oracle_lib)
-    for e in (g, o):
-        e.step([1] * n)
-    st = o.get_state(2)
-    st.n_balls = 2
-    st.ball_x[1], st.ball_y[1], st.ball_vx[1], st.ball_vy[1] = 60.0, 100.0, 1.5, -1.25
-    for j in range(6):
-        st.bricks[j].alive = 0
-    st.paddle_x = 77.5
-    st.lives = 2
-    for e in (g, o):
-        e.set_state(2, st)
-    _assert_states_equal(g, o, range(n))
-    for t in range(200):
-        a = synthetic_actions("breakout", n, t, seed=3)
-        rg, ro = g.step(a), o.step(a)
-        for x, y in zip(rg, ro):
-            assert np.array_equal(x, y)
-    _assert_states_equal(g, o, range(n))
-    # custom bricks: colour, geometry, points, an indestructible brick
-    st = o.get_state(5)
-    st.bricks[50].color.g = 77
-    st.bricks[3].x, st.bricks[3].w = 30.5, 20.0
-    st.bricks[10].destructible = 0
-    st.bricks[17].points = 50
-    for e in (g, o):
-        e.set_state(5, st)
-    _assert_states_equal(g, o, range(n))
-    for ch in (1, 3, 4):
-        assert np.array_equal(g.render(ch), o.render(ch))
-    for t in range(600):
-        a = synthetic_actions("breakout", n, t, seed=11)
-        rg, ro = g.step(a, auto_reset=True), o.step(a, auto_reset=True)
-        for x, y in zip(rg, ro):
-            assert np.array_equal(x, y)
-        if t % 100 == 0:
-            assert np.array_equal(g.render(3), o.render(3))
-    _assert_states_equal(g, o, range(n))
+    for ev in rule_inputs.breakout_interventions([g, o], n):
+        _check(ev, g, o)
 
 
 def test_breakout_config_change_parity(hip_lib, oracle_lib):
     """write_config_json + new_game (interventions/base.py:401-403): 8 rows, other scores/speeds."""
-    from toybox_amd.games import breakout as brk
-    js = brk.config_to_json(brk.default_config())
-    js["row_scores"] = [9, 7, 7, 4, 4, 1, 1, 1]
-    js["row_colors"] = js["row_colors"] + js["row_colors"][:2]
-    js["start_lives"] = 2
-    js["ball_speed_fast"] = 5.0
-    js["paddle_discrete_segments"] = 7
-    cfg = brk.config_from_json(js)
     n = 64
     g, o = _pair("breakout", n, hip_lib, oracle_lib)
-    for e in (g, o):
-        e.set_config(cfg)
-        e.seed(4321)
-        e.new_game()
-    assert g.get_state(0).n_bricks == 18 * 8
-    for t in range(1200):
-        a = synthetic_actions("breakout", n, t, seed=21)
-        rg, ro = g.step(a, auto_reset=True), o.step(a, auto_reset=True)
-        for x, y in zip(rg, ro):
-            assert np.array_equal(x, y)
-    _assert_states_equal(g, o, range(n))
-    assert np.array_equal(g.render(3), o.render(3))
+    for ev in rule_inputs.breakout_config_change([g, o], n):
+        if ev[0] == "config":
+            assert g.get_state(0).n_bricks == 18 * 8
+        _check(ev, g, o)
 
 
 @pytest.mark.parametrize("game", ["breakout", "space_invaders", "amidar"])
@@ -209,50 +171,10 @@ def test_full_size_properties(game, hip_lib):
 def test_amidar_protocols_parity(hip_lib, oracle_lib):
     """Every enemy movement protocol of interventions/amidar.py:101-112 (incl. EnemyRandomMvmt, which draws from the
     state RNG in enemy order), a 6th enemy, chase / jump modes and painted boxes, stepped on both engines."""
-    import json
-    from toybox_amd.games import amidar as am
     n = 16
     g, o = _pair("amidar", n, hip_lib, oracle_lib)
-    for t in range(50):
-        a = synthetic_actions("amidar", n, t, seed=2)
-        g.step(a), o.step(a)
-    js = am.state_to_json(o.get_state(3))
-    tp = lambda x, y: {"tx": x, "ty": y}
-    js["enemies"][0]["ai"] = {"EnemyPerimeterAI": {"start": tp(0, 0)}}
-    js["enemies"][1]["ai"] = {"EnemyAmidarMvmt": {"vert": "Down", "horiz": "Right", "start_vert": "Down", "start_horiz": "Right", "start": tp(6, 0)}}
-    js["enemies"][2]["ai"] = {"EnemyTargetPlayer": {"start": tp(0, 30), "start_dir": "Right", "vision_distance": 12, "dir": "Right"}}
-    js["enemies"][3]["ai"] = {"EnemyRandomMvmt": {"start": tp(31, 30), "start_dir": "Up", "dir": "Up"}}
-    js["enemies"].append(json.loads(json.dumps(js["enemies"][3])))
-    js["enemies"][5]["ai"] = {"EnemyRandomMvmt": {"start": tp(12, 12), "start_dir": "Left", "dir": "Left"}}
-    js["enemies"][5]["position"] = {"x": 12 * 64, "y": 12 * 80}
-    js["enemies"][5]["step"] = None
-    for env in (3, 4, 5, 6):
-        st = am.state_from_json(js)
-        st.chase_timer = 40 * (env - 3)
-        for e in (g, o):
-            e.set_state(env, st)
-    _assert_states_equal(g, o, range(n))
-    for t in range(2500):
-        a = synthetic_actions("amidar", n, t, seed=9)
-        rg, ro = g.step(a, auto_reset=(t % 2 == 0)), o.step(a, auto_reset=(t % 2 == 0))
-        for x, y in zip(rg, ro):
-            assert np.array_equal(x, y), "step %d" % t
-        if t % 500 == 0:
-            assert np.array_equal(g.render(3), o.render(3))
-            _assert_states_equal(g, o, range(n))
-    _assert_states_equal(g, o, range(n))
-    # a painted board: every box painted, inner fill rendered
-    st = o.get_state(0)
-    for y in range(31):
-        for x in range(32):
-            if st.tiles[y][x]:
-                st.tiles[y][x] = 2
-    for b in range(st.n_boxes):
-        st.boxes[b].painted = 1
-    for e in (g, o):
-        e.set_state(0, st)
-    for ch in (1, 3, 4):
-        assert np.array_equal(g.render(ch), o.render(ch))
+    for ev in rule_inputs.amidar_protocols([g, o], n):
+        _check(ev, g, o)
 
 
 @pytest.mark.parametrize("game", ["breakout", "space_invaders", "amidar"])
@@ -333,52 +255,8 @@ def test_space_invaders_interventions_parity(hip_lib, oracle_lib):
     objects -- frames in every format, the fused observation, and the dynamics from there."""
     n = 24
     g, o = _pair("space_invaders", n, hip_lib, oracle_lib, seed=8)
-    for t in range(140):                                   # past the get-ready phase
-        a = synthetic_actions("space_invaders", n, t, seed=4)
-        g.step(a), o.step(a)
-    rng = np.random.default_rng(5)
-    for i in range(n):
-        st = o.get_state(i)
-        for k in range(0, 36, 3):                          # pile enemies up: same and overlapping columns
-            st.enemies[k].x = st.enemies[(k + 1) % 36].x + int(rng.integers(-14, 15))
-            st.enemies[k].y = st.enemies[(k + 1) % 36].y + int(rng.integers(-6, 7))
-        st.enemies[5].x, st.enemies[5].y = -9, 40          # partly outside the frame
-        st.enemies[7].x = 312
-        st.enemies[9].alive, st.enemies[9].death_counter = 0, 7   # exploding
-        st.n_enemy_lasers = 8
-        for k in range(8):
-            l = st.enemy_lasers[k]
-            l.x, l.y, l.w, l.h, l.t, l.movement, l.speed = 40 + 33 * k + i, 120 + 9 * k, 2, 8, 0, 1, 3
-            l.color.r, l.color.g, l.color.b, l.color.a = 200 - 20 * k, 30 * k, 255, 255
-        st.has_ship_laser = 1
-        st.ship_laser.x, st.ship_laser.y, st.ship_laser.w, st.ship_laser.h, st.ship_laser.movement, st.ship_laser.speed = 150, 100 + i, 2, 8, 0, 6
-        st.ship_laser.color.r, st.ship_laser.color.g, st.ship_laser.color.b, st.ship_laser.color.a = 255, 255, 0, 255
-        for r in range(18):
-            st.shield_rows[1][r] = int(rng.integers(0, 1 << 16))
-        st.shield_x[2], st.shield_y[2] = 150, 150 + i % 5   # overlaps shield 1's columns
-        st.ufo_x, st.ufo_appearance_counter = 100 + 3 * i, 0
-        if i % 3 == 0:
-            st.ship_alive, st.ship_death_counter, st.ship_death_hit_1 = 0, 20, i % 2
-        for e in (g, o):
-            e.set_state(i, st)
-    _assert_states_equal(g, o, range(n))
-    for ch in (1, 3, 4):
-        assert np.array_equal(g.render(ch), o.render(ch)), ch
-    for e in (g, o):
-        e.agent_init(skip=3, out_h=84, out_w=84, stack=2, clip_reward=False)
-    # the agent path reads the current states (no reset): step it and compare observations
-    for t in range(60):
-        a = synthetic_actions("space_invaders", n, t, seed=6)
-        x, y = g.agent_step(a), o.agent_step(a)
-        for p, q in zip(x, y):
-            assert np.array_equal(p, q), t
-    for t in range(200):
-        a = synthetic_actions("space_invaders", n, t, seed=7)
-        rg, ro = g.step(a, auto_reset=True), o.step(a, auto_reset=True)
-        for p, q in zip(rg, ro):
-            assert np.array_equal(p, q), t
-    _assert_states_equal(g, o, range(n))
-    assert np.array_equal(g.render(3), o.render(3))
+    for ev in rule_inputs.si_interventions([g, o], n):
+        _check(ev, g, o)
 
 
 def test_amidar_interventions_parity(hip_lib, oracle_lib):
@@ -387,45 +265,8 @@ def test_amidar_interventions_parity(hip_lib, oracle_lib):
     fused observation (movers differ between the two sub-frames, the board usually does not), and the dynamics from there."""
     n = 24
     g, o = _pair("amidar", n, hip_lib, oracle_lib, seed=8)
-    for t in range(60):
-        a = synthetic_actions("amidar", n, t, seed=4)
-        g.step(a), o.step(a)
-    rng = np.random.default_rng(6)
-    for i in range(n):
-        st = o.get_state(i)
-        for b in range(0, st.n_boxes, 3):
-            st.boxes[b].painted = 1
-        for ty in range(31):
-            for tx in range(32):
-                if st.tiles[ty][tx] == 1 and rng.random() < 0.3:      # Unpainted -> Painted
-                    st.tiles[ty][tx] = 2
-        st.enemies[1].x, st.enemies[1].y = st.enemies[0].x + 16 * (i % 4), st.enemies[0].y     # overlapping movers, off-tile x
-        st.enemies[2].x, st.enemies[2].y = st.player.x, st.player.y                              # under the player
-        st.enemies[3].x, st.enemies[3].y = 31 * 64, 30 * 80                                      # bottom-right corner
-        st.enemies[4].caught = 1
-        st.chase_timer = 40 if i % 2 else 0
-        st.jump_timer = 25 if i % 3 == 0 else 0
-        st.score = 98765 - i
-        st.lives = 1 + i % 3
-        for e in (g, o):
-            e.set_state(i, st)
-    _assert_states_equal(g, o, range(n))
-    for ch in (1, 3, 4):
-        assert np.array_equal(g.render(ch), o.render(ch)), ch
-    for e in (g, o):
-        e.agent_init(skip=4, out_h=84, out_w=84, stack=4, clip_reward=False)
-    for t in range(60):
-        a = synthetic_actions("amidar", n, t, seed=6)
-        x, y = g.agent_step(a), o.agent_step(a)
-        for p, q in zip(x, y):
-            assert np.array_equal(p, q), t
-    for t in range(200):
-        a = synthetic_actions("amidar", n, t, seed=7)
-        rg, ro = g.step(a, auto_reset=True), o.step(a, auto_reset=True)
-        for p, q in zip(rg, ro):
-            assert np.array_equal(p, q), t
-    _assert_states_equal(g, o, range(n))
-    assert np.array_equal(g.render(3), o.render(3))
+    for ev in rule_inputs.amidar_interventions([g, o], n):
+        _check(ev, g, o)
 
 
 def test_level_transitions_parity(hip_lib, oracle_lib):
@@ -435,173 +276,44 @@ def test_level_transitions_parity(hip_lib, oracle_lib):
     n = 8
     # Breakout: one brick left, a ball right under it flying up
     g, o = _pair("breakout", n, hip_lib, oracle_lib, seed=3)
-    for e in (g, o):
-        e.step([1] * n)
-    for i in range(n):
-        st = o.get_state(i)
-        keep = 7 * i + 3
-        for j in range(st.n_bricks):
-            st.bricks[j].alive = 1 if j == keep else 0
-        b = st.bricks[keep]
-        st.n_balls = 1
-        st.ball_x[0], st.ball_y[0], st.ball_vx[0], st.ball_vy[0] = b.x + 6.0, b.y + b.h + 2.5, 0.25, -2.0
-        st.is_dead, st.reset = 0, 0
-        for e in (g, o):
-            e.set_state(i, st)
-    lv0 = o.scalars()[2].copy()
-    for t in range(40):
-        a = synthetic_actions("breakout", n, t, seed=9)
-        for x, y in zip(g.step(a), o.step(a)):
-            assert np.array_equal(x, y), t
-    _assert_states_equal(g, o, range(n))
+    for ev in rule_inputs.breakout_level_transition([g, o], n):
+        if ev[0] == "written":
+            lv0 = o.scalars()[2].copy()
+        _check(ev, g, o)
     assert (o.scalars()[2] == lv0 + 1).all() and np.array_equal(g.render(3), o.render(3))
     assert all(sum(b.alive for b in list(o.get_state(i).bricks)[:108]) >= 95 for i in range(n))     # the wall is back (the ball keeps eating)
 
     # SpaceInvaders: one invader left with the ship's laser right under it
     g, o = _pair("space_invaders", n, hip_lib, oracle_lib, seed=3)
-    for t in range(140):
-        a = synthetic_actions("space_invaders", n, t, seed=4)
-        g.step(a), o.step(a)
-    for i in range(n):
-        st = o.get_state(i)
-        keep = (5 * i + 2) % 36
-        for j in range(36):
-            st.enemies[j].alive, st.enemies[j].death_counter = (1 if j == keep else 0), -1
-        en = st.enemies[keep]
-        st.has_ship_laser = 1
-        st.ship_laser.x, st.ship_laser.y, st.ship_laser.w, st.ship_laser.h = en.x + 7, en.y + 14, 2, 8
-        st.ship_laser.movement, st.ship_laser.speed, st.ship_laser.t = 0, 6, 0
-        st.n_enemy_lasers = 0
-        for e in (g, o):
-            e.set_state(i, st)
-    lv0 = o.scalars()[2].copy()
-    for t in range(60):
-        a = synthetic_actions("space_invaders", n, t, seed=9)
-        for x, y in zip(g.step(a), o.step(a)):
-            assert np.array_equal(x, y), t
-    _assert_states_equal(g, o, range(n))
+    for ev in rule_inputs.si_level_transition([g, o], n):
+        if ev[0] == "written":
+            lv0 = o.scalars()[2].copy()
+        _check(ev, g, o)
     assert (o.scalars()[2] == lv0 + 1).all() and np.array_equal(g.render(3), o.render(3))
     assert all(sum(en.alive for en in list(o.get_state(i).enemies)[:36]) >= 30 for i in range(n))       # a fresh formation
 
     # Amidar: every piece of track painted except the stretch of the right-hand column the player is about to close
     g, o = _pair("amidar", n, hip_lib, oracle_lib, seed=3)
-    for i in range(n):
-        st = o.get_state(i)
-        for ty in range(31):
-            for tx in range(32):
-                if st.tiles[ty][tx] in (1, 3) and not (tx == 31 and ty <= 18):
-                    st.tiles[ty][tx] = 2
-        st.n_enemies = i % 3                              # with and without pursuers
-        for e in (g, o):
-            e.set_state(i, st)
-    lv0 = o.scalars()[2].copy()
-    for t in range(260):
-        a = np.full(n, 2, np.int32)                        # UP along the column, junction after junction
-        for x, y in zip(g.step(a), o.step(a)):
-            assert np.array_equal(x, y), t
-    _assert_states_equal(g, o, range(n))
+    for ev in rule_inputs.amidar_level_transition([g, o], n):
+        if ev[0] == "written":
+            lv0 = o.scalars()[2].copy()
+        _check(ev, g, o)
     assert (o.scalars()[2] > lv0).sum() >= n // 2 and np.array_equal(g.render(3), o.render(3))
 
 
-def _fuzz_breakout(st, rng):
-    st.score = int(rng.integers(0, 250000)); st.lives = int(rng.integers(1, 12)); st.level = int(rng.integers(0, 30))
-    st.paddle_x = float(rng.uniform(-40, 280)); st.paddle_width = float(rng.choice([0.0, 3.0, 24.0, 90.0, 400.0]))
-    st.paddle_speed = float(rng.choice([0.0, 4.0, 17.5]))
-    st.ball_radius = float(rng.choice([0.5, 2.0, 2.0, 5.5]))
-    st.n_balls = int(rng.integers(0, 5))
-    for b in range(st.n_balls):
-        st.ball_x[b], st.ball_y[b] = float(rng.uniform(-30, 270)), float(rng.uniform(-20, 190))
-        st.ball_vx[b], st.ball_vy[b] = float(rng.uniform(-9, 9)), float(rng.uniform(-9, 9))
-    st.is_dead, st.reset = int(st.n_balls == 0 or rng.random() < 0.2), int(rng.random() < 0.3)
-    for j in range(st.n_bricks):
-        st.bricks[j].alive = int(rng.random() < 0.6)
-
-
-def _fuzz_si(st, rng):
-    st.score = int(rng.integers(0, 250000)); st.lives = int(rng.integers(1, 12)); st.level = int(rng.integers(0, 30))
-    st.life_display_timer = int(rng.choice([0, 0, 0, 5])); st.enemy_shot_delay = int(rng.integers(0, 60))
-    st.ship_x = int(rng.integers(-20, 330)); st.ship_alive = int(rng.random() < 0.8)
-    st.ship_death_counter = -1 if st.ship_alive else int(rng.integers(0, 33))
-    st.ufo_x, st.ufo_appearance_counter = int(rng.integers(-40, 340)), int(rng.choice([0, 0, 7, 300]))
-    st.ufo_death_counter = int(rng.choice([-1, -1, 10]))
-    st.move_counter, st.move_dir = int(rng.integers(0, 33)), int(rng.integers(0, 2)) * 1
-    st.visual_orientation = int(rng.integers(0, 2))
-    for j in range(st.n_enemies):
-        en = st.enemies[j]
-        en.x += int(rng.integers(-30, 31)); en.y += int(rng.integers(-40, 90))
-        en.alive = int(rng.random() < 0.7)
-        en.death_counter = -1 if en.alive or rng.random() < 0.7 else int(rng.integers(0, 17))
-    st.n_enemy_lasers = int(rng.integers(0, 9))
-    for k in range(st.n_enemy_lasers):
-        l = st.enemy_lasers[k]
-        l.x, l.y, l.w, l.h = int(rng.integers(-5, 325)), int(rng.integers(-12, 215)), int(rng.integers(1, 5)), int(rng.integers(1, 12))
-        l.t, l.movement, l.speed = 0, 1, int(rng.integers(1, 6))
-        l.color.r, l.color.g, l.color.b, l.color.a = int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 256)), 255
-    st.has_ship_laser = int(rng.random() < 0.5)
-    if st.has_ship_laser:
-        l = st.ship_laser
-        l.x, l.y, l.w, l.h, l.t, l.movement, l.speed = int(rng.integers(0, 320)), int(rng.integers(-5, 200)), 2, 8, 0, 0, 6
-        l.color.r, l.color.g, l.color.b, l.color.a = 255, 200, 0, 255
-    for k in range(st.n_shields):
-        st.shield_x[k] += int(rng.integers(-60, 61)); st.shield_y[k] += int(rng.integers(-30, 31))
-        for r in range(18):
-            if rng.random() < 0.5:
-                st.shield_rows[k][r] = int(rng.integers(0, 1 << 16))
-
-
-def _fuzz_amidar(st, rng):
-    st.score = int(rng.integers(0, 250000)); st.lives = int(rng.integers(1, 12)); st.level = int(rng.integers(0, 30))
-    st.jumps, st.jump_timer, st.chase_timer = int(rng.integers(0, 12)), int(rng.choice([0, 0, 30])), int(rng.choice([0, 0, 50]))
-    track = [(tx, ty) for ty in range(31) for tx in range(32) if st.tiles[ty][tx] != 0]
-    for m in [st.player] + [st.enemies[k] for k in range(st.n_enemies)]:
-        tx, ty = track[int(rng.integers(0, len(track)))]
-        m.x, m.y = 64 * tx, 80 * ty                       # on a track tile, so the movement code has a defined start
-        m.step_tx, m.step_ty = tx, ty
-        m.caught = int(rng.random() < 0.15)
-    st.player.caught = 0
-    for ty in range(31):
-        for tx in range(32):
-            if st.tiles[ty][tx] == 1 and rng.random() < 0.4:
-                st.tiles[ty][tx] = 2
-    for b in range(st.n_boxes):
-        st.boxes[b].painted = int(rng.random() < 0.3)
-
-
-@pytest.mark.parametrize("fuzz_seed", [12345, 777])
-@pytest.mark.parametrize("game,fuzz", [("breakout", _fuzz_breakout), ("space_invaders", _fuzz_si), ("amidar", _fuzz_amidar)])
+@pytest.mark.parametrize("fuzz_seed", rule_inputs.FUZZ_SEEDS)
+@pytest.mark.parametrize("game,fuzz", [pytest.param("breakout", _fuzz_breakout, id="breakout-_fuzz_breakout"),
+                                       pytest.param("space_invaders", _fuzz_si, id="space_invaders-_fuzz_si"),
+                                       pytest.param("amidar", _fuzz_amidar, id="amidar-_fuzz_amidar")])
 def test_fuzzed_states_parity(game, fuzz, fuzz_seed, hip_lib, oracle_lib):
     """Randomised hand-written states -- out-of-frame and overlapping objects, degenerate sizes, odd counters, scores
     beyond the HUD's digits -- written to both libraries: every frame format, then 120 frames of dynamics (auto-reset on)
     and the agent pipeline, all equal to the CPU restatement."""
     n = 96
     g, o = _pair(game, n, hip_lib, oracle_lib, seed=21)
-    for t in range(30):
-        a = synthetic_actions(game, n, t, seed=1)
-        g.step(a), o.step(a)
-    import os
-    rng = np.random.default_rng(int(os.environ.get("TBX_FUZZ_SEED", fuzz_seed)))
-    for i in range(n):
-        st = o.get_state(i)
-        fuzz(st, rng)
-        for e in (g, o):
-            e.set_state(i, st)
-    _assert_states_equal(g, o, range(n))
-    for ch in (1, 3, 4):
-        fg, fo = g.render(ch), o.render(ch)
-        assert np.array_equal(fg, fo), (ch, np.argwhere(fg != fo)[:3])
-    for t in range(120):
-        a = synthetic_actions(game, n, t, seed=2)
-        for x, y, name in zip(g.step(a, auto_reset=True), o.step(a, auto_reset=True), ("reward", "done", "lives", "score")):
-            assert np.array_equal(x, y), (name, t, np.nonzero(x != y)[0][:5])
-        if t % 30 == 7:
-            assert np.array_equal(g.render(3), o.render(3)), t
-    _assert_states_equal(g, o, range(n))
-    for e in (g, o):
-        e.agent_init(skip=4, out_h=84, out_w=84, stack=4, clip_reward=False, episodic_life=True, fire_reset=True, noop_max=4)
-    for t in range(25):
-        a = synthetic_actions(game, n, t, seed=3)
-        for p, q in zip(g.agent_step(a), o.agent_step(a)):
-            assert np.array_equal(p, q), t
+    assert fuzz is rule_inputs.FUZZ[game]
+    for ev in rule_inputs.fuzzed_states([g, o], n, game, fuzz_seed):
+        _check(ev, g, o)
 
 
 def _fuzz_si_on_the_grid(st, rng, extreme):

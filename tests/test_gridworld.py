@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+import rule_inputs
+from rule_inputs import maze_config as _maze_config
 from support import synthetic_actions
 from toybox_amd import Engine, _abi
 from toybox_amd.games import gridworld as gw
@@ -108,19 +110,6 @@ def test_picture(oracle_lib):
         assert (a[..., 3] == 255).all() and np.array_equal(a[..., :3], f)
 
 
-def _maze_config(w, h, seed):
-    rng = np.random.default_rng(seed)
-    names = ["0", "1", "G", "R", "P"]
-    rows = []
-    for y in range(h):
-        rows.append("".join(names[int(rng.choice(5, p=[0.55, 0.2, 0.03, 0.17, 0.05]))] for _ in range(w)))
-    rows[0] = "0" + rows[0][1:]
-    cfg = gw.default_config()
-    cfg["tiles"]["P"] = {"color": {"r": 90, "g": 20, "b": 200, "a": 255}, "goal": False, "reward": -3, "walkable": True}
-    cfg.update(game_size=[w, h], grid=rows, player_start=[0, 0], reward_becomes="0")
-    return cfg
-
-
 def test_toybox_and_env_surface(oracle_lib):
     from toybox_amd import toybox as tbm
     from toybox_amd.envs import GridWorldEnv
@@ -176,34 +165,26 @@ def _same_states(g, o, envs):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("config", [None, (20, 11, 3), (32, 32, 9), (1, 1, 0), (5, 32, 2)])
+@pytest.mark.parametrize("config", rule_inputs.GRIDWORLD_CONFIGS)
 def test_gpu_rollout_and_frames(config, hip_lib, oracle_lib):
     n, steps = 2048, 1200
-    cfg = None if config is None else _maze_config(*config)
-    g, o = _pair(n, hip_lib, oracle_lib, cfg)
-    _same_states(g, o, range(0, n, 97))
+    g, o = rule_inputs.gridworld_engines(n, (hip_lib, oracle_lib), config)
     dones = 0
-    for t in range(steps):
-        a = synthetic_actions("gridworld", n, t)
-        rg, ro = g.step(a, auto_reset=True), o.step(a, auto_reset=True)
-        for x, y, name in zip(rg, ro, ("reward", "done", "lives", "score")):
-            assert np.array_equal(x, y), (name, t)
-        dones += int(rg[1].sum())
-        if t in (0, 5, 300, steps - 1):
-            for ch in (1, 3, 4):
-                fg, fo = g.render(ch), o.render(ch)
-                assert np.array_equal(fg, fo), (t, ch)
-    _same_states(g, o, range(n))
-    for x, y in zip(g.scalars(), o.scalars()):
-        assert np.array_equal(x, y)
-    if config in (None, (20, 11, 3)):
-        assert dones > 0
-    # in-kernel actions
-    for t in range(100):
-        g.step_synthetic(1337, t, env_offset=11, auto_reset=True)
-        o.step(synthetic_actions("gridworld", n, t, seed=1337, env_offset=11), auto_reset=True)
-    g.sync()
-    _same_states(g, o, range(0, n, 5))
+    for ev in rule_inputs.gridworld_rollout([g, o], n, steps):
+        if ev[0] == "states":
+            g.sync()
+            _same_states(g, o, ev[1])
+        elif ev[0] == "step":
+            for x, y, name in zip(ev[2][0], ev[2][1], ("reward", "done", "lives", "score")):
+                assert np.array_equal(x, y), (name, ev[1])
+            dones += int(ev[2][0][1].sum())
+        elif ev[0] == "frames":
+            assert np.array_equal(*ev[2]), ev[1]
+        elif ev[0] == "scalars":
+            for x, y in zip(*ev[1]):
+                assert np.array_equal(x, y)
+            if config in (None, (20, 11, 3)):
+                assert dones > 0
 
 
 @pytest.mark.gpu

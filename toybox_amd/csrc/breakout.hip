@@ -362,7 +362,7 @@ __device__ __forceinline__ void brk_wave_frame(const BrkDev& d, const BrkCfg& c,
             if (vy > 0.0 && y + r >= s.py && y - r <= s.py + TBX_BRK_PADDLE_H && x + r >= pl && x - r <= pr) {
                 const int S = c.segments;
                 double t = (x - pl) / s.pw;
-                if (t < 0.0) t = 0.0;
+                if (!(t >= 0.0)) t = 0.0;     // (also 0/0: segment 0, SPEC.md)
                 if (t > 1.0) t = 1.0;
                 int seg = (int)(t * (double)S);
                 if (seg > S - 1) seg = S - 1;
@@ -722,7 +722,7 @@ __device__ __forceinline__ void brk_t_step(const BrkCfg& c, BrkT& s, uint32_t bu
             if (vy > 0.0 && y + r >= s.py && y - r <= s.py + TBX_BRK_PADDLE_H && x + r >= pl && x - r <= pr) {
                 const int S = c.segments;
                 double t = (x - pl) / s.pw;
-                if (t < 0.0) t = 0.0;
+                if (!(t >= 0.0)) t = 0.0;     // (also 0/0: segment 0, SPEC.md)
                 if (t > 1.0) t = 1.0;
                 int seg = (int)(t * (double)S);
                 if (seg > S - 1) seg = S - 1;
