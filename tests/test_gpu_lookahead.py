@@ -138,6 +138,33 @@ def test_single_form_per_env_rows(game, hip_lib, oracle_lib):
     assert g.reduce_width(_abi.QUERY_LOOKAHEAD) == 5
 
 
+def test_breakout_wave_per_env_step_form(hip_lib, oracle_lib):
+    """TBX_OPT_STEP_FORM = 2: both queries on the canonical wall through the wave form (40 envs: 120 pairs, a partial block)"""
+    n = 40
+    g = Engine("breakout", n, lib=hip_lib)
+    g.set_option(_abi.OPT_STEP_FORM, _abi.STEP_FORM_WAVE_PER_ENV)
+    o = batch(oracle_lib, "breakout", n)
+    g.set_states(0, o.get_states())
+    for i, r in enumerate(sim_rngs(o)):
+        g.set_sim_rng((int(r[0]), int(r[1])), env=i)
+    _held_to_twin(g, o, "breakout, wave per env")
+    states, rngs = g.get_states(), sim_rngs(g)
+    s = SCHEDULES["hold4_noop"]
+    sched, refused = _per_env_schedule("breakout", n)
+    assert refused == [11, 20]
+    want_all = expected(oracle_lib, "breakout", states, rngs, s, all_actions=True)
+    want = expected(oracle_lib, "breakout", states, rngs, sched)
+    for w, frames in ((want_all, H), (want, sched["frames"])):
+        cov = coverage(w, frames)
+        assert cov["scored"] and cov["ended"], cov
+    for k in FIELDS:
+        assert (want[k][refused] == 0).all()
+    assert_fields_equal(g.lookahead_all(s["frames"], hold=s["hold"], rest=s["rest"]), want_all, "breakout, wave per env, all actions")
+    assert_fields_equal(g.lookahead(**sched), want, "breakout, wave per env, single form")
+    _held_to_twin(g, o, "breakout, wave per env, after the queries")
+    g.close(); o.close()
+
+
 # ---------------------------------------------------------------- 3. untouched
 
 @pytest.mark.parametrize("game", GAMES)

@@ -1264,40 +1264,21 @@ __global__ __launch_bounds__(TBX_BLOCK) void ami_step_kernel(AmiDev d, ActionSou
     ami_step_body<false>(d, d, d, src, flags, first_env + rel, lane);
 }
 
-// TBX_QUERY_LOOKAHEAD / _ALL: one wave per (env, candidate); one load, `frames` turns of ami_step on the registers, no store; the
-// exit at game over is wave-uniform.  cands = 1: the single form.
-__global__ __launch_bounds__(TBX_BLOCK) void ami_lookahead_kernel(AmiDev d, TbxEditArgs a, int cands, long long first_pair, int count, double* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63;
-    const int rel = wave_uniform(blockIdx.x * TBX_WAVES_PER_BLOCK + (threadIdx.x >> 6));
-    if (rel >= count) return;
-    const long long pair = first_pair + rel;
-    const int env = wave_uniform((int)(pair / cands)), cand = cands > 1 ? wave_uniform((int)(pair - (long long)env * cands)) : -1;
-    double* const o = out + pair * 5;
-    TbxLookahead<TBX_GAME_AMIDAR> look;
-    if (!wave_uniform(look.read(a, env, cand))) {
-        if (lane == 0) tbx_lookahead_refuse(o);
-        return;
-    }
-    look.uniform();
-    AmiRegs s;
-    ami_load(d, env, lane, s);
-    look.run(lane == 0 ? o : nullptr, [&](uint32_t buttons) { ami_step(*d.tab, lane, (uint32_t)wave_uniform((int)buttons), s); },
-             [&] { return wave_uniform(s.f[A_SCORE]); }, [&] { return wave_uniform(s.f[A_LIVES]); });
-}
-
-// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH / _SAMPLES (tbx_plan_kernel, tbx_search_kernel, tbx_sample_kernel): a wave per unit, the plan as the
-// action source; salt: the game RNG of a sampled future (tbx_salt_rng)
+// The leaf policy of every lookahead query (tbx_lookahead_kernel, tbx_plan_kernel, tbx_search_kernel, tbx_sample_kernel ...): a wave
+// per unit; one load, `frames` turns of ami_step on the registers, no store; the exit at game over is wave-uniform.  salt: the game
+// RNG of a sampled future (tbx_salt_rng)
 struct AmiLook {
     static constexpr int GAME = TBX_GAME_AMIDAR, BLOCK = TBX_BLOCK;
     static constexpr bool WAVE = true;
     AmiDev d;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look, uint64_t salt = 0) const
+    template <bool PLAN>
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, PLAN>& look, uint64_t salt = 0) const
     {
+        const AmiDev dd = d;     // a local copy: read through the policy object, the compiler keeps 14 or more extra VGPRs live
         AmiRegs s;
-        ami_load(d, env, lane, s);
+        ami_load(dd, env, lane, s);
         tbx_salt_rng(s.rng, salt);
-        return look.run_fields([&](uint32_t buttons) { ami_step(*d.tab, lane, (uint32_t)wave_uniform((int)buttons), s); },
+        return look.run_fields([&](uint32_t buttons) { ami_step(*dd.tab, lane, (uint32_t)wave_uniform((int)buttons), s); },
                                [&] { return wave_uniform(s.f[A_SCORE]); }, [&] { return wave_uniform(s.f[A_LIVES]); });
     }
 };
@@ -2280,15 +2261,6 @@ struct AmiOps : GameOps {
         return TBX_OK;
     }
 
-    int lookahead(tbx_engine* e, const TbxEditArgs& a, bool all, double* out_dev, hipStream_t s) override
-    {
-        const int cands = all ? tbx_legal_count(TBX_GAME_AMIDAR) : 1;
-        tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
-            hipLaunchKernelGGL(ami_lookahead_kernel, grid_for(count), dim3(TBX_BLOCK), 0, s, d, a, cands, p0, count, out_dev);
-        });
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
     int lookahead_play(tbx_engine* e, const TbxEditArgs& a, const TbxPlanLaunch& l, hipStream_t s) override
     {
         if (!tbx_launch_planner(AmiLook{d}, a, l, s)) return e->fail(TBX_E_UNSUPPORTED, "lookahead_play: no play kernel for this query");

@@ -934,56 +934,17 @@ __global__ __launch_bounds__(128) void brk_step_tpe_kernel(BrkDev d, const BrkCf
     brk_step_tpe_body<AGENT>(d, *cp, src, flags, recs, recs_a, recs_b, env);   // tables are indexed per thread: read from memory, not from kernel arguments
 }
 
-// TBX_QUERY_LOOKAHEAD / _ALL, canonical wall: one THREAD per (env, candidate), the candidates of an env in neighbouring lanes (their
-// state loads hit the same lines).  One load, `frames` turns of brk_t_step on the registers, no store; lanes whose game has ended
-// leave the loop (masked).  cands = 1: the single form.
-__global__ __launch_bounds__(128) void brk_lookahead_tpe_kernel(BrkDev d, const BrkCfg* __restrict__ cp, TbxEditArgs a, int cands, long long first_pair, int count,
-                                                                double* __restrict__ out)
-{
-    const int rel = blockIdx.x * blockDim.x + threadIdx.x;
-    if (rel >= count) return;
-    const long long pair = first_pair + rel;
-    const int env = (int)(pair / cands), cand = cands > 1 ? (int)(pair - (long long)env * cands) : -1;
-    double* const o = out + pair * 5;
-    TbxLookahead<TBX_GAME_BREAKOUT> look;
-    if (!look.read(a, env, cand)) { tbx_lookahead_refuse(o); return; }
-    const BrkCfg& c = *cp;
-    BrkT s;
-    t_load(d, env, s);
-    look.run(o, [&](uint32_t buttons) { brk_t_step(c, s, buttons); }, [&] { return s.score; }, [&] { return s.lives; });
-}
-
-// ... and the wave form for an engine that has left the canonical wall (and for TBX_OPT_STEP_FORM = 2): one wave per pair
-template <bool CUSTOM>
-__global__ __launch_bounds__(TBX_BLOCK) void brk_lookahead_kernel(BrkDev d, BrkCfg c, TbxEditArgs a, int cands, long long first_pair, int count, double* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63;
-    const int rel = wave_uniform(blockIdx.x * TBX_WAVES_PER_BLOCK + (threadIdx.x >> 6));
-    if (rel >= count) return;
-    const long long pair = first_pair + rel;
-    const int env = wave_uniform((int)(pair / cands)), cand = cands > 1 ? wave_uniform((int)(pair - (long long)env * cands)) : -1;
-    double* const o = out + pair * 5;
-    TbxLookahead<TBX_GAME_BREAKOUT> look;
-    if (!wave_uniform(look.read(a, env, cand))) {
-        if (lane == 0) tbx_lookahead_refuse(o);
-        return;
-    }
-    look.uniform();
-    BrkRegs s;
-    brk_load(d, env, lane, s);
-    look.run(lane == 0 ? o : nullptr, [&](uint32_t buttons) { brk_wave_frame<CUSTOM>(d, c, env, lane, (uint32_t)wave_uniform((int)buttons), s); },
-             [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.lives); });
-}
-
-// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH / _SAMPLES (tbx_plan_kernel, tbx_search_kernel, tbx_sample_kernel): the same two forms with the
-// plan as the action source; salt: the game RNG of a sampled future (tbx_salt_rng).
-// A thread per unit on the canonical wall ...
+// The leaf policies of every lookahead query (tbx_lookahead_kernel, tbx_plan_kernel, tbx_search_kernel, tbx_sample_kernel ...), in the
+// step kernels' two forms: one load, `frames` turns of the step on the registers, no store.  salt: the game RNG of a sampled
+// future (tbx_salt_rng).
+// A thread per unit on the canonical wall: lanes whose game has ended leave the frame loop (masked) ...
 struct BrkTLook {
     static constexpr int GAME = TBX_GAME_BREAKOUT, BLOCK = 128;
     static constexpr bool WAVE = false;
     BrkDev d;
     const BrkCfg* cp;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int, const TbxLookahead<GAME, true>& look, uint64_t salt = 0) const
+    template <bool PLAN>
+    __device__ __forceinline__ TbxLookFields leaf(int env, int, const TbxLookahead<GAME, PLAN>& look, uint64_t salt = 0) const
     {
         const BrkCfg& c = *cp;
         BrkT s;
@@ -992,14 +953,15 @@ struct BrkTLook {
         return look.run_fields([&](uint32_t buttons) { brk_t_step(c, s, buttons); }, [&] { return s.score; }, [&] { return s.lives; });
     }
 };
-// ... and a wave per unit once the wall is custom (and for TBX_OPT_STEP_FORM = 2)
+// ... and a wave per unit once the wall is custom (and for TBX_OPT_STEP_FORM = 2); the exit at game over is wave-uniform
 template <bool CUSTOM>
 struct BrkWaveLook {
     static constexpr int GAME = TBX_GAME_BREAKOUT, BLOCK = TBX_BLOCK;
     static constexpr bool WAVE = true;
     BrkDev d;
     BrkCfg c;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look, uint64_t salt = 0) const
+    template <bool PLAN>
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, PLAN>& look, uint64_t salt = 0) const
     {
         BrkRegs s;
         brk_load(d, env, lane, s);
@@ -2407,17 +2369,6 @@ struct BreakoutOps : GameOps {
         tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_edit_kernel<decltype(cu)::value != 0>, grid, block, 0, s, d, c.n_rows, op, a, mask_dev); });
         TBX_HIP(hipGetLastError());
         recs.valid = false;
-        return TBX_OK;
-    }
-
-    int lookahead(tbx_engine* e, const TbxEditArgs& a, bool all, double* out_dev, hipStream_t s) override
-    {
-        const int cands = all ? tbx_legal_count(TBX_GAME_BREAKOUT) : 1;
-        tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
-            if (!custom && use_tpe) hipLaunchKernelGGL(brk_lookahead_tpe_kernel, dim3((count + 127) / 128), dim3(128), 0, s, d, cfg_dev, a, cands, p0, count, out_dev);
-            else tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_lookahead_kernel<decltype(cu)::value != 0>, grid_for(count), dim3(TBX_BLOCK), 0, s, d, c, a, cands, p0, count, out_dev); });
-        });
-        TBX_HIP(hipGetLastError());
         return TBX_OK;
     }
 

@@ -1991,7 +1991,11 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
                 if (int rc = shared_action(e, a, 2, "first")) return rc;
             if (int rc = shared_action(e, a, 3, "rest")) return rc;
         }
-        return e->ops->lookahead(e, a, query == TBX_QUERY_LOOKAHEAD_ALL, out_dev, s);
+        TbxPlanLaunch l{};
+        l.query = query;
+        l.envs = e->n;
+        l.rows = out_dev;
+        return e->ops->lookahead_play(e, a, l, s);
     }
     if (query == TBX_QUERY_LOOKAHEAD_PLAN || query == TBX_QUERY_LOOKAHEAD_SEARCH) return lookahead_plans(e, query, a, out_dev, s);
     if (query == TBX_QUERY_LOOKAHEAD_BEAM) return lookahead_beam(e, a, out_dev, s);

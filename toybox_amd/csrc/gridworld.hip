@@ -190,47 +190,21 @@ __global__ __launch_bounds__(128) void gw_step_kernel(GwDev d, ActionSource src,
     gw_step_body(d, src, flags, first_env + rel);
 }
 
-// TBX_QUERY_LOOKAHEAD / _ALL: one wave per (env, candidate).  The scalars fit in registers, the 1 KB board a frame may write does
-// not: the wave copies it into its own LDS slice once and steps on that copy (every lane runs the scalar procedure redundantly,
-// as in the reset kernel below) -- HBM is read once and never written.  cands = 1: the single form.
-__global__ __launch_bounds__(TBX_BLOCK) void gw_lookahead_kernel(GwDev d, TbxEditArgs a, int cands, long long first_pair, int count, double* __restrict__ out)
-{
-    __shared__ uint32_t boards[TBX_WAVES_PER_BLOCK][CELLS / 4];
-    const int lane = threadIdx.x & 63;
-    const int rel = wave_uniform(blockIdx.x * TBX_WAVES_PER_BLOCK + (threadIdx.x >> 6));
-    if (rel >= count) return;
-    const long long pair = first_pair + rel;
-    const int env = wave_uniform((int)(pair / cands)), cand = cands > 1 ? wave_uniform((int)(pair - (long long)env * cands)) : -1;
-    double* const o = out + pair * 5;
-    TbxLookahead<TBX_GAME_GRIDWORLD> look;
-    if (!wave_uniform(look.read(a, env, cand))) {
-        if (lane == 0) tbx_lookahead_refuse(o);
-        return;
-    }
-    look.uniform();
-    uint32_t* const mine = boards[wave_uniform((int)(threadIdx.x >> 6))];
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(d.grid + (size_t)env * CELLS);
-    for (int i = lane; i < CELLS / 4; i += 64) mine[i] = src[i];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       // gw_step_on() reads cells other lanes copied
-    const uint32_t* tiles = d.tiles + (size_t)env * GT * 3;
-    GwT s;
-    gw_load(d, env, s);
-    look.run(lane == 0 ? o : nullptr, [&](uint32_t buttons) { gw_step_on(reinterpret_cast<uint8_t*>(mine), tiles, s, buttons); },
-             [&] { return wave_uniform(s.score); }, [&] { return wave_uniform(s.over ? 0 : 1); });
-}
-
-// TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (tbx_plan_kernel, tbx_search_kernel): a wave per unit, the plan as the action source; every
-// leaf copies the board into the wave's LDS slice again
+// The leaf policy of every lookahead query (tbx_lookahead_kernel, tbx_plan_kernel, tbx_search_kernel ...): a wave per unit.  The
+// scalars fit in registers, the 1 KB board a frame may write does not: every leaf copies it into the wave's own LDS slice and
+// steps on that copy (every lane runs the scalar procedure redundantly, as in the reset kernel below) -- HBM is read once a leaf
+// and never written.
 struct GwLook {
     static constexpr int GAME = TBX_GAME_GRIDWORLD, BLOCK = TBX_BLOCK;
     static constexpr bool WAVE = true;
     GwDev d;
-    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, true>& look, uint64_t /*salt: no game RNG*/ = 0) const
+    template <bool PLAN>
+    __device__ __forceinline__ TbxLookFields leaf(int env, int lane, const TbxLookahead<GAME, PLAN>& look, uint64_t /*salt: no game RNG*/ = 0) const
     {
         __shared__ uint32_t boards[TBX_WAVES_PER_BLOCK][CELLS / 4];
         uint32_t* const mine = boards[wave_uniform((int)(threadIdx.x >> 6))];
         const uint32_t* src = reinterpret_cast<const uint32_t*>(d.grid + (size_t)env * CELLS);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       // the previous leaf's reads of the slice come first
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       // the previous leaf's reads of the slice come first (redundant where a wave plays one leaf)
         for (int i = lane; i < CELLS / 4; i += 64) mine[i] = src[i];
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       // gw_step_on() reads cells other lanes copied
         const uint32_t* tiles = d.tiles + (size_t)env * GT * 3;
@@ -781,15 +755,6 @@ struct GridWorldOps : GameOps {
         return TBX_OK;
     }
 
-    int lookahead(tbx_engine* e, const TbxEditArgs& a, bool all, double* out_dev, hipStream_t s) override
-    {
-        const int cands = all ? tbx_legal_count(TBX_GAME_GRIDWORLD) : 1;
-        tbx_lookahead_launches(e->n, cands, [&](long long p0, int count) {
-            hipLaunchKernelGGL(gw_lookahead_kernel, grid_for(count), dim3(TBX_BLOCK), 0, s, d, a, cands, p0, count, out_dev);
-        });
-        TBX_HIP(hipGetLastError());
-        return TBX_OK;
-    }
     int lookahead_play(tbx_engine* e, const TbxEditArgs& a, const TbxPlanLaunch& l, hipStream_t s) override
     {
         if (!tbx_launch_planner(GwLook{d}, a, l, s)) return e->fail(TBX_E_UNSUPPORTED, "lookahead_play: no play kernel for this query");

@@ -588,15 +588,15 @@ struct TbxEditArgs {
 };
 
 // TBX_QUERY_LOOKAHEAD / _ALL (include/toybox_amd.h): the schedule of one (env, candidate) pair and the loop every game's
-// lookahead kernel runs around its own step body.  The state lives in the caller's registers between one load and NO store.
+// leaf policy runs around its own step body.  The state lives in the caller's registers between one load and NO store.
 // The five fields of one played schedule, as TbxLookahead::run_fields leaves them in registers.
 struct TbxLookFields {
     long long ret;
     int score, lives, frames_run, lost_at;
 };
 // PLAN (TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH): the action of period p < depth is digit p of `code` in base n_legal instead of
-// `first`; the branch exists in that instantiation only (depth and code are dead members in the other), so the 150 / 151 kernels
-// compile to what they were (profiles/search.md).
+// `first`; the branch exists in that instantiation only (depth and code are dead members in the other), so tbx_lookahead_kernel
+// pays nothing for it (profiles/lookahead.md).
 template <int GAME, bool PLAN = false>
 struct TbxLookahead {
     int frames, hold, first, rest;
@@ -679,16 +679,9 @@ struct TbxLookahead {
         if (a < 0) a = tbx_legal_action(GAME, (int)(tbx_splitmix64(key ^ (t + (uint64_t)period)) % (uint64_t)tbx_legal_count(GAME)));
         return tbx_ale_buttons(a);
     }
-    // step(buttons) runs one frame; score() / lives() read the state.  `out` != nullptr in the lane that writes the five doubles.
-    // Wave-per-env callers hand in wave-uniform score() / lives(), so the exit at game over is wave-uniform; in thread-per-env
-    // callers it masks the finished lanes.
-    template <class Step, class Score, class Lives>
-    __device__ __forceinline__ void run(double* out, Step&& step, Score&& score, Lives&& lives) const
-    {
-        const TbxLookFields f = run_fields(step, score, lives);
-        if (out) { out[0] = (double)f.ret; out[1] = (double)f.score; out[2] = (double)f.lives; out[3] = (double)f.frames_run; out[4] = (double)f.lost_at; }
-    }
-    // ... the same into registers (the search compares leaf after leaf and stores once)
+    // step(buttons) runs one frame; score() / lives() read the state.  The five fields stay in registers: the caller stores them
+    // (tbx_lookahead_store) or compares leaf after leaf and stores once.  Wave-per-env callers hand in wave-uniform score() /
+    // lives(), so the exit at game over is wave-uniform; in thread-per-env callers it masks the finished lanes.
     template <class Step, class Score, class Lives>
     __device__ __forceinline__ TbxLookFields run_fields(Step&& step, Score&& score, Lives&& lives) const
     {
@@ -719,6 +712,11 @@ __device__ __forceinline__ void tbx_lookahead_refuse(double* out)
 #pragma unroll
     for (int i = 0; i < 5; i++) out[i] = 0.0;
 }
+// a played row: the five doubles of TBX_QUERY_LOOKAHEAD / _ALL / _PLAN
+__device__ __forceinline__ void tbx_lookahead_store(double* out, const TbxLookFields& f)
+{
+    out[0] = (double)f.ret; out[1] = (double)f.score; out[2] = (double)f.lives; out[3] = (double)f.frames_run; out[4] = (double)f.lost_at;
+}
 // the (env, candidate) pairs of one launch: the grids of a query stay below 2^30 pairs each
 constexpr long long TBX_LOOKAHEAD_PAIRS_PER_LAUNCH = 1ll << 30;
 // f(first_pair, count) per launch
@@ -730,9 +728,43 @@ void tbx_lookahead_launches(int n, int cands, F&& f)
         f(p0, (int)(pairs - p0 < TBX_LOOKAHEAD_PAIRS_PER_LAUNCH ? pairs - p0 : TBX_LOOKAHEAD_PAIRS_PER_LAUNCH));
 }
 
-// ---- TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH (include/toybox_amd.h).  A game hands in a policy G next to its lookahead kernel:
+// ---- The play kernels of every lookahead query (include/toybox_amd.h), written once.  A game hands in a leaf policy G:
 //   G::GAME, G::WAVE (a wave per unit, else a thread), G::BLOCK, and
-//   TbxLookFields G::leaf(env, lane, look) const  -- load env from HBM, play `look` on the registers (run_fields), store nothing.
+//   TbxLookFields G::leaf(env, lane, look[, salt]) const  -- load env from HBM, play `look` on the registers (run_fields), store
+//   nothing; `look` is a TbxLookahead<GAME, PLAN> of either action source.
+
+// TBX_QUERY_LOOKAHEAD / _ALL: a unit per (env, candidate) pair, pair = first_pair + rel; cands = 1: the single form, the first
+// action from the arguments.  Thread form: the candidates of an env sit in neighbouring lanes (their state loads hit the same lines).
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_lookahead_kernel(G g, TbxEditArgs a, int cands, long long first_pair, int count, double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int rel = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (rel >= count) return;
+    const long long pair = first_pair + rel;
+    int env = (int)(pair / cands), cand = cands > 1 ? (int)(pair - (long long)env * cands) : -1;
+    if (G::WAVE) { env = wave_uniform(env); cand = wave_uniform(cand); }
+    double* const o = out + pair * 5;
+    TbxLookahead<G::GAME> look;
+    bool ok = look.read(a, env, cand);
+    if (G::WAVE) ok = wave_uniform(ok);
+    if (!ok) {
+        if (!G::WAVE || lane == 0) tbx_lookahead_refuse(o);
+        return;
+    }
+    if (G::WAVE) look.uniform();
+    const TbxLookFields f = g.leaf(env, lane, look);
+    if (!G::WAVE || lane == 0) tbx_lookahead_store(o, f);
+}
+
+template <class G>
+void tbx_launch_lookahead(const G& g, const TbxEditArgs& a, int n, int cands, double* out_dev, hipStream_t s)
+{
+    tbx_lookahead_launches(n, cands, [&](long long p0, int count) {
+        const long long threads = (long long)count * (G::WAVE ? 64 : 1);
+        hipLaunchKernelGGL(tbx_lookahead_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, cands, p0, count, out_dev);
+    });
+}
 
 // "x beats y": a total order once the code breaks the last tie, so the winner does not depend on how the leaves are cut up.
 // objective 0 (return): ret, lives, loss; objective 1 (survival): lives, loss, ret; larger wins, then the smaller code.
@@ -769,7 +801,7 @@ __device__ __forceinline__ void tbx_search_store(double* o, const TbxLookFields&
     o[3] = none ? 0.0 : (double)f.frames_run; o[4] = none ? 0.0 : (double)f.lost_at; o[5] = none ? (partial ? -1.0 : 0.0) : (double)code;
 }
 
-// TBX_QUERY_LOOKAHEAD_PLAN: the cands = 1 form of the lookahead kernels with the plan as the action source, a unit per env
+// TBX_QUERY_LOOKAHEAD_PLAN: the cands = 1 form of tbx_lookahead_kernel with the plan as the action source, a unit per env
 template <class G>
 __global__ __launch_bounds__(G::BLOCK) void tbx_plan_kernel(G g, TbxEditArgs a, int n, double* __restrict__ out)
 {
@@ -789,7 +821,7 @@ __global__ __launch_bounds__(G::BLOCK) void tbx_plan_kernel(G g, TbxEditArgs a, 
     }
     if (G::WAVE) look.uniform_plan();
     const TbxLookFields f = g.leaf(env, lane, look);
-    if (!G::WAVE || lane == 0) { o[0] = (double)f.ret; o[1] = (double)f.score; o[2] = (double)f.lives; o[3] = (double)f.frames_run; o[4] = (double)f.lost_at; }
+    if (!G::WAVE || lane == 0) tbx_lookahead_store(o, f);
 }
 
 template <class G>
@@ -1419,9 +1451,10 @@ void tbx_launch_beam_samples(const G& g, const TbxEditArgs& a, int level, int sl
 }
 
 // One play launch of a planner query as the engine hands it to the game (GameOps::lookahead_play): which query, the env range, and
-// of the rest what that query's tbx_launch_* above takes.  TBX_QUERY_LOOKAHEAD_PLAN: every env, first_env = 0, rows = the output.
+// of the rest what that query's tbx_launch_* above takes.  TBX_QUERY_LOOKAHEAD / _ALL / _PLAN: every env, first_env = 0, rows = the
+// output.
 struct TbxPlanLaunch {
-    int query;                       // TBX_QUERY_LOOKAHEAD_PLAN / _SEARCH / _SAMPLES / _SEARCH_SAMPLES / _BEAM / _EVOLVE / _BEAM_SAMPLES
+    int query;                       // TBX_QUERY_LOOKAHEAD / _ALL / _PLAN / _SEARCH / _SAMPLES / _SEARCH_SAMPLES / _BEAM / _EVOLVE / _BEAM_SAMPLES
     int first_env, envs, chunks;
     int level, first_slot, slots;    // level: the beam's level or the generation
     double* rows;
@@ -1437,6 +1470,8 @@ template <class G>
 bool tbx_launch_planner(const G& g, const TbxEditArgs& a, const TbxPlanLaunch& l, hipStream_t s)
 {
     switch (l.query) {
+    case TBX_QUERY_LOOKAHEAD: tbx_launch_lookahead(g, a, l.envs, 1, l.rows, s); break;
+    case TBX_QUERY_LOOKAHEAD_ALL: tbx_launch_lookahead(g, a, l.envs, tbx_legal_count(G::GAME), l.rows, s); break;
     case TBX_QUERY_LOOKAHEAD_PLAN: tbx_launch_plan(g, a, l.envs, l.rows, s); break;
     case TBX_QUERY_LOOKAHEAD_SEARCH: tbx_launch_search(g, a, l.chunks, l.first_env, l.envs, l.rows, s); break;
     case TBX_QUERY_LOOKAHEAD_SAMPLES: tbx_launch_sample(g, a, l.chunks, l.first_env, l.envs, l.rows, s); break;
@@ -1626,11 +1661,9 @@ struct GameOps {
     // batched interventions (include/toybox_amd.h, tbx_edit / tbx_reduce): one kernel over the selected envs
     virtual int edit(tbx_engine* e, int /*op*/, const TbxEditArgs&, const uint8_t* /*mask_dev*/, hipStream_t) { return e->fail(TBX_E_INVALID, "this game has no such edit"); }
     virtual int reduce(tbx_engine* e, int /*query*/, const TbxEditArgs&, double* /*out_dev*/, int /*width*/, hipStream_t) { return e->fail(TBX_E_INVALID, "this game has no such query"); }
-    // TBX_QUERY_LOOKAHEAD (cands = 1, the first action from the arguments) / _ALL (cands = the game's legal count): one launch over
-    // the (env, candidate) pairs, out_dev[env][candidate][5]; the arguments' shared values are already checked (engine.hip)
-    virtual int lookahead(tbx_engine* e, const TbxEditArgs&, bool /*all*/, double* /*out_dev*/, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
-    // TBX_QUERY_LOOKAHEAD_PLAN .. _EVOLVE: the play kernel of l.query with the game's leaf policy (tbx_launch_planner) over the units of
-    // envs [l.first_env, l.first_env + l.envs); search_lanes(): the lanes one unit takes in the form the engine is in (64 or 1)
+    // TBX_QUERY_LOOKAHEAD .. _EVOLVE: the play kernel of l.query with the game's leaf policy (tbx_launch_planner) over the units of
+    // envs [l.first_env, l.first_env + l.envs); the arguments' shared values are already checked (engine.hip).  search_lanes(): the
+    // lanes one unit takes in the form the engine is in (64 or 1)
     virtual int lookahead_play(tbx_engine* e, const TbxEditArgs&, const TbxPlanLaunch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }
     virtual int search_lanes() const { return 64; }
     // TBX_EDIT_COPY_ENV, TBX_EDIT_CHECKPOINT_*: every per-env array that decides the env's future outputs -- the game state, its
