@@ -876,6 +876,56 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
  *   TBX_E_INVALID, nothing launched, both buffers unchanged: per_env = 1, a planner other than the five, more arguments than
  *   1 + the planner's maximum, whatever the planner refuses in a shared row. */
 #define TBX_QUERY_LOOKAHEAD_ACT 159  /* {planner, the planner's columns} -> 11 */
+/* Tree search: open-loop Monte-Carlo tree search over plan prefixes -- a budget of `simulations` stochastic futures per env and
+ * first action, spent ADAPTIVELY: where queries 154 / 155 / 157 give every candidate the same samples and 156 / 158 fit deep plans
+ * to one future, this one grows a tree of action prefixes and sends each new future down the branch its statistics favour.  The
+ * search is deterministic and defined in integers.  Columns 0 .. 8 stand where TBX_QUERY_LOOKAHEAD_BEAM has them, with the same
+ * defaults for trailing arguments left out and the same ranges (1 <= depth <= TBX_PLAN_MAX_DEPTH(game), no L^depth cap); appended are
+ *     simulations M  default 1    1 .. TBX_TREE_MAX_SIMULATIONS
+ *     explore        default 0    0 .. TBX_TREE_MAX_EXPLORE, an integer in units of the value (below)
+ *     salt           default 0    the ranges of TBX_QUERY_LOOKAHEAD_SAMPLES with `simulations` in the place of `samples`
+ *   Tree: one for every env and every first action index a in legal-set order, with L = n_legal(game).  Its nodes are plan prefixes
+ *   with digit_0 = a (plan codes: TBX_QUERY_LOOKAHEAD_PLAN's); the root, node 0, is the prefix of depth 1.  A node keeps n, the
+ *   completed simulations through it, v_sum, the 64-bit sum of their values, and L child links.  Nodes are numbered in creation order.
+ *   Value of a simulation, from its five fields: objective 0 (return) v = ret; objective 1 (survival)
+ *   v = life lost at < 0 ? frames run : life lost at -- the safe-frames term of TBX_QUERY_LOOKAHEAD_SAMPLES.  Both are
+ *   non-negative integers.
+ *   Selection: for simulation m = 0 .. M-1, in order, start with cur = root, d = 1, code = a.  While d < depth:
+ *     if cur lacks a child: take the smallest missing digit k, create that node, code += k * L^d, d += 1, and stop -- the
+ *       expansion, at most one node per simulation;
+ *     otherwise choose the k that maximises P_k = Q_k + U_k over the children, the smaller k winning a tie, with
+ *       Q_k = (v_sum_k * 256) / n_k (integer division), U_k = explore * isqrt(n_cur << 16) / (1 + n_k), isqrt the exact floor
+ *       square root and n_cur the count of cur before this simulation -- everything in signed 64-bit arithmetic, which the ranges
+ *       above keep below 2^60 -- then code += k * L^d, d += 1, cur = child_k.
+ *   If the loop ends with d == depth nothing is expanded.
+ *   Play: exactly TBX_QUERY_LOOKAHEAD_PLAN {frames, hold, d, code, rest, seed_m, t, env_offset} from the env's state with its game
+ *   RNG salted by salt_m; seed_m = splitmix64((seed + m) mod 2^64) and salt_m = salt == 0 ? 0 : salt + m are the rules of
+ *   TBX_QUERY_LOOKAHEAD_SAMPLES, applied in registers and never stored.  COMMON RANDOM NUMBERS: all L trees of an env meet the same
+ *   future m.
+ *   Backup: every node on the path, the root and a new node included, gets n += 1 and v_sum += v; the root also accumulates the
+ *   eight integer sums of TBX_QUERY_LOOKAHEAD_SAMPLES.
+ *   Out: row out[env][a][0 .. 11].  [0 .. 7] the root's eight sums (samples = M, ret_sum, ret_min, ret_max, lives_sum, lost, ended,
+ *   safe_frames_sum), 64-bit integers converted to binary64 once at the store.  Then the principal variation: from the root, while
+ *   the node has a child, move to the child with the largest n, ties to the larger v_sum, then to the smaller k; [8] the final
+ *   node's code, [9] its depth, [10] its n, [11] its v_sum.
+ *   It follows that
+ *     (i)   with depth 1 columns 0 .. 7 are the row of TBX_QUERY_LOOKAHEAD_SAMPLES {frames, hold, M, salt, rest, seed, t,
+ *           env_offset} and [8 .. 10] = a, 1, M;
+ *     (ii)  with depth >= 2 and M <= L simulation m plays code a + m * L at depth 2 on future m;
+ *     (iii) with depth >= 2 the n of the root's children sum to M, and [9] >= 2;
+ *     (iv)  env ranges (TBX_OPT_TREE_RANGES, capped by TBX_OPT_BEAM_RANGE_ENVS) and cuts of the simulations into several launches
+ *           (TBX_OPT_TREE_LAUNCH_SIMULATIONS) change no output bit;
+ *     (v)   two equal calls with no step between them give equal rows.
+ *   The budget is per first action, not one root over the L actions: the row-per-first-action convention of every other planner
+ *   holds, and callers pick the action with the order of the sampled planners on the root sums.
+ *   The trees live in engine-owned scratch between the launches of one query, on the calling stream.  "Nothing in the engine
+ *   changes" is the lookahead's sentence, verbatim.
+ *   TBX_E_INVALID, nothing launched: a shared value out of the ranges above (frames, hold, depth, objective, rest, simulations,
+ *   explore, salt), more than 12 arguments.  In per-env rows such an env's rows are 12 zeros per action -- field 0 = 0 -- and the
+ *   other envs are answered. */
+#define TBX_TREE_MAX_SIMULATIONS 1024
+#define TBX_TREE_MAX_EXPLORE     1048576
+#define TBX_QUERY_LOOKAHEAD_TREE 160  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, simulations, explore, salt} -> 12 * n_legal(game) */
 /* ids of tbx_device_buffer that exist only once this query has run */
 enum {
     TBX_BUF_PLAN_ACTION = 17,    /* int32[N]  the ALE action every env's winner of the last TBX_QUERY_LOOKAHEAD_ACT plays first */
@@ -1198,6 +1248,11 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
 #define TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS 113
 /* read-only: into how many env ranges the last TBX_QUERY_LOOKAHEAD_EVOLVE was cut (0: none yet; a refused query leaves it standing) */
 #define TBX_OPT_EVOLVE_RANGES 114
+/* read-only: into how many env ranges the last TBX_QUERY_LOOKAHEAD_TREE was cut (0: none yet; a refused query leaves it standing) */
+#define TBX_OPT_TREE_RANGES 115
+/* at most this many simulations per launch of a TBX_QUERY_LOOKAHEAD_TREE (0 .. TBX_TREE_MAX_SIMULATIONS), on top of the engine's
+ * budget; 0 (default): the engine's choice.  It changes no output bit. */
+#define TBX_OPT_TREE_LAUNCH_SIMULATIONS 116
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
 /* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could

@@ -54,6 +54,8 @@ OPT_BEAM_SAMPLES_RANGES = 111      # read-only: env ranges of the last TBX_QUERY
 OPT_BEAM_SAMPLES_CHUNKS = 112      # read-only: the most sample chunks any level of the last TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES used
 OPT_BEAM_SAMPLES_MAX_CHUNKS = 113  # at most this many sample chunks per level of a TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES (0: the engine's choice, 1: never cut)
 OPT_EVOLVE_RANGES = 114            # read-only: env ranges of the last TBX_QUERY_LOOKAHEAD_EVOLVE
+OPT_TREE_RANGES = 115              # read-only: env ranges of the last TBX_QUERY_LOOKAHEAD_TREE
+OPT_TREE_LAUNCH_SIMULATIONS = 116  # at most this many simulations per launch of a TBX_QUERY_LOOKAHEAD_TREE (0: the engine's choice)
 PIPELINE_OFF, PIPELINE_AUTO, PIPELINE_STEP_BESIDE_RENDER, PIPELINE_OVERLAP_RENDERS = 0, 1, 2, 3
 STEP_FORM_AUTO, STEP_FORM_THREAD_PER_ENV, STEP_FORM_WAVE_PER_ENV = 0, 1, 2
 
@@ -123,6 +125,9 @@ EVOLVE_MAX_POPULATION = 256
 EVOLVE_MAX_GENERATIONS = 64
 QUERY_LOOKAHEAD_EVOLVE = 158
 QUERY_LOOKAHEAD_ACT = 159
+TREE_MAX_SIMULATIONS = 1024
+TREE_MAX_EXPLORE = 1048576
+QUERY_LOOKAHEAD_TREE = 160
 # the legal sets in the engine's order (tbx_legal_actions) and TBX_PLAN_MAX_DEPTH: the largest depth with n_legal ** depth <= 2 ** 32
 LEGAL_ACTIONS = {"breakout": (0, 1, 3, 4), "space_invaders": (0, 1, 3, 4, 11, 12), "amidar": (0, 1, 2, 3, 4, 5), "gridworld": (0, 2, 3, 4, 5)}
 PLAN_MAX_DEPTH = {"breakout": 16, "space_invaders": 12, "amidar": 12, "gridworld": 13}

@@ -1154,6 +1154,7 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_LOOKAHEAD_ACT: return every_game ? 11 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SAMPLES: return every_game ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: return every_game ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_TREE: return every_game ? 12 * tbx_legal_count(game) : TBX_E_INVALID;
     default: return TBX_E_INVALID;
     }
 }
@@ -1229,9 +1230,9 @@ static int shared_salt(tbx_engine* e, const char* word, double salt, long long s
     return TBX_OK;
 }
 // The most arguments each lookahead query takes: its own "takes {...}" refusal, tbx_reduce's scan of host rows and TBX_QUERY_LOOKAHEAD_ACT
-// read it here (150 / 151, 152, 153, 154, 155, 156, 157, 158)
+// read it here (150 / 151, 152, 153, 154, 155, 156, 157, 158, 160)
 static constexpr int MAX_ARGS_LOOKAHEAD = 8, MAX_ARGS_PLAN = 9, MAX_ARGS_SEARCH = 9, MAX_ARGS_SAMPLES = 9, MAX_ARGS_SEARCH_SAMPLES = 11, MAX_ARGS_BEAM = 10,
-                     MAX_ARGS_BEAM_SAMPLES = 12, MAX_ARGS_EVOLVE = 15;
+                     MAX_ARGS_BEAM_SAMPLES = 12, MAX_ARGS_EVOLVE = 15, MAX_ARGS_TREE = 12;
 
 // chunks > 1: the winner among the partial rows parts[group][chunks][6] of every (env, first action) group of envs from
 // first_env on, by the order of the search kernel; a group without a leaf (a refused row) answers zeros
@@ -1546,6 +1547,82 @@ static int lookahead_evolve(tbx_engine* e, const TbxEditArgs& a, const TbxEvolve
     });
     if (rc) return rc;
     e->evolve_ranges = ranges;
+    EHIP(hipGetLastError());
+    return TBX_OK;
+}
+
+// What a TBX_QUERY_LOOKAHEAD_TREE is budgeted for: the largest frames and simulations of a valid row
+struct TbxTreeBounds {
+    long long frames;
+    int simulations;
+};
+// tbx_reduce has per-env rows on the host: the bounds of the rows that tbx_tree_values accepts (none: the smallest query)
+static TbxTreeBounds tree_scan(const tbx_engine* e, const double* rows, int n)
+{
+    TbxTreeBounds b{1, 1};
+    for (int env = 0; env < e->n; env++) {
+        const double* const r = rows + (size_t)env * n;
+        auto geti = [&](int i, int otherwise) { return i < n ? TbxEditArgs::to_int(r[i]) : otherwise; };
+        const int frames = geti(0, 0), simulations = geti(9, 1);
+        if (!tbx_tree_values(e->game, frames, geti(1, 1), geti(2, 1), geti(3, 0), geti(4, -1), simulations, geti(10, 0), n > 11 ? r[11] : 0.0)) continue;
+        if (frames > b.frames) b.frames = frames;
+        if (simulations > b.simulations) b.simulations = simulations;
+    }
+    return b;
+}
+
+// TBX_QUERY_LOOKAHEAD_TREE: shared values are refused here, before anything is launched; per-env rows are met by the kernel.  Env
+// ranges come from the beam's three budgets -- a launch of ONE simulation per unit under TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH
+// leaf-frames and TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units, the scratch under TBX_BEAM_SCRATCH_BYTES -- and TBX_OPT_BEAM_RANGE_ENVS
+// cuts them as it cuts the beam's.  Per env the scratch is L trees of simulations + 1 nodes (TbxTreeScratch); beam_scratch is shared
+// with the beam queries and the evolution: all run in stream order, and the launch of simulation 0 makes its trees empty.  Within a
+// range the simulations are cut into launches that stay under the leaf-frame budget (and under TBX_OPT_TREE_LAUNCH_SIMULATIONS);
+// the trees persist in scratch between them.  Per-env rows are budgeted by `rows` where the host form has scanned them, else as
+// the largest valid row -- the device form cannot see the rows; an env stores its row in the launch of its own last simulation and
+// idles afterwards.  All on `s`, in stream order, no host synchronisation.
+static int lookahead_tree(tbx_engine* e, const TbxEditArgs& a, const TbxTreeBounds* rows, double* out_dev, hipStream_t s)
+{
+    const int L = tbx_legal_count(e->game);
+    if (a.n < 1 || a.n > MAX_ARGS_TREE)
+        return e->fail(TBX_E_INVALID, "tree takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, simulations, explore, salt]}");
+    TbxTreeBounds b{TBX_LOOKAHEAD_MAX_FRAMES, TBX_TREE_MAX_SIMULATIONS};      // per-env rows the host has not seen: the most a valid row can ask for
+    if (!a.per_env) {
+        const double dp = a.n > 2 ? a.v[2] : 1.0, sims = a.n > 9 ? a.v[9] : 1.0, explore = a.n > 10 ? a.v[10] : 0.0, salt = a.n > 11 ? a.v[11] : 0.0;
+        if (int rc = shared_frames_hold(e, a)) return rc;
+        if (int rc = shared_depth(e, "tree", dp, 1)) return rc;
+        if (int rc = shared_objective(e, "tree", a)) return rc;
+        if (int rc = shared_action(e, a, 4, "rest")) return rc;
+        if (!(sims >= 1.0 && sims <= (double)TBX_TREE_MAX_SIMULATIONS)) return e->fail(TBX_E_INVALID, "tree: simulations must be 1 .. TBX_TREE_MAX_SIMULATIONS");
+        if (!(explore >= 0.0 && explore <= (double)TBX_TREE_MAX_EXPLORE)) return e->fail(TBX_E_INVALID, "tree: explore must be 0 .. TBX_TREE_MAX_EXPLORE");
+        b.frames = TbxEditArgs::to_int(a.v[0]);
+        b.simulations = TbxEditArgs::to_int(sims);
+        if (int rc = shared_salt(e, "tree", salt, b.simulations)) return rc;
+    } else if (rows) b = *rows;
+    const int stride = TbxTreeScratch::stride_for(b.simulations);
+    const size_t bytes_per_env = (size_t)L * TbxTreeScratch::unit_bytes(stride);
+    const long long step = tbx_range_step(e->n, TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH, (long long)L * b.frames, L, bytes_per_env, e->beam_range_envs);
+    EHIP(e->beam_scratch.reserve(bytes_per_env * (size_t)step, e->stream, s));
+    TbxPlanLaunch l{};
+    l.query = TBX_QUERY_LOOKAHEAD_TREE;
+    l.rows = out_dev;
+    l.tree.base = e->beam_scratch.p;
+    l.tree.stride = stride;
+    int rc = TBX_OK;
+    const int ranges = tbx_each_range(e->n, step, [&](int env0, int envs) {
+        l.first_env = env0;
+        l.envs = envs;
+        long long per_launch = TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH / ((long long)envs * L * b.frames);
+        if (e->tree_launch_simulations > 0 && per_launch > e->tree_launch_simulations) per_launch = e->tree_launch_simulations;
+        if (per_launch > b.simulations) per_launch = b.simulations;
+        if (per_launch < 1) per_launch = 1;
+        for (int m0 = 0; !rc && m0 < b.simulations; m0 += (int)per_launch) {
+            l.first_slot = m0;
+            l.slots = (int)(b.simulations - m0 < per_launch ? b.simulations - m0 : per_launch);
+            rc = e->ops->lookahead_play(e, a, l, s);
+        }
+    });
+    if (rc) return rc;
+    e->tree_ranges = ranges;
     EHIP(hipGetLastError());
     return TBX_OK;
 }
@@ -1979,7 +2056,7 @@ static int lookahead_act(tbx_engine* e, const TbxEditArgs& a, double* out_dev, h
 }
 
 // the queries every game has (the engine's own), else the game's.  rows_host: tbx_reduce has the per-env rows on the host, a.n doubles
-// an env -- queries 157 and 158 then budget for the rows there are, not for the largest row there could be
+// an env -- queries 157, 158 and 160 then budget for the rows there are, not for the largest row there could be
 static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s, const double* rows_host = nullptr)
 {
     if (query == TBX_QUERY_LOOKAHEAD || query == TBX_QUERY_LOOKAHEAD_ALL) {
@@ -2012,6 +2089,12 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
         const bool scanned = rows_host && a.per_env && a.n <= MAX_ARGS_EVOLVE;
         if (scanned) seen = evolve_scan(e, rows_host, a.n);
         return lookahead_evolve(e, a, scanned ? &seen : nullptr, out_dev, s);
+    }
+    if (query == TBX_QUERY_LOOKAHEAD_TREE) {
+        TbxTreeBounds seen;
+        const bool scanned = rows_host && a.per_env && a.n <= MAX_ARGS_TREE;
+        if (scanned) seen = tree_scan(e, rows_host, a.n);
+        return lookahead_tree(e, a, scanned ? &seen : nullptr, out_dev, s);
     }
     if (query == TBX_QUERY_LOOKAHEAD_ACT) return lookahead_act(e, a, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
@@ -2091,7 +2174,7 @@ int tbx_reduce(tbx_engine* e, int query, const double* args, int n_args, int per
     if (rc) return rc;
     const size_t bytes = sizeof(double) * (size_t)e->n * (size_t)width;
     EHIP(e->reduce_out.reserve(bytes, e->stream));
-    rc = engine_reduce(e, query, a, e->reduce_out.p, width, e->stream, args);      // (the host's rows: queries 157 and 158 scan them)
+    rc = engine_reduce(e, query, a, e->reduce_out.p, width, e->stream, args);      // (the host's rows: queries 157, 158 and 160 scan them)
     if (rc) return rc;
     EHIP(hipMemcpyAsync(out_host, e->reduce_out.p, bytes, hipMemcpyDeviceToHost, e->stream));
     EHIP(hipStreamSynchronize(e->stream));
@@ -2172,6 +2255,11 @@ int tbx_set_option(tbx_engine* e, int option, int value)
         e->beam_samples_max_chunks = value;
         return TBX_OK;
     }
+    if (option == TBX_OPT_TREE_LAUNCH_SIMULATIONS) {   // read by the host when a tree's simulations are cut into launches: nothing in flight depends on it
+        if (value < 0 || value > TBX_TREE_MAX_SIMULATIONS) return e->fail(TBX_E_INVALID, "option value out of range");
+        e->tree_launch_simulations = value;
+        return TBX_OK;
+    }
     bool ok = false;
     switch (option) {
     case TBX_OPT_PIPELINE: ok = value >= 0 && value <= 3; break;
@@ -2212,6 +2300,8 @@ int tbx_get_option(tbx_engine* e, int option, int* value_out)
     if (value_out && option == TBX_OPT_BEAM_SAMPLES_CHUNKS) { *value_out = e->beam_samples_chunks; return TBX_OK; }
     if (value_out && option == TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS) { *value_out = e->beam_samples_max_chunks; return TBX_OK; }
     if (value_out && option == TBX_OPT_EVOLVE_RANGES) { *value_out = e->evolve_ranges; return TBX_OK; }
+    if (value_out && option == TBX_OPT_TREE_RANGES) { *value_out = e->tree_ranges; return TBX_OK; }
+    if (value_out && option == TBX_OPT_TREE_LAUNCH_SIMULATIONS) { *value_out = e->tree_launch_simulations; return TBX_OK; }
     if (value_out && option == TBX_OPT_SEARCH_SAMPLES_LAUNCHES) { *value_out = e->search_samples_launches; return TBX_OK; }
     if (option < 0 || option >= TBX_OPT_COUNT || !value_out) return e->fail(TBX_E_INVALID, "unknown option");
     *value_out = e->opt[option];

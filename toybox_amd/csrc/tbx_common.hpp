@@ -459,6 +459,8 @@ struct tbx_engine {
     int beam_samples_ranges = 0, beam_samples_chunks = 0;   // env ranges, and the most sample chunks of a level, of the last TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES (0: none yet)
     int beam_samples_max_chunks = 0;   // TBX_OPT_BEAM_SAMPLES_MAX_CHUNKS (0: the engine's choice)
     int evolve_ranges = 0;             // env ranges of the last TBX_QUERY_LOOKAHEAD_EVOLVE (0: none yet); its scratch is beam_scratch
+    int tree_ranges = 0;               // env ranges of the last TBX_QUERY_LOOKAHEAD_TREE (0: none yet); its scratch is beam_scratch
+    int tree_launch_simulations = 0;   // TBX_OPT_TREE_LAUNCH_SIMULATIONS (0: the engine's choice)
     // TBX_QUERY_LOOKAHEAD_ACT: not env state -- made and zeroed on first use (act_alloc, engine.hip), never forked or checkpointed
     int32_t* plan_action = nullptr;    // [N] TBX_BUF_PLAN_ACTION: the ALE action of every env's winner
     uint32_t* plan_carry = nullptr;    // [N] TBX_BUF_PLAN_CARRY: the winner's code shifted by one period
@@ -1450,18 +1452,235 @@ void tbx_launch_beam_samples(const G& g, const TbxEditArgs& a, int level, int sl
     hipLaunchKernelGGL(tbx_beam_samples_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, level, slots, chunks, first_env, (int)count, sc);
 }
 
+// ---- TBX_QUERY_LOOKAHEAD_TREE (include/toybox_amd.h): open-loop tree search over plan prefixes.  A node of depth d IS a plan code
+// of depth d, selection reads visit statistics and never simulated state, and one simulation is the plan query's leaf on future m --
+// so the play step is leaf(env, lane, look, salt_m), unchanged, and the tree is all that is new.
+
+// The values of a row {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, simulations, explore, salt} are a valid
+// tree row; the kernel asks here (tbx_tree_row), and so does the host where it has the rows (tbx_reduce).
+__host__ __device__ __forceinline__ bool tbx_tree_values(int game, int frames, int hold, int depth, int objective, int rest, int simulations, int explore, double salt)
+{
+    bool playable = rest == -1;
+    for (int i = 0; i < tbx_legal_count(game); i++) playable = playable || rest == tbx_legal_action(game, i);
+    const bool ok = frames >= 1 && frames <= TBX_LOOKAHEAD_MAX_FRAMES && hold >= 1 && depth >= 1 && depth <= tbx_plan_max_depth(game) &&
+                    (objective == 0 || objective == 1) && playable && simulations >= 1 && simulations <= TBX_TREE_MAX_SIMULATIONS &&
+                    explore >= 0 && explore <= TBX_TREE_MAX_EXPLORE && salt >= 0.0 && salt < 4294967296.0;
+    return ok && ((uint64_t)salt == 0 || (uint64_t)salt + (uint64_t)simulations - 1 < (1ull << 32));
+}
+__device__ __forceinline__ bool tbx_tree_row(int game, const TbxEditArgs& a, int env, int& depth, int& objective, int& simulations, int& explore, uint64_t& salt)
+{
+    depth = a.n > 2 ? a.geti(env, 2) : 1;
+    objective = a.n > 3 ? a.geti(env, 3) : 0;
+    simulations = a.n > 9 ? a.geti(env, 9) : 1;
+    explore = a.n > 10 ? a.geti(env, 10) : 0;
+    const double salt_arg = a.n > 11 ? a.get(env, 11) : 0.0;
+    const bool ok = tbx_tree_values(game, a.geti(env, 0), a.n > 1 ? a.geti(env, 1) : 1, depth, objective, a.n > 4 ? a.geti(env, 4) : -1, simulations, explore, salt_arg);
+    salt = ok ? (uint64_t)salt_arg : 0ull;
+    return ok;
+}
+// One node, 32 bytes: link 0 is "no child" (node 0 is the root, nobody's child), and TBX_TREE_MAX_SIMULATIONS + 1 nodes keep the
+// ids in 16 bits.  `nodes`, the nodes of the tree so far, is read in the root alone.
+struct TbxTreeNode {
+    long long v_sum;
+    uint32_t n;
+    uint16_t child[6];
+    uint32_t nodes, pad;
+};
+static_assert(sizeof(TbxTreeNode) == 32, "two nodes a 64-byte line");
+// The scratch of one env range, indexed by the unit's number WITHIN the range: per unit a block of unit_bytes() -- the root's eight
+// sums (64-bit integers, one 64-byte line), then `stride` nodes in creation order, stride even -- so a block is whole 64-byte lines
+// and no lane's stores share a line with another lane's.  A lane's loads are its own lines too: nothing here coalesces, and nothing
+// needs to (profiles/tree.md: a path of at most 16 nodes per `frames` steps of play).
+struct TbxTreeScratch {
+    uint8_t* base;
+    int stride;
+    __host__ __device__ static size_t unit_bytes(int stride) { return 64 + (size_t)stride * sizeof(TbxTreeNode); }
+    __host__ __device__ static int stride_for(int simulations) { return (simulations + 2) & ~1; }       // simulations + 1 nodes, rounded up to even
+    __device__ __forceinline__ long long* sums(int unit) const { return reinterpret_cast<long long*>(base + (size_t)unit * unit_bytes(stride)); }
+    __device__ __forceinline__ TbxTreeNode* nodes(int unit) const { return reinterpret_cast<TbxTreeNode*>(base + (size_t)unit * unit_bytes(stride) + 64); }
+};
+// the exact floor square root of x < 2^27: the double square root, corrected by one step
+__device__ __forceinline__ long long tbx_isqrt(long long x)
+{
+    long long r = (long long)sqrt((double)x);
+    if (r * r > x) r--;
+    else if ((r + 1) * (r + 1) <= x) r++;
+    return r;
+}
+// Selection of one simulation in the tree `nd` of first action `cand`: walks from the root by priority, expands at most one node,
+// and leaves the plan to play in depth_out / code_out.  Every node is read where it lies; nothing is kept in a per-thread array.
+template <int GAME>
+__device__ __forceinline__ void tbx_tree_select(TbxTreeNode* nd, int stride, int cand, int depth, long long explore, int& depth_out, uint32_t& code_out)
+{
+    const int L = tbx_legal_count(GAME);
+    int cur = 0, d = 1;
+    uint32_t code = (uint32_t)cand, pow = (uint32_t)L;        // (pow wraps only after its last use, as in tbx_evolve_first_code)
+    while (d < depth) {
+        int miss = -1;
+#pragma unroll
+        for (int k = L - 1; k >= 0; k--) miss = nd[cur].child[k] == 0 ? k : miss;
+        if (miss >= 0) {
+            const uint32_t id = nd[0].nodes;
+            if (id >= (uint32_t)stride) break;                 // (never: a simulation adds at most one node, and stride > simulations)
+            nd[0].nodes = id + 1;
+            TbxTreeNode fresh{};
+            nd[id] = fresh;
+            nd[cur].child[miss] = (uint16_t)id;
+            code += (uint32_t)miss * pow;
+            d++;
+            break;
+        }
+        const long long root_term = explore * tbx_isqrt((long long)nd[cur].n << 16);
+        int best = 0, best_child = 0;
+        long long best_p = 0;
+#pragma unroll
+        for (int k = 0; k < L; k++) {
+            const int c = nd[cur].child[k];
+            const long long n_k = nd[c].n;
+            const long long p = nd[c].v_sum * 256 / (n_k > 0 ? n_k : 1) + root_term / (1 + n_k);
+            if (k == 0 || p > best_p) { best = k; best_child = c; best_p = p; }
+        }
+        code += (uint32_t)best * pow;
+        pow *= (uint32_t)L;
+        d++;
+        cur = best_child;
+    }
+    depth_out = d;
+    code_out = code;
+}
+// Backup of value v along the path of `code` at depth d: a second descent from the root by the digits of the code -- no path stack
+template <int GAME>
+__device__ __forceinline__ void tbx_tree_backup(TbxTreeNode* nd, int d, uint32_t code, long long v)
+{
+    const uint32_t L = (uint32_t)tbx_legal_count(GAME);
+    int cur = 0;
+    uint32_t c = code / L;
+    for (int level = 1; level <= d; level++, c /= L) {
+        nd[cur].n += 1;
+        nd[cur].v_sum += v;
+        if (level < d) cur = nd[cur].child[c % L];
+    }
+}
+// The row's last four: the principal variation from the root -- the child with the largest n, then the larger v_sum, then the smaller k
+template <int GAME>
+__device__ __forceinline__ void tbx_tree_store_pv(const TbxTreeNode* nd, int cand, double* o)
+{
+    const int L = tbx_legal_count(GAME);
+    int cur = 0, d = 1;
+    uint32_t code = (uint32_t)cand, pow = (uint32_t)L;
+    for (;;) {
+        int best = -1, best_child = 0;
+#pragma unroll
+        for (int k = 0; k < L; k++) {
+            const int c = nd[cur].child[k];
+            if (c == 0) continue;
+            if (best < 0 || nd[c].n > nd[best_child].n || (nd[c].n == nd[best_child].n && nd[c].v_sum > nd[best_child].v_sum)) { best = k; best_child = c; }
+        }
+        if (best < 0) break;
+        code += (uint32_t)best * pow;
+        pow *= (uint32_t)L;
+        d++;
+        cur = best_child;
+    }
+    o[8] = (double)code; o[9] = (double)d; o[10] = (double)nd[cur].n; o[11] = (double)nd[cur].v_sum;
+}
+
+// A unit is (env, first action), unit = (env - first_env) * L + cand: neighbouring lanes hold the actions of one env, as in
+// tbx_lookahead_kernel.  It runs the simulations m0 .. m1-1 of its tree (its own row may have fewer) one after the other -- select,
+// play through the opaque env index (reload, salt: the loop of tbx_sample_kernel), back up, add to the root's sums -- with the tree
+// and the sums in scratch from launch to launch: the launch with m0 = 0 makes the empty tree, the one that holds the row's last
+// simulation stores the row.  Wave forms: lane 0 walks and updates the tree, depth and code are broadcast before the play.  A
+// refused row answers zeros at m0 = 0.
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) void tbx_tree_kernel(G g, TbxEditArgs a, int m0, int m1, int first_env, int count, TbxTreeScratch sc, double* __restrict__ out)
+{
+    const int L = tbx_legal_count(G::GAME);
+    const int lane = threadIdx.x & 63;
+    const int rel = G::WAVE ? wave_uniform((int)(blockIdx.x * (G::BLOCK / 64) + (threadIdx.x >> 6))) : (int)(blockIdx.x * G::BLOCK + threadIdx.x);
+    if (rel >= count) return;
+    int env = first_env + rel / L, cand = rel % L;
+    const bool writer = !G::WAVE || lane == 0;
+    double* const o = out + ((size_t)env * L + cand) * 12;
+    TbxLookahead<G::GAME, true> look;
+    int depth, objective, M, explore;
+    uint64_t salt;
+    bool ok = look.read_plan(a, env, 1);
+    ok = tbx_tree_row(G::GAME, a, env, depth, objective, M, explore, salt) && ok;
+    uint64_t seed = (uint64_t)a.getu(env, 5) | ((uint64_t)a.getu(env, 6) << 32);
+    uint64_t env_key = ((uint64_t)a.getu(env, 8) + (uint64_t)env) << 32;
+    if (G::WAVE) {
+        env = wave_uniform(env); cand = wave_uniform(cand); ok = wave_uniform(ok);
+        depth = wave_uniform(depth); objective = wave_uniform(objective); M = wave_uniform(M); explore = wave_uniform(explore);
+        salt = wave_uniform64(salt); seed = wave_uniform64(seed); env_key = wave_uniform64(env_key);
+    }
+    if (!ok) {
+        if (writer && m0 == 0)
+            for (int i = 0; i < 12; i++) o[i] = 0.0;
+        return;
+    }
+    if (m0 >= M) return;
+    const int last = m1 < M ? m1 : M;
+    long long* const sums = sc.sums(rel);
+    TbxTreeNode* const nd = sc.nodes(rel);
+    if (writer && m0 == 0) {
+        for (int i = 0; i < 8; i++) sums[i] = 0;
+        TbxTreeNode root{};
+        root.nodes = 1;
+        nd[0] = root;
+    }
+    for (int m = m0; m < last; m++) {
+        int d = 1;
+        uint32_t code = (uint32_t)cand;
+        if (writer) tbx_tree_select<G::GAME>(nd, sc.stride, cand, depth, (long long)explore, d, code);
+        look.depth = d;
+        look.code = code;
+        look.key = tbx_splitmix64(seed + (uint64_t)m) ^ env_key;
+        if (G::WAVE) look.uniform_plan();
+        // every simulation RELOADS its env through an opaque index, as every sample of tbx_sample_kernel does (profiles/search.md)
+        int env_now = env;
+        if (G::WAVE) asm volatile("" : "+s"(env_now));
+        else asm volatile("" : "+v"(env_now));
+        TbxLookFields f = g.leaf(env_now, lane, look, salt ? salt + (uint64_t)m : 0ull);
+        if (G::WAVE) {
+            f.ret = (long long)wave_uniform64((uint64_t)f.ret);
+            f.lives = wave_uniform(f.lives); f.frames_run = wave_uniform(f.frames_run); f.lost_at = wave_uniform(f.lost_at);
+        }
+        if (writer) {
+            const long long safe = f.lost_at < 0 ? f.frames_run : f.lost_at;
+            tbx_tree_backup<G::GAME>(nd, look.depth, look.code, objective == 0 ? f.ret : safe);
+            const bool first = sums[0] == 0;
+            sums[2] = first || f.ret < sums[2] ? f.ret : sums[2];
+            sums[3] = first || f.ret > sums[3] ? f.ret : sums[3];
+            sums[0] += 1; sums[1] += f.ret; sums[4] += f.lives; sums[5] += f.lost_at >= 0 ? 1 : 0; sums[6] += f.lives <= 0 ? 1 : 0; sums[7] += safe;
+        }
+    }
+    if (writer && last == M) {
+        for (int i = 0; i < 8; i++) o[i] = (double)sums[i];
+        tbx_tree_store_pv<G::GAME>(nd, cand, o);
+    }
+}
+
+template <class G>
+void tbx_launch_tree(const G& g, const TbxEditArgs& a, int m0, int m1, int first_env, int envs, const TbxTreeScratch& sc, double* out, hipStream_t s)
+{
+    const long long count = (long long)envs * tbx_legal_count(G::GAME);     // (lookahead_tree, engine.hip: below 2^30)
+    const long long threads = count * (G::WAVE ? 64 : 1);
+    hipLaunchKernelGGL(tbx_tree_kernel<G>, dim3((unsigned)((threads + G::BLOCK - 1) / G::BLOCK)), dim3(G::BLOCK), 0, s, g, a, m0, m1, first_env, (int)count, sc, out);
+}
+
 // One play launch of a planner query as the engine hands it to the game (GameOps::lookahead_play): which query, the env range, and
 // of the rest what that query's tbx_launch_* above takes.  TBX_QUERY_LOOKAHEAD / _ALL / _PLAN: every env, first_env = 0, rows = the
 // output.
 struct TbxPlanLaunch {
-    int query;                       // TBX_QUERY_LOOKAHEAD / _ALL / _PLAN / _SEARCH / _SAMPLES / _SEARCH_SAMPLES / _BEAM / _EVOLVE / _BEAM_SAMPLES
+    int query;                       // TBX_QUERY_LOOKAHEAD / _ALL / _PLAN / _SEARCH / _SAMPLES / _SEARCH_SAMPLES / _BEAM / _EVOLVE / _BEAM_SAMPLES / _TREE
     int first_env, envs, chunks;
-    int level, first_slot, slots;    // level: the beam's level or the generation
+    int level, first_slot, slots;    // level: the beam's level or the generation; the tree: simulations first_slot .. first_slot + slots - 1
     double* rows;
     union {                          // the scratch view of the query
         TbxBeamScratch beam;
         TbxEvolveScratch evolve;
         TbxBeamSamplesScratch beam_samples;
+        TbxTreeScratch tree;
     };
 };
 // the play kernel of l.query with the game's leaf policy g; false: no arm for that query, nothing launched.  A plain switch: every
@@ -1479,6 +1698,7 @@ bool tbx_launch_planner(const G& g, const TbxEditArgs& a, const TbxPlanLaunch& l
     case TBX_QUERY_LOOKAHEAD_BEAM: tbx_launch_beam(g, a, l.level, l.slots, l.first_env, l.envs, l.beam, s); break;
     case TBX_QUERY_LOOKAHEAD_EVOLVE: tbx_launch_evolve(g, a, l.level, l.first_slot, l.slots, l.first_env, l.envs, l.evolve, s); break;
     case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: tbx_launch_beam_samples(g, a, l.level, l.slots, l.chunks, l.first_env, l.envs, l.beam_samples, s); break;
+    case TBX_QUERY_LOOKAHEAD_TREE: tbx_launch_tree(g, a, l.first_slot, l.first_slot + l.slots, l.first_env, l.envs, l.tree, l.rows, s); break;
     default: return false;
     }
     return true;
@@ -1661,7 +1881,7 @@ struct GameOps {
     // batched interventions (include/toybox_amd.h, tbx_edit / tbx_reduce): one kernel over the selected envs
     virtual int edit(tbx_engine* e, int /*op*/, const TbxEditArgs&, const uint8_t* /*mask_dev*/, hipStream_t) { return e->fail(TBX_E_INVALID, "this game has no such edit"); }
     virtual int reduce(tbx_engine* e, int /*query*/, const TbxEditArgs&, double* /*out_dev*/, int /*width*/, hipStream_t) { return e->fail(TBX_E_INVALID, "this game has no such query"); }
-    // TBX_QUERY_LOOKAHEAD .. _EVOLVE: the play kernel of l.query with the game's leaf policy (tbx_launch_planner) over the units of
+    // TBX_QUERY_LOOKAHEAD .. _TREE: the play kernel of l.query with the game's leaf policy (tbx_launch_planner) over the units of
     // envs [l.first_env, l.first_env + l.envs); the arguments' shared values are already checked (engine.hip).  search_lanes(): the
     // lanes one unit takes in the form the engine is in (64 or 1)
     virtual int lookahead_play(tbx_engine* e, const TbxEditArgs&, const TbxPlanLaunch&, hipStream_t) { return e->fail(TBX_E_UNSUPPORTED, "this game has no lookahead"); }

@@ -477,6 +477,44 @@ def beam_samples_args(game, n_envs, frames, depth, width, samples, hold=1, objec
     return args, True
 
 
+TREE_FIELDS = SAMPLE_FIELDS + ("code", "pv_depth", "pv_visits", "pv_value")
+
+
+def tree_args(game, n_envs, frames, depth, simulations=1, explore=0, salt=0, hold=1, objective=0, rest=None, seed=0, t=0, env_offset=0):
+    """The argument rows of TBX_QUERY_LOOKAHEAD_TREE: columns {frames, hold, depth, objective, rest, seed_lo, seed_hi, t,
+    env_offset, simulations, explore, salt} -- the beam's first nine with the three of the tree appended; (args, per_env) as
+    lookahead_args gives them.  Shared values are range-checked here (ValueError): depth 1 .. PLAN_MAX_DEPTH (no n_legal ** depth
+    cap), simulations 1 .. TREE_MAX_SIMULATIONS, explore 0 .. TREE_MAX_EXPLORE (an integer in units of the value), the salt ranges
+    of sample_args with simulations for samples, objective 0 / "return" or 1 / "survival"; per-env rows are left to the device (a
+    bad row answers zeros)."""
+    name = _game_name(game)
+    if isinstance(objective, str):
+        if objective not in SEARCH_OBJECTIVES:
+            raise ValueError("tree objective is 'return' or 'survival', got %r" % (objective,))
+        objective = SEARCH_OBJECTIVES[objective]
+    if not np.ndim(objective) and int(objective) not in (0, 1):
+        raise ValueError("tree objective is 0 (return) or 1 (survival), got %r" % (objective,))
+    if not np.ndim(depth) and not 1 <= int(depth) <= _abi.PLAN_MAX_DEPTH[name]:
+        raise ValueError("tree depth must be 1 .. %d, got %r" % (_abi.PLAN_MAX_DEPTH[name], depth))
+    own = (("simulations", simulations), ("explore", explore), ("salt", salt))
+    for what, c in own:
+        if np.ndim(c) > 1 or (np.ndim(c) == 1 and len(c) != int(n_envs)):
+            raise ValueError("lookahead %s is a scalar or one value per env (%d), got shape %r" % (what, n_envs, np.shape(c)))
+    for what, c, lo, hi in (("simulations", simulations, 1, _abi.TREE_MAX_SIMULATIONS), ("explore", explore, 0, _abi.TREE_MAX_EXPLORE), ("salt", salt, 0, (1 << 32) - 1)):
+        if not np.ndim(c) and not lo <= int(c) <= hi:
+            raise ValueError("tree %s must be %d .. %d, got %r" % (what, lo, hi, c))
+    if not np.ndim(salt) and int(salt) and not np.ndim(simulations) and int(salt) + int(simulations) - 1 >= 1 << 32:
+        raise ValueError("tree salt + simulations - 1 must stay below 2**32, got %r + %r" % (salt, simulations))
+    base, per_env = _plan_rows("objective", name, n_envs, frames, hold, depth, objective, rest, seed, t, env_offset)
+    if not per_env and not any(np.ndim(c) for _, c in own):
+        return list(base) + [float(int(c)) for _, c in own], False
+    args = np.empty((int(n_envs), 12), np.float64)
+    args[:, :9] = np.asarray(base, np.float64)
+    for k, (_, c) in enumerate(own):
+        args[:, 9 + k] = np.asarray(c, np.float64)
+    return args, True
+
+
 class Engine:
     def __init__(self, game, n_envs=1, device=0, config=None, lib=None):
         self._lib = lib if lib is not None else load()
@@ -807,6 +845,37 @@ class Engine:
     def evolve_ranges(self):
         """into how many env ranges the last lookahead_evolve was cut (0: none yet)"""
         return self.get_option(_abi.OPT_EVOLVE_RANGES)
+
+    def lookahead_tree(self, frames, depth, simulations, explore=0, salt=0, hold=1, objective="return", rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_TREE: open-loop Monte-Carlo tree search on the device -- per env and first action a tree of action
+        prefixes up to `depth` periods deep, grown by `simulations` (1 .. TREE_MAX_SIMULATIONS) futures spent adaptively: every
+        simulation walks down by the priority Q + U (Q the mean value of a child in 1/256ths, U = explore x sqrt(visits of the
+        parent) / (1 + visits of the child), in integers), adds at most one node and plays its prefix, `rest` behind it, on future
+        m (seed sample_seed(seed, m), the game RNG salted by salt + m where salt is not 0: the futures of lookahead_samples, the
+        same for all first actions).  The value is ret ("return") or the frames before the first lost life ("survival").  Returns
+        a dict of [N, n_legal] arrays: the eight lookahead_samples() sums of the root (samples 0: the row was refused), then the
+        principal variation -- the most visited path -- as code (uint64), pv_depth, pv_visits and pv_value (the sum of the values
+        through its last node), int64.  With depth 1 the sums are lookahead_samples'.  Nothing in the engine is written."""
+        args, _ = tree_args(self.game, self.n_envs, frames, depth, simulations, explore, salt, hold, objective, rest, seed, t, env_offset)
+        return self._tree_dict(self.reduce(_abi.QUERY_LOOKAHEAD_TREE, args))
+
+    def _tree_dict(self, out):
+        out = np.asarray(out).reshape(self.n_envs, len(self.legal_actions), 12)
+        return {k: out[..., i].astype(np.uint64 if k == "code" else np.int64) for i, k in enumerate(TREE_FIELDS)}
+
+    @property
+    def tree_ranges(self):
+        """into how many env ranges the last lookahead_tree was cut (0: none yet)"""
+        return self.get_option(_abi.OPT_TREE_RANGES)
+
+    @property
+    def tree_launch_simulations(self):
+        """at most this many simulations per launch of a lookahead_tree, on top of the engine's budget (0: the engine's choice)"""
+        return self.get_option(_abi.OPT_TREE_LAUNCH_SIMULATIONS)
+
+    @tree_launch_simulations.setter
+    def tree_launch_simulations(self, simulations):
+        self.set_option(_abi.OPT_TREE_LAUNCH_SIMULATIONS, simulations)
 
     def lookahead_act(self, planner, **planner_keywords):
         """TBX_QUERY_LOOKAHEAD_ACT: the planner's query (a name of ACT_PLANNERS or its id; keywords as act_args takes them) with

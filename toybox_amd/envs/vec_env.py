@@ -192,6 +192,22 @@ def _beam_samples(env, frames, hold, depth, width, samples, objective, rest, see
     return _with_sample_best(env, out, depth, objective)
 
 
+def _tree(env, frames, hold, depth, simulations, explore, objective, rest, seed, t, salt):
+    """Engine.lookahead_tree for an adapter: `rest` an action index going in; the rows are in action-index order.  best_action is
+    sample_best_action over the root sums, best_plan [num_envs, depth] the digits of that row's principal variation, -1 beyond
+    its pv_depth"""
+    from ..engine import plan_digits
+    if objective not in ("return", "survival"):
+        raise ValueError("objective is 'return' or 'survival', got %r" % (objective,))
+    out = env.engine.lookahead_tree(frames, int(depth), int(simulations), explore=explore, salt=salt, hold=hold, objective=objective, rest=_ale(env, rest), seed=seed, t=t)
+    out["best_action"] = sample_best_action(out, objective)
+    rows = np.arange(out["code"].shape[0])
+    plan = plan_digits(len(env._action_set), out["code"][rows, out["best_action"]], int(depth))
+    plan[np.arange(int(depth))[None, :] >= out["pv_depth"][rows, out["best_action"]][:, None]] = -1
+    out["best_plan"] = plan
+    return out
+
+
 class _PlanLoop:
     """What plan_step / plan_rollout of an adapter keep on the device: a stream of their own, the rows of the last rollout's
     TBX_QUERY_LOOKAHEAD_ACT calls [k][N][11] and its per-step rewards and dones, copied device-to-device behind every step"""
@@ -478,6 +494,17 @@ class ToyboxVecEnv:
         if self._in_flight is not None or self._pending is not None:
             self.step_wait()
         return _evolve(self, int(steps), 1, depth, population, generations, elite, mutation, plan_seed, init_plan, objective, rest, seed, t)
+
+    def tree_search(self, steps, depth, simulations, explore=0, objective="return", rest=None, seed=0, t=0, salt=0):
+        """Monte-Carlo tree search over action prefixes up to `depth` steps deep (Engine.lookahead_tree): per first action index
+        `simulations` futures of `steps` steps are spent adaptively -- each walks down the tree by mean value plus `explore` x
+        the visit bonus, adds at most one node and plays its prefix, `rest` behind it.  The eight sums of sample_lookahead() over
+        the root's futures, then the most visited path: code, pv_depth, pv_visits, pv_value [num_envs, n_actions]; best_action
+        [num_envs] by sample_best_action and best_plan [num_envs, depth] (action indices, -1 beyond the path's depth).  Nothing
+        is touched; a pending step_async ends first."""
+        if self._in_flight is not None or self._pending is not None:
+            self.step_wait()
+        return _tree(self, int(steps), 1, depth, simulations, explore, objective, rest, seed, t, salt)
 
     def plan_rollout(self, k, planner="evolve", steps=16, depth=4, hold=1, objective="return", rest=None, seed=0, t=0, **planner_keywords):
         """k closed-loop steps queued back to back on a stream of the env's own, no host synchronisation in between
@@ -896,6 +923,13 @@ class ToyboxPreprocVecEnv:
         if self._in_flight is not None:
             self.step_wait()
         return _evolve(self, int(steps) * self._skip, self._skip, depth, population, generations, elite, mutation, plan_seed, init_plan, objective, rest, seed, t)
+
+    def tree_search(self, steps, depth, simulations, explore=0, objective="return", rest=None, seed=0, t=0, salt=0):
+        """ToyboxVecEnv.tree_search in agent steps: steps x skip raw frames, every action held for skip frames; raw frames, no
+        wrapper, as in lookahead().  Between step_async and step_wait the step ends first."""
+        if self._in_flight is not None:
+            self.step_wait()
+        return _tree(self, int(steps) * self._skip, self._skip, depth, simulations, explore, objective, rest, seed, t, salt)
 
     def plan_rollout(self, k, planner="evolve", steps=16, depth=4, objective="return", rest=None, seed=0, t=0, **planner_keywords):
         """ToyboxVecEnv.plan_rollout in agent steps: per step the planner looks steps x skip raw frames ahead with hold = skip
