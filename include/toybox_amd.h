@@ -926,10 +926,77 @@ int tbx_query(tbx_engine* engine, int env, int query_id, const int32_t* args, in
 #define TBX_TREE_MAX_SIMULATIONS 1024
 #define TBX_TREE_MAX_EXPLORE     1048576
 #define TBX_QUERY_LOOKAHEAD_TREE 160  /* {frames, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, simulations, explore, salt} -> 12 * n_legal(game) */
-/* ids of tbx_device_buffer that exist only once this query has run */
+/* Closed-loop tree search: search, pick, act and CARRY THE CHOSEN SUBTREE.  TBX_QUERY_LOOKAHEAD_ACT closes the loop for the planners
+ * that answer a plan code; this query closes it for TBX_QUERY_LOOKAHEAD_TREE, whose memory is a tree: after a* is played, the subtree
+ * under the root's children of tree a* is a search already done for the next state, and the next call may start from it.
+ *   Arguments: {the twelve columns of TBX_QUERY_LOOKAHEAD_TREE in its order, reuse}.  Trailing columns may be left out with 160's
+ *   defaults; reuse defaults to 0 and must be 0 or 1; at most 13 arguments.  SHARED ARGUMENTS ONLY: per_env = 1 answers TBX_E_INVALID
+ *   with nothing launched.  Every shared value is checked exactly as TBX_QUERY_LOOKAHEAD_TREE checks it.
+ *   Step 1, start trees, per env e and first action index a.  With reuse = 1 the tree starts as the carried tree (e, a) of the store
+ *   (below) where one is LIVE: the store exists, its key (frames, hold, depth, objective, simulations) equals this call's, env e's
+ *   drop flag is clear, and the carried tree is present (node count above 0).  Otherwise, and with reuse = 0 always, it starts as
+ *   160's empty root.  The root's eight sums start at zero in every call: they cover this call's M futures only, so samples = M and
+ *   rows stay comparable between actions and between calls.  Carried statistics steer the selection and nothing else.
+ *   Step 2, M simulations: exactly 160's selection, play, backup and common random numbers, on the start trees.  A link that the
+ *   carry dropped (below) is a missing child and is re-expanded as 160 expands.  Row columns 0 .. 7 are this call's sums; columns
+ *   8 .. 11 are the principal variation of the whole tree, carried nodes included, so pv_visits may exceed M.
+ *   Step 3, pick: one winner a* per env among the L rows, by the order of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES on (ret_sum, lost,
+ *   safe_frames_sum) for `objective`, then the smaller action index -- TBX_QUERY_LOOKAHEAD_ACT's pick of a sampled planner.
+ *   Out, width 14 for every game: out[env] = {legal[a*], a*, the twelve columns of a*'s row}.  legal[a*] also goes to
+ *   TBX_BUF_PLAN_ACTION int32[N], the buffer and pointer of TBX_QUERY_LOOKAHEAD_ACT (this query makes both of that query's buffers,
+ *   zeroed, if they do not exist yet); TBX_BUF_PLAN_CARRY is left unchanged.
+ *   Step 4, carry: for every k in 0 .. L-1 the new carried tree (e, k) is the subtree of the final tree a* under the root's child k,
+ *   absent (node count 0) where the root has no such child; with depth 1 everything is absent.  Node ids in a tree always grow from
+ *   parent to child (creation order; the carry preserves it), so the subtree's nodes are taken in ascending source id: the first
+ *   `keep` of them are kept and renumbered 0, 1, 2, ... in that order -- the root's child comes first and becomes the new root.  A
+ *   link to a node that was not kept becomes 0; a dropped node's descendants have larger ids and are dropped with it; the
+ *   ancestors keep their n and v_sum.  keep = simulations + 1 (TBX_OPT_TREE_CARRY_KEEP lowers it), so a start tree plus M
+ *   expansions never passes 2 * simulations + 1 nodes and the ids stay in 16 bits.  If the new root's n exceeds
+ *   TBX_TREE_CARRY_MAX_VISITS (TBX_OPT_TREE_CARRY_MAX_VISITS lowers it), every kept node of that tree gets n = (n + 1) / 2 and
+ *   v_sum = v_sum / 2, integer divisions: values are non-negative and every carried node has n >= 1, so no n becomes 0 and
+ *   child n <= parent n survives.  No node's n ever passes TBX_TREE_CARRY_MAX_VISITS + TBX_TREE_MAX_SIMULATIONS = 5120: that, with
+ *   the ranges of 160, is what keeps the selection's signed 64-bit arithmetic below 2^60 in this query (v_sum <= 5120 values of at
+ *   most 2^31, times 256; explore * isqrt(5120 << 16) < 2^20 * 2^15).
+ *   The store, TBX_BUF_PLAN_TREE, engine-owned: made by the first successful call of this query, TBX_E_INVALID until then.  N x L unit
+ *   blocks in env-major order, block (e, k) at byte (e * L + k) * (64 + 32 * stride), stride = (simulations + 2) & ~1.  A block is one
+ *   64-byte line whose first uint32 is the node count (0: absent) and whose other bytes are zero, then `stride` nodes of 32 bytes:
+ *   int64 v_sum, uint32 n, uint16 child[6] (0: no child; child[L ..] zero), and 8 bytes of zero.  Nodes past the count are
+ *   unspecified.  The store is rewritten for every env by each successful call, with either value of reuse, and left byte for byte
+ *   unchanged by a refused one.  Its size follows `simulations`: a call with another `simulations` may move it (ask
+ *   tbx_device_buffer again), and the key rule has made its content dead by then.  A failed allocation returns the HIP error and
+ *   leaves the engine without a store.  The drop flags (uint8[N]) and the key live beside it.  All of it is ENGINE state, not env
+ *   state: TBX_EDIT_COPY_ENV, the checkpoint edits, tbx_new_game and tbx_set_states leave it alone.  A caller who resets or rewrites
+ *   envs says so with TBX_EDIT_TREE_DROP (no arguments, the usual mask in host or device form, NULL meaning all; TBX_E_INVALID before
+ *   the store exists): it sets the drop flag of the masked envs, the next call of this query starts those envs' trees empty whatever
+ *   reuse says, and every successful call clears all flags.  In the device form it is one small kernel on the given stream, so a
+ *   device-side loop queues it behind every step with mask_dev = the step's own done buffer and forgets the trees of games that
+ *   ended, with no host in it.  A stale tree is a heuristic gone wrong, not a wrong answer -- but statistics of a lost game must not
+ *   steer a new one.
+ *   "Nothing in the engine changes" holds for state, RNGs, step outputs, records, agent layer and checkpoint store: the action buffer,
+ *   the store with its flags and key, and the scratch are the only writes.  On tbx_reduce_device everything runs on the caller's
+ *   stream in order, with no host synchronisation in a call that allocates nothing.  The scratch: the working trees of one env range
+ *   have 2 * simulations + 2 nodes and live in the planners' shared scratch under twice its usual budget (512 MiB instead of 256), so
+ *   that the env ranges are never smaller than TBX_QUERY_LOOKAHEAD_TREE's; that scratch only grows, so an engine that has run this
+ *   query keeps up to 512 MiB for its later planner queries, until tbx_destroy.
+ *   It follows that
+ *     (i)   with reuse = 0 columns 2 .. 13 are TBX_QUERY_LOOKAHEAD_TREE's row for a* bit for bit, and a* is the sampled planners'
+ *           pick on 160's rows;
+ *     (ii)  with reuse = 1 and no live tree the call equals reuse = 0: the first call, a changed key, dropped envs;
+ *     (iii) column `samples` is M in every row;
+ *     (iv)  env ranges (TBX_OPT_BEAM_RANGE_ENVS) and launch cuts (TBX_OPT_TREE_LAUNCH_SIMULATIONS) change no output bit and no byte of
+ *           the store;
+ *     (v)   the store after a call is step 4 applied to the final trees, node by node;
+ *     (vi)  a refused call changes neither buffer nor store nor flags.
+ *   TBX_E_INVALID, nothing launched: per_env = 1, more than 13 arguments, reuse other than 0 or 1, whatever
+ *   TBX_QUERY_LOOKAHEAD_TREE refuses in a shared row. */
+#define TBX_TREE_CARRY_MAX_VISITS 4096   /* 4 * TBX_TREE_MAX_SIMULATIONS */
+#define TBX_QUERY_LOOKAHEAD_TREE_ACT 161  /* {the twelve columns of 160, reuse} -> 14 */
+#define TBX_EDIT_TREE_DROP 44             /* {} : the masked envs' carried trees are dead for the next TBX_QUERY_LOOKAHEAD_TREE_ACT */
+/* ids of tbx_device_buffer that exist only once their query has run */
 enum {
-    TBX_BUF_PLAN_ACTION = 17,    /* int32[N]  the ALE action every env's winner of the last TBX_QUERY_LOOKAHEAD_ACT plays first */
-    TBX_BUF_PLAN_CARRY = 18      /* uint32[N] that winner's plan code shifted by one period: the next call's init = -2 */
+    TBX_BUF_PLAN_ACTION = 17,    /* int32[N]  the ALE action every env's winner of the last TBX_QUERY_LOOKAHEAD_ACT / _TREE_ACT plays first */
+    TBX_BUF_PLAN_CARRY = 18,     /* uint32[N] that winner's plan code shifted by one period: the next call's init = -2 */
+    TBX_BUF_PLAN_TREE = 19       /* the carried trees of the last TBX_QUERY_LOOKAHEAD_TREE_ACT, N x n_legal unit blocks (layout above) */
 };
 int tbx_reduce_width(int game, int query);   /* doubles per env, or TBX_E_INVALID */
 int tbx_edit(tbx_engine* engine, int op, const double* args_host, int n_args, int per_env, const uint8_t* mask_host);
@@ -1253,6 +1320,12 @@ int tbx_device_buffer(tbx_engine* engine, int which, void** out_ptr, size_t* out
 /* at most this many simulations per launch of a TBX_QUERY_LOOKAHEAD_TREE (0 .. TBX_TREE_MAX_SIMULATIONS), on top of the engine's
  * budget; 0 (default): the engine's choice.  It changes no output bit. */
 #define TBX_OPT_TREE_LAUNCH_SIMULATIONS 116
+/* for tests of the carry of TBX_QUERY_LOOKAHEAD_TREE_ACT; neither changes anything at its default.
+ * at most this many nodes of a subtree are carried: 0 (default) means simulations + 1.  The option is set before a call names its
+ * `simulations`, so tbx_set_option accepts 1 .. TBX_TREE_MAX_SIMULATIONS + 1 and a call carries min(value, simulations + 1). */
+#define TBX_OPT_TREE_CARRY_KEEP 117
+/* the halving threshold of the carry: 0 (default) means TBX_TREE_CARRY_MAX_VISITS, otherwise 1 .. TBX_TREE_CARRY_MAX_VISITS */
+#define TBX_OPT_TREE_CARRY_MAX_VISITS 118
 int tbx_set_option(tbx_engine* engine, int option, int value);
 int tbx_get_option(tbx_engine* engine, int option, int* value_out);
 /* Block until all work queued by this engine has finished, and report what the asynchronous calls since the last report could

@@ -28,6 +28,7 @@ BUF_ROLLOUT_FRAMES = 15            # uint8[k][N][H][W][C] frames of the last tbx
 BUF_ROLLOUT_PACKED = 16            # uint64[k][stride] its step records (stride = the gather's records_per_rank under a K-step ring, else N)
 BUF_PLAN_ACTION = 17               # int32[N] the ALE action every env's winner of the last TBX_QUERY_LOOKAHEAD_ACT plays first
 BUF_PLAN_CARRY = 18                # uint32[N] that winner's plan code shifted by one period (init = -2 of the next call)
+BUF_PLAN_TREE = 19                 # the carried trees of the last TBX_QUERY_LOOKAHEAD_TREE_ACT, N x n_legal unit blocks
 GATHER_ID_BYTES = 128
 # engine options (tbx_set_option)
 OPT_PIPELINE, OPT_STEP_FORM, OPT_RENDER_SPLIT, OPT_AGENT_GENERIC, OPT_RESIDENT_STEP, OPT_GATHER_EVERY = 0, 1, 2, 3, 4, 5
@@ -56,6 +57,8 @@ OPT_BEAM_SAMPLES_MAX_CHUNKS = 113  # at most this many sample chunks per level o
 OPT_EVOLVE_RANGES = 114            # read-only: env ranges of the last TBX_QUERY_LOOKAHEAD_EVOLVE
 OPT_TREE_RANGES = 115              # read-only: env ranges of the last TBX_QUERY_LOOKAHEAD_TREE
 OPT_TREE_LAUNCH_SIMULATIONS = 116  # at most this many simulations per launch of a TBX_QUERY_LOOKAHEAD_TREE (0: the engine's choice)
+OPT_TREE_CARRY_KEEP = 117          # at most this many nodes of a subtree are carried by a TBX_QUERY_LOOKAHEAD_TREE_ACT (0: simulations + 1)
+OPT_TREE_CARRY_MAX_VISITS = 118    # the halving threshold of that carry (0: TREE_CARRY_MAX_VISITS)
 PIPELINE_OFF, PIPELINE_AUTO, PIPELINE_STEP_BESIDE_RENDER, PIPELINE_OVERLAP_RENDERS = 0, 1, 2, 3
 STEP_FORM_AUTO, STEP_FORM_THREAD_PER_ENV, STEP_FORM_WAVE_PER_ENV = 0, 1, 2
 
@@ -83,6 +86,7 @@ EDIT_COPY_ENV = 40
 EDIT_CHECKPOINT_SLOTS = 41
 EDIT_CHECKPOINT_SAVE = 42
 EDIT_CHECKPOINT_RESTORE = 43
+EDIT_TREE_DROP = 44
 QUERY_BRK_BRICKS_REMAINING = 110
 QUERY_BRK_NUM_BRICKS = 111
 QUERY_BRK_COLUMN = 112
@@ -128,6 +132,8 @@ QUERY_LOOKAHEAD_ACT = 159
 TREE_MAX_SIMULATIONS = 1024
 TREE_MAX_EXPLORE = 1048576
 QUERY_LOOKAHEAD_TREE = 160
+TREE_CARRY_MAX_VISITS = 4096
+QUERY_LOOKAHEAD_TREE_ACT = 161
 # the legal sets in the engine's order (tbx_legal_actions) and TBX_PLAN_MAX_DEPTH: the largest depth with n_legal ** depth <= 2 ** 32
 LEGAL_ACTIONS = {"breakout": (0, 1, 3, 4), "space_invaders": (0, 1, 3, 4, 11, 12), "amidar": (0, 1, 2, 3, 4, 5), "gridworld": (0, 2, 3, 4, 5)}
 PLAN_MAX_DEPTH = {"breakout": 16, "space_invaders": 12, "amidar": 12, "gridworld": 13}

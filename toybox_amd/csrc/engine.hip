@@ -310,6 +310,7 @@ int tbx_destroy(tbx_engine* e)
     pipe_free(e);
     hipFree(e->actions);
     hipFree(e->plan_action); hipFree(e->plan_carry); e->act_scratch.release();
+    hipFree(e->plan_tree); hipFree(e->plan_tree_drop);
     e->edit_args.release(); e->reduce_out.release(); e->search_parts.release(); e->sample_parts.release(); e->search_samples_parts.release(); e->beam_scratch.release(); envcopy_free(e); e->frame_own.release(); e->staging.release();
     hipFree(e->mask); hipFree(e->err_flag); hipFree(e->scal); hipFree(e->one_frame); hipFree(e->io_dev);
     if (e->io_host) hipHostFree(e->io_host);
@@ -1152,6 +1153,7 @@ int tbx_reduce_width(int game, int query)
     case TBX_QUERY_LOOKAHEAD_ALL: return every_game ? 5 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH: case TBX_QUERY_LOOKAHEAD_BEAM: case TBX_QUERY_LOOKAHEAD_EVOLVE: return every_game ? 6 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_ACT: return every_game ? 11 : TBX_E_INVALID;
+    case TBX_QUERY_LOOKAHEAD_TREE_ACT: return every_game ? 14 : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SAMPLES: return every_game ? 8 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES: case TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES: return every_game ? 9 * tbx_legal_count(game) : TBX_E_INVALID;
     case TBX_QUERY_LOOKAHEAD_TREE: return every_game ? 12 * tbx_legal_count(game) : TBX_E_INVALID;
@@ -1571,6 +1573,105 @@ static TbxTreeBounds tree_scan(const tbx_engine* e, const double* rows, int n)
     return b;
 }
 
+// ---- TBX_QUERY_LOOKAHEAD_TREE_ACT (include/toybox_amd.h): the tree query on start trees, then pick and carry per env range.
+
+// What lookahead_tree does on top of query 160 when it runs for query 161: where the working trees start from, where the L rows
+// of an env go before the pick, and what the carry writes.  The store's blocks have TbxTreeScratch's layout at store_stride.
+struct TbxTreeAct {
+    uint8_t* store;            // TBX_BUF_PLAN_TREE
+    uint8_t* drop;             // [N] drop flags
+    int32_t* action;           // TBX_BUF_PLAN_ACTION
+    double* rows;              // [N][L][12] the tree's rows (act_scratch)
+    int store_stride, live, keep, max_visits, objective;
+};
+
+// Step 1 for the units of one env range: one wave per unit.  A live carried tree is copied into the unit's working block, 16 bytes
+// a lane and coalesced, with the node count put where the tree kernel keeps it (the root's `nodes`); any other unit gets 160's
+// empty root.  The drop flags are read here and cleared by tbx_tree_carry_kernel, which runs behind every launch that reads them.
+__global__ __launch_bounds__(64) void tbx_tree_load_kernel(TbxTreeAct t, int legal, int first_env, TbxTreeScratch sc)
+{
+    const int rel = blockIdx.x, lane = threadIdx.x;
+    const int env = first_env + rel / legal;
+    const uint8_t* const block = t.store + ((size_t)env * legal + rel % legal) * TbxTreeScratch::unit_bytes(t.store_stride);
+    uint32_t count = t.live && !t.drop[env] ? *reinterpret_cast<const uint32_t*>(block) : 0u;
+    if (count > (uint32_t)t.store_stride) count = 0;                                   // (never: the carry keeps at most simulations + 1)
+    uint4* const dst = reinterpret_cast<uint4*>(sc.nodes(rel));
+    if (count == 0) {
+        if (lane < 2) dst[lane] = uint4{0u, 0u, lane == 1 ? 1u : 0u, 0u};              // bytes 24 .. 27 of node 0: nodes = 1
+        return;
+    }
+    const uint4* const src = reinterpret_cast<const uint4*>(block + 64);
+    for (uint32_t i = lane; i < 2 * count; i += 64) {
+        uint4 v = src[i];
+        if (i == 1) v.z = count;
+        dst[i] = v;
+    }
+}
+
+// Steps 3 and 4 for the envs of one range, one thread per env.  Pick: tbx_act_pick_kernel's sampled order on the L rows.  Carry: ONE
+// ascending pass over the working tree a*.  A node of a kept subtree carries a tag in its `pad` word (free below the root; the
+// working copy is dead after this kernel): the destination tree k, the parent's new id, the digit under it, and whether the
+// tree is being halved.  The root tags its children as new roots; a tagged node that still fits under `keep` takes the next id of
+// its tree -- the count in the block's first word is the counter -- writes itself with empty links, patches its parent's link and
+// tags its own children.  Ids grow from parent to child, so every tag is in place before its node is met, a node past `keep` tags
+// nobody, and its descendants fall with it.  Reads come from the range's working scratch and writes go to the store: tree a*'s own
+// slot is written like any other.  Nothing here coalesces: profiles/tree_act.md.
+__global__ __launch_bounds__(64) void tbx_tree_carry_kernel(TbxTreeAct t, int game, int first_env, int envs, TbxTreeScratch sc, double* __restrict__ out)
+{
+    constexpr uint32_t TAG = 1u << 31, NEW_ROOT = 1u << 30, HALVE = 1u << 29;
+    const int rel = blockIdx.x * 64 + threadIdx.x;
+    if (rel >= envs) return;
+    const int env = first_env + rel, L = tbx_legal_count(game);
+    const double* p = t.rows + (size_t)env * L * 12;
+    TbxSearchSamplesKey bk{0, 0, 0};
+    int best_a = 0;
+    for (int a = 0; a < L; a++) {
+        const TbxSearchSamplesKey k{(long long)p[a * 12 + 1], (int)p[a * 12 + 5], (int)p[a * 12 + 7]};
+        if (a == 0 || tbx_search_samples_better(t.objective, k, (uint32_t)a, bk, (uint32_t)best_a)) { bk = k; best_a = a; }
+    }
+    const int ale = tbx_legal_action(game, best_a);
+    double* const o = out + (size_t)env * 14;
+    o[0] = (double)ale;
+    o[1] = (double)best_a;
+    for (int i = 0; i < 12; i++) o[2 + i] = p[best_a * 12 + i];
+    t.action[env] = ale;
+    t.drop[env] = 0;
+
+    const size_t block_bytes = TbxTreeScratch::unit_bytes(t.store_stride);
+    uint8_t* const blocks = t.store + (size_t)env * L * block_bytes;
+    for (int k = 0; k < L; k++) {
+        uint4* const line = reinterpret_cast<uint4*>(blocks + (size_t)k * block_bytes);
+        for (int i = 0; i < 4; i++) line[i] = uint4{0u, 0u, 0u, 0u};
+    }
+    TbxTreeNode* const nd = sc.nodes(rel * L + best_a);
+    const uint32_t count = nd[0].nodes;
+    for (int k = 0; k < L; k++) {
+        const uint32_t c = nd[0].child[k];
+        if (c) nd[c].pad = TAG | NEW_ROOT | ((uint32_t)k << 20);
+    }
+    for (uint32_t id = 1; id < count; id++) {
+        const TbxTreeNode src = nd[id];
+        if (!(src.pad & TAG)) continue;
+        const uint32_t k = (src.pad >> 20) & 7u;
+        uint8_t* const block = blocks + (size_t)k * block_bytes;
+        uint32_t* const counter = reinterpret_cast<uint32_t*>(block);
+        TbxTreeNode* const dst = reinterpret_cast<TbxTreeNode*>(block + 64);
+        const uint32_t id_new = *counter;
+        if (id_new >= (uint32_t)t.keep) continue;
+        *counter = id_new + 1;
+        const bool halve = src.pad & NEW_ROOT ? src.n > (uint32_t)t.max_visits : (src.pad & HALVE) != 0;
+        TbxTreeNode kept{};
+        kept.v_sum = halve ? src.v_sum / 2 : src.v_sum;
+        kept.n = halve ? (src.n + 1) / 2 : src.n;
+        dst[id_new] = kept;
+        if (!(src.pad & NEW_ROOT)) dst[src.pad & 0xffffu].child[(src.pad >> 16) & 7u] = (uint16_t)id_new;
+        for (int j = 0; j < L; j++) {
+            const uint32_t c = src.child[j];
+            if (c) nd[c].pad = TAG | (halve ? HALVE : 0u) | (k << 20) | ((uint32_t)j << 16) | id_new;
+        }
+    }
+}
+
 // TBX_QUERY_LOOKAHEAD_TREE: shared values are refused here, before anything is launched; per-env rows are met by the kernel.  Env
 // ranges come from the beam's three budgets -- a launch of ONE simulation per unit under TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH
 // leaf-frames and TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units, the scratch under TBX_BEAM_SCRATCH_BYTES -- and TBX_OPT_BEAM_RANGE_ENVS
@@ -1580,12 +1681,16 @@ static TbxTreeBounds tree_scan(const tbx_engine* e, const double* rows, int n)
 // the trees persist in scratch between them.  Per-env rows are budgeted by `rows` where the host form has scanned them, else as
 // the largest valid row -- the device form cannot see the rows; an env stores its row in the launch of its own last simulation and
 // idles afterwards.  All on `s`, in stream order, no host synchronisation.
-static int lookahead_tree(tbx_engine* e, const TbxEditArgs& a, const TbxTreeBounds* rows, double* out_dev, hipStream_t s)
+// tree_check holds the checks and answers the budget; tree_run cuts the ranges and launches.
+// TBX_QUERY_LOOKAHEAD_TREE_ACT goes through both (`act`, lookahead_tree_act below): the same checks, and the same range cut -- its
+// working trees have 2 * simulations + 1 nodes and its scratch budget is twice TBX_BEAM_SCRATCH_BYTES, so its env ranges are query
+// 160's -- with the rows into act->rows, tbx_tree_load_kernel in front of a range's first launch and tbx_tree_carry_kernel behind its
+// last, before the next range overwrites the scratch.
+static int tree_check(tbx_engine* e, const TbxEditArgs& a, const TbxTreeBounds* rows, TbxTreeBounds& b)
 {
-    const int L = tbx_legal_count(e->game);
     if (a.n < 1 || a.n > MAX_ARGS_TREE)
         return e->fail(TBX_E_INVALID, "tree takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, simulations, explore, salt]}");
-    TbxTreeBounds b{TBX_LOOKAHEAD_MAX_FRAMES, TBX_TREE_MAX_SIMULATIONS};      // per-env rows the host has not seen: the most a valid row can ask for
+    b = TbxTreeBounds{TBX_LOOKAHEAD_MAX_FRAMES, TBX_TREE_MAX_SIMULATIONS};      // per-env rows the host has not seen: the most a valid row can ask for
     if (!a.per_env) {
         const double dp = a.n > 2 ? a.v[2] : 1.0, sims = a.n > 9 ? a.v[9] : 1.0, explore = a.n > 10 ? a.v[10] : 0.0, salt = a.n > 11 ? a.v[11] : 0.0;
         if (int rc = shared_frames_hold(e, a)) return rc;
@@ -1598,15 +1703,23 @@ static int lookahead_tree(tbx_engine* e, const TbxEditArgs& a, const TbxTreeBoun
         b.simulations = TbxEditArgs::to_int(sims);
         if (int rc = shared_salt(e, "tree", salt, b.simulations)) return rc;
     } else if (rows) b = *rows;
-    const int stride = TbxTreeScratch::stride_for(b.simulations);
+    return TBX_OK;
+}
+
+static int tree_run(tbx_engine* e, const TbxEditArgs& a, const TbxTreeBounds& b, double* out_dev, hipStream_t s, const TbxTreeAct* act)
+{
+    const int L = tbx_legal_count(e->game);
+    const int stride = TbxTreeScratch::stride_for(act ? 2 * b.simulations : b.simulations);
     const size_t bytes_per_env = (size_t)L * TbxTreeScratch::unit_bytes(stride);
-    const long long step = tbx_range_step(e->n, TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH, (long long)L * b.frames, L, bytes_per_env, e->beam_range_envs);
+    const long long step = tbx_range_step(e->n, TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH, (long long)L * b.frames, L, bytes_per_env, e->beam_range_envs,
+                                          act ? 2 * TBX_BEAM_SCRATCH_BYTES : TBX_BEAM_SCRATCH_BYTES);
     EHIP(e->beam_scratch.reserve(bytes_per_env * (size_t)step, e->stream, s));
     TbxPlanLaunch l{};
     l.query = TBX_QUERY_LOOKAHEAD_TREE;
-    l.rows = out_dev;
+    l.rows = act ? act->rows : out_dev;
     l.tree.base = e->beam_scratch.p;
     l.tree.stride = stride;
+    l.tree.preloaded = act ? 1 : 0;
     int rc = TBX_OK;
     const int ranges = tbx_each_range(e->n, step, [&](int env0, int envs) {
         l.first_env = env0;
@@ -1615,16 +1728,31 @@ static int lookahead_tree(tbx_engine* e, const TbxEditArgs& a, const TbxTreeBoun
         if (e->tree_launch_simulations > 0 && per_launch > e->tree_launch_simulations) per_launch = e->tree_launch_simulations;
         if (per_launch > b.simulations) per_launch = b.simulations;
         if (per_launch < 1) per_launch = 1;
+        if (act && !rc) {
+            hipLaunchKernelGGL(tbx_tree_load_kernel, dim3((unsigned)(envs * L)), dim3(64), 0, s, *act, L, env0, l.tree);
+            if (hipGetLastError() != hipSuccess) rc = e->fail(TBX_E_NO_DEVICE, "tree act: the start-tree launch failed");
+        }
         for (int m0 = 0; !rc && m0 < b.simulations; m0 += (int)per_launch) {
             l.first_slot = m0;
             l.slots = (int)(b.simulations - m0 < per_launch ? b.simulations - m0 : per_launch);
             rc = e->ops->lookahead_play(e, a, l, s);
+        }
+        if (act && !rc) {
+            hipLaunchKernelGGL(tbx_tree_carry_kernel, dim3((unsigned)((envs + 63) / 64)), dim3(64), 0, s, *act, e->game, env0, envs, l.tree, out_dev);
+            if (hipGetLastError() != hipSuccess) rc = e->fail(TBX_E_NO_DEVICE, "tree act: the carry launch failed");
         }
     });
     if (rc) return rc;
     e->tree_ranges = ranges;
     EHIP(hipGetLastError());
     return TBX_OK;
+}
+
+static int lookahead_tree(tbx_engine* e, const TbxEditArgs& a, const TbxTreeBounds* rows, double* out_dev, hipStream_t s)
+{
+    TbxTreeBounds b;
+    if (int rc = tree_check(e, a, rows, b)) return rc;
+    return tree_run(e, a, b, out_dev, s, nullptr);
 }
 
 // chunks > 1: the sum of the partial rows parts[group][chunks][8] (64-bit integers; fields 2 / 3: the smallest / the largest) of
@@ -2055,6 +2183,77 @@ static int lookahead_act(tbx_engine* e, const TbxEditArgs& a, double* out_dev, h
     return TBX_OK;
 }
 
+// TBX_QUERY_LOOKAHEAD_TREE_ACT: {the tree's columns, reuse}.  tree_check refuses what query 160 refuses, before anything is launched
+// or allocated; then the buffers are made (the action buffer by act_alloc; the store where there is none or `simulations` changed
+// its size, zeroed; the flags once), liveness is decided on the host -- the key is host state, and calls are in order -- and
+// tree_run's kernels follow on `s`.  The key is written LAST, once everything is queued: a call that fails after the checks
+// leaves a key that matches nothing, so a half-written store is never live.  A call that allocates nothing does not synchronise.
+static int lookahead_tree_act(tbx_engine* e, const TbxEditArgs& a, double* out_dev, hipStream_t s)
+{
+    if (a.per_env) return e->fail(TBX_E_INVALID, "tree act takes shared arguments only");
+    if (a.n < 1 || a.n > MAX_ARGS_TREE + 1)
+        return e->fail(TBX_E_INVALID, "tree act takes {frames[, hold, depth, objective, rest, seed_lo, seed_hi, t, env_offset, simulations, explore, salt, reuse]}");
+    const double reuse = a.n > MAX_ARGS_TREE ? a.v[MAX_ARGS_TREE] : 0.0;
+    if (!(reuse == 0.0 || reuse == 1.0)) return e->fail(TBX_E_INVALID, "tree act: reuse must be 0 or 1");
+    TbxEditArgs b = a;
+    if (b.n > MAX_ARGS_TREE) b.n = MAX_ARGS_TREE;
+    TbxTreeBounds bounds;
+    if (int rc = tree_check(e, b, nullptr, bounds)) return rc;
+    const int L = tbx_legal_count(e->game);
+    if (int rc = act_alloc(e)) return rc;
+    const int key[5] = {TbxEditArgs::to_int(b.v[0]), b.n > 1 ? TbxEditArgs::to_int(b.v[1]) : 1, b.n > 2 ? TbxEditArgs::to_int(b.v[2]) : 1,
+                        b.n > 3 ? TbxEditArgs::to_int(b.v[3]) : 0, bounds.simulations};
+    const int store_stride = TbxTreeScratch::stride_for(bounds.simulations);
+    const size_t bytes = (size_t)e->n * L * TbxTreeScratch::unit_bytes(store_stride);
+    bool live = reuse == 1.0 && e->plan_tree;
+    for (int i = 0; i < 5; i++) live = live && key[i] == e->plan_tree_key[i];
+    e->plan_tree_key[4] = 0;                                  // until this call is queued whole, nothing in the store is live
+    if (!e->plan_tree_drop) {
+        EHIP(hipMalloc((void**)&e->plan_tree_drop, (size_t)e->n));
+        EHIP(hipMemsetAsync(e->plan_tree_drop, 0, (size_t)e->n, s));
+    }
+    if (!e->plan_tree || e->plan_tree_bytes != bytes) {
+        live = false;
+        EHIP(hipStreamSynchronize(e->stream));
+        EHIP(hipStreamSynchronize(s));
+        if (e->plan_tree) EHIP(hipFree(e->plan_tree));
+        e->plan_tree = nullptr;
+        e->plan_tree_bytes = 0;
+        EHIP(hipMalloc((void**)&e->plan_tree, bytes));
+        e->plan_tree_bytes = bytes;
+        EHIP(hipMemsetAsync(e->plan_tree, 0, bytes, s));
+    }
+    EHIP(e->act_scratch.reserve(sizeof(double) * (size_t)e->n * L * 12, e->stream, s));
+    TbxTreeAct act{};
+    act.store = e->plan_tree;
+    act.drop = e->plan_tree_drop;
+    act.action = e->plan_action;
+    act.rows = e->act_scratch.p;
+    act.store_stride = store_stride;
+    act.live = live ? 1 : 0;
+    act.keep = e->tree_carry_keep > 0 && e->tree_carry_keep < bounds.simulations + 1 ? e->tree_carry_keep : bounds.simulations + 1;
+    act.max_visits = e->tree_carry_max_visits > 0 ? e->tree_carry_max_visits : TBX_TREE_CARRY_MAX_VISITS;
+    act.objective = key[3];
+    if (int rc = tree_run(e, b, bounds, out_dev, s, &act)) return rc;
+    for (int i = 0; i < 5; i++) e->plan_tree_key[i] = key[i];
+    return TBX_OK;
+}
+
+// TBX_EDIT_TREE_DROP: the drop flag of every masked env (mask NULL: all), one thread per env
+__global__ __launch_bounds__(256) void tbx_tree_drop_kernel(const uint8_t* __restrict__ mask, int n, uint8_t* __restrict__ drop)
+{
+    const int env = blockIdx.x * 256 + threadIdx.x;
+    if (env < n && (!mask || mask[env])) drop[env] = 1;
+}
+static int tree_drop(tbx_engine* e, const TbxEditArgs& a, const uint8_t* mask_dev, hipStream_t s)
+{
+    if (a.n != 0) return e->fail(TBX_E_INVALID, "TBX_EDIT_TREE_DROP takes no arguments");
+    if (!e->plan_tree || !e->plan_tree_drop) return e->fail(TBX_E_INVALID, "TBX_QUERY_LOOKAHEAD_TREE_ACT has not been called");
+    hipLaunchKernelGGL(tbx_tree_drop_kernel, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, s, mask_dev, e->n, e->plan_tree_drop);
+    EHIP(hipGetLastError());
+    return TBX_OK;
+}
+
 // the queries every game has (the engine's own), else the game's.  rows_host: tbx_reduce has the per-env rows on the host, a.n doubles
 // an env -- queries 157, 158 and 160 then budget for the rows there are, not for the largest row there could be
 static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double* out_dev, int width, hipStream_t s, const double* rows_host = nullptr)
@@ -2097,6 +2296,7 @@ static int engine_reduce(tbx_engine* e, int query, const TbxEditArgs& a, double*
         return lookahead_tree(e, a, scanned ? &seen : nullptr, out_dev, s);
     }
     if (query == TBX_QUERY_LOOKAHEAD_ACT) return lookahead_act(e, a, out_dev, s);
+    if (query == TBX_QUERY_LOOKAHEAD_TREE_ACT) return lookahead_tree_act(e, a, out_dev, s);
     if (query != TBX_QUERY_CHECKPOINT_VALID) return e->ops->reduce(e, query, a, out_dev, width, s);
     return checkpoint_valid(e, a, out_dev, s);
 }
@@ -2113,6 +2313,7 @@ int tbx_edit_device(tbx_engine* e, int op, const double* args, int n_args, int p
     if (op == TBX_EDIT_CHECKPOINT_SLOTS) return e->fail(TBX_E_INVALID, "TBX_EDIT_CHECKPOINT_SLOTS has a host form only (tbx_edit)");
     if (op == TBX_EDIT_CHECKPOINT_SAVE || op == TBX_EDIT_CHECKPOINT_RESTORE)
         return checkpoint_copy(e, op == TBX_EDIT_CHECKPOINT_SAVE, a, mask_dev, false, (hipStream_t)stream);
+    if (op == TBX_EDIT_TREE_DROP) return tree_drop(e, a, mask_dev, (hipStream_t)stream);
     return e->ops->edit(e, op, a, mask_dev, (hipStream_t)stream);
 }
 
@@ -2139,6 +2340,7 @@ int tbx_edit(tbx_engine* e, int op, const double* args, int n_args, int per_env,
         m = e->mask;
     }
     if (op == TBX_EDIT_CHECKPOINT_SAVE || op == TBX_EDIT_CHECKPOINT_RESTORE) rc = checkpoint_copy(e, op == TBX_EDIT_CHECKPOINT_SAVE, a, m, true, e->stream);
+    else if (op == TBX_EDIT_TREE_DROP) rc = tree_drop(e, a, m, e->stream);
     else rc = op == TBX_EDIT_COPY_ENV ? fork_envs(e, a, m, fork_direct, e->stream) : e->ops->edit(e, op, a, m, e->stream);
     if (rc) return rc;
     EHIP(hipStreamSynchronize(e->stream));
@@ -2151,7 +2353,7 @@ int tbx_reduce_device(tbx_engine* e, int query, const double* args, int n_args, 
     const int width = tbx_reduce_width(e->game, query);
     if (width < 0) return e->fail(TBX_E_INVALID, "unknown query for this game");
     if (!out_dev) return e->fail(TBX_E_INVALID, "output pointer is NULL");
-    if (query == TBX_QUERY_LOOKAHEAD_ACT && per_env) return e->fail(TBX_E_INVALID, "act takes shared arguments only");
+    if ((query == TBX_QUERY_LOOKAHEAD_ACT || query == TBX_QUERY_LOOKAHEAD_TREE_ACT) && per_env) return e->fail(TBX_E_INVALID, "act takes shared arguments only");
     EHIP(hipSetDevice(e->device));
     EHIP(tbx_use_stream(e, (hipStream_t)stream));
     TbxEditArgs a;
@@ -2166,7 +2368,7 @@ int tbx_reduce(tbx_engine* e, int query, const double* args, int n_args, int per
     const int width = tbx_reduce_width(e->game, query);
     if (width < 0) return e->fail(TBX_E_INVALID, "unknown query for this game");
     if (!out_host) return e->fail(TBX_E_INVALID, "output pointer is NULL");
-    if (query == TBX_QUERY_LOOKAHEAD_ACT && per_env) return e->fail(TBX_E_INVALID, "act takes shared arguments only");
+    if ((query == TBX_QUERY_LOOKAHEAD_ACT || query == TBX_QUERY_LOOKAHEAD_TREE_ACT) && per_env) return e->fail(TBX_E_INVALID, "act takes shared arguments only");
     EHIP(hipSetDevice(e->device));
     EHIP(tbx_use_stream(e, e->stream));
     TbxEditArgs a;
@@ -2235,6 +2437,11 @@ int tbx_device_buffer(tbx_engine* e, int which, void** out_ptr, size_t* out_byte
         b = N * 4;
         break;
     }
+    case TBX_BUF_PLAN_TREE:
+        if (!e->plan_tree) return e->fail(TBX_E_INVALID, "TBX_QUERY_LOOKAHEAD_TREE_ACT has not been called");
+        p = e->plan_tree;
+        b = e->plan_tree_bytes;
+        break;
     default: return e->fail(TBX_E_INVALID, "unknown buffer id");
     }
     *out_ptr = p;
@@ -2258,6 +2465,12 @@ int tbx_set_option(tbx_engine* e, int option, int value)
     if (option == TBX_OPT_TREE_LAUNCH_SIMULATIONS) {   // read by the host when a tree's simulations are cut into launches: nothing in flight depends on it
         if (value < 0 || value > TBX_TREE_MAX_SIMULATIONS) return e->fail(TBX_E_INVALID, "option value out of range");
         e->tree_launch_simulations = value;
+        return TBX_OK;
+    }
+    if (option == TBX_OPT_TREE_CARRY_KEEP || option == TBX_OPT_TREE_CARRY_MAX_VISITS) {   // read by the host when a tree act is queued: nothing in flight depends on them
+        const bool keep = option == TBX_OPT_TREE_CARRY_KEEP;
+        if (value < 0 || value > (keep ? TBX_TREE_MAX_SIMULATIONS + 1 : TBX_TREE_CARRY_MAX_VISITS)) return e->fail(TBX_E_INVALID, "option value out of range");
+        (keep ? e->tree_carry_keep : e->tree_carry_max_visits) = value;
         return TBX_OK;
     }
     bool ok = false;
@@ -2302,6 +2515,8 @@ int tbx_get_option(tbx_engine* e, int option, int* value_out)
     if (value_out && option == TBX_OPT_EVOLVE_RANGES) { *value_out = e->evolve_ranges; return TBX_OK; }
     if (value_out && option == TBX_OPT_TREE_RANGES) { *value_out = e->tree_ranges; return TBX_OK; }
     if (value_out && option == TBX_OPT_TREE_LAUNCH_SIMULATIONS) { *value_out = e->tree_launch_simulations; return TBX_OK; }
+    if (value_out && option == TBX_OPT_TREE_CARRY_KEEP) { *value_out = e->tree_carry_keep; return TBX_OK; }
+    if (value_out && option == TBX_OPT_TREE_CARRY_MAX_VISITS) { *value_out = e->tree_carry_max_visits; return TBX_OK; }
     if (value_out && option == TBX_OPT_SEARCH_SAMPLES_LAUNCHES) { *value_out = e->search_samples_launches; return TBX_OK; }
     if (option < 0 || option >= TBX_OPT_COUNT || !value_out) return e->fail(TBX_E_INVALID, "unknown option");
     *value_out = e->opt[option];

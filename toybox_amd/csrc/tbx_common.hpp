@@ -453,7 +453,7 @@ struct tbx_engine {
     int sample_chunks = 0;          // chunks of the last TBX_QUERY_LOOKAHEAD_SAMPLES (0: none yet)
     TbxDevBuf<double> search_samples_parts;  // [N][n_legal][chunks][9] partial rows of TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES (64-bit integers)
     int search_samples_chunks = 0, search_samples_launches = 0;   // chunks and launches of the last TBX_QUERY_LOOKAHEAD_SEARCH_SAMPLES (0: none yet)
-    TbxDevBuf<uint8_t> beam_scratch;   // candidates and two beams of one env range of TBX_QUERY_LOOKAHEAD_BEAM (at most TBX_BEAM_SCRATCH_BYTES)
+    TbxDevBuf<uint8_t> beam_scratch;   // candidates and two beams of one env range of TBX_QUERY_LOOKAHEAD_BEAM (at most TBX_BEAM_SCRATCH_BYTES; twice that once query 161 has run)
     int beam_ranges = 0;               // env ranges of the last TBX_QUERY_LOOKAHEAD_BEAM (0: none yet)
     int beam_range_envs = 0;           // TBX_OPT_BEAM_RANGE_ENVS (0: the engine's choice)
     int beam_samples_ranges = 0, beam_samples_chunks = 0;   // env ranges, and the most sample chunks of a level, of the last TBX_QUERY_LOOKAHEAD_BEAM_SAMPLES (0: none yet)
@@ -461,6 +461,12 @@ struct tbx_engine {
     int evolve_ranges = 0;             // env ranges of the last TBX_QUERY_LOOKAHEAD_EVOLVE (0: none yet); its scratch is beam_scratch
     int tree_ranges = 0;               // env ranges of the last TBX_QUERY_LOOKAHEAD_TREE (0: none yet); its scratch is beam_scratch
     int tree_launch_simulations = 0;   // TBX_OPT_TREE_LAUNCH_SIMULATIONS (0: the engine's choice)
+    // TBX_QUERY_LOOKAHEAD_TREE_ACT: engine state, not env state -- made by the first accepted call (lookahead_tree_act, engine.hip)
+    uint8_t* plan_tree = nullptr;      // TBX_BUF_PLAN_TREE: [N][n_legal] unit blocks of TbxTreeScratch::unit_bytes(stride_for(plan_tree_key[4]))
+    size_t plan_tree_bytes = 0;
+    uint8_t* plan_tree_drop = nullptr; // [N] drop flags (TBX_EDIT_TREE_DROP)
+    int plan_tree_key[5] = {0, 0, 0, 0, 0};   // frames, hold, depth, objective, simulations of the call that wrote the store (simulations 0: no live content)
+    int tree_carry_keep = 0, tree_carry_max_visits = 0;   // TBX_OPT_TREE_CARRY_KEEP, TBX_OPT_TREE_CARRY_MAX_VISITS (0: the defaults)
     // TBX_QUERY_LOOKAHEAD_ACT: not env state -- made and zeroed on first use (act_alloc, engine.hip), never forked or checkpointed
     int32_t* plan_action = nullptr;    // [N] TBX_BUF_PLAN_ACTION: the ALE action of every env's winner
     uint32_t* plan_carry = nullptr;    // [N] TBX_BUF_PLAN_CARRY: the winner's code shifted by one period
@@ -902,17 +908,22 @@ inline int tbx_search_chunks(int n, int legal, long long suffixes, int lanes)
 // near half a second: profiles/search.md has the rate behind the number.
 constexpr long long TBX_SEARCH_LEAF_FRAMES_PER_LAUNCH = 1ll << 31;
 // One env range of a beam holds candidates plus two beams in engine-owned scratch; the ranges keep it under this, whatever N and
-// width are (a starting value: profiles/beam.md).
+// width are (a starting value: profiles/beam.md).  It is the budget of every planner query but TBX_QUERY_LOOKAHEAD_TREE_ACT, which
+// asks tbx_range_step for TWICE this (its working trees are twice as long as query 160's, and its ranges must not be smaller: a
+// second, nearly empty range costs a whole range again).  beam_scratch only grows: an engine that has run that query keeps up to
+// 512 MiB for every later planner query, until tbx_destroy.
 constexpr size_t TBX_BEAM_SCRATCH_BYTES = 256ull << 20;
 // How every planner query cuts its n envs into ranges, the one copy of the rule: the envs of a range stay under `budget`
 // leaf-frames (leaf_frames_per_env: leaves x frames of one env; per-env rows: the largest a valid row can ask for) and under
 // TBX_LOOKAHEAD_PAIRS_PER_LAUNCH units, where the range keeps scratch (bytes_per_env > 0) under TBX_BEAM_SCRATCH_BYTES, and where
-// TBX_OPT_BEAM_RANGE_ENVS is set (range_envs > 0) under that; at most n, at least 1.
-inline long long tbx_range_step(int n, long long budget, long long leaf_frames_per_env, long long units_per_env, size_t bytes_per_env = 0, int range_envs = 0)
+// TBX_OPT_BEAM_RANGE_ENVS is set (range_envs > 0) under that; at most n, at least 1.  scratch_bytes: the scratch budget where it is
+// not TBX_BEAM_SCRATCH_BYTES (TBX_QUERY_LOOKAHEAD_TREE_ACT: twice that for trees twice as long, so that its ranges are query 160's).
+inline long long tbx_range_step(int n, long long budget, long long leaf_frames_per_env, long long units_per_env, size_t bytes_per_env = 0, int range_envs = 0,
+                                size_t scratch_bytes = TBX_BEAM_SCRATCH_BYTES)
 {
     long long step = budget / leaf_frames_per_env;
     if (step > TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env) step = TBX_LOOKAHEAD_PAIRS_PER_LAUNCH / units_per_env;
-    if (bytes_per_env > 0 && step > (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env)) step = (long long)(TBX_BEAM_SCRATCH_BYTES / bytes_per_env);
+    if (bytes_per_env > 0 && step > (long long)(scratch_bytes / bytes_per_env)) step = (long long)(scratch_bytes / bytes_per_env);
     if (range_envs > 0 && step > range_envs) step = range_envs;
     if (step > n) step = n;
     if (step < 1) step = 1;
@@ -1494,13 +1505,18 @@ static_assert(sizeof(TbxTreeNode) == 32, "two nodes a 64-byte line");
 struct TbxTreeScratch {
     uint8_t* base;
     int stride;
+    int preloaded;      // TBX_QUERY_LOOKAHEAD_TREE_ACT: the start trees are in place (tbx_tree_load_kernel, engine.hip); the launch with m0 = 0 makes none
     __host__ __device__ static size_t unit_bytes(int stride) { return 64 + (size_t)stride * sizeof(TbxTreeNode); }
     __host__ __device__ static int stride_for(int simulations) { return (simulations + 2) & ~1; }       // simulations + 1 nodes, rounded up to even
     __device__ __forceinline__ long long* sums(int unit) const { return reinterpret_cast<long long*>(base + (size_t)unit * unit_bytes(stride)); }
     __device__ __forceinline__ TbxTreeNode* nodes(int unit) const { return reinterpret_cast<TbxTreeNode*>(base + (size_t)unit * unit_bytes(stride) + 64); }
 };
-// the exact floor square root of x < 2^27: the double square root, corrected by one step
-__device__ __forceinline__ long long tbx_isqrt(long long x)
+// The exact floor square root of 0 <= x < 2^52.  Such an x is a double, and its double square root is correctly rounded (IEEE 754):
+// within half a unit in the last place of the real root, far less than 1 at these sizes.  So the truncated r is at most one off the
+// floor root -- one above where the rounding went up across an integer -- and the one correction step below repairs an r that is
+// off by one in either direction.  The result is therefore exact far beyond the tree's largest argument, n << 16 with n <= 5120
+// (TBX_QUERY_LOOKAHEAD_TREE_ACT: below 2^29); r * r stays far inside 64 bits.
+__host__ __device__ __forceinline__ long long tbx_isqrt(long long x)
 {
     long long r = (long long)sqrt((double)x);
     if (r * r > x) r--;
@@ -1589,8 +1605,8 @@ __device__ __forceinline__ void tbx_tree_store_pv(const TbxTreeNode* nd, int can
 // tbx_lookahead_kernel.  It runs the simulations m0 .. m1-1 of its tree (its own row may have fewer) one after the other -- select,
 // play through the opaque env index (reload, salt: the loop of tbx_sample_kernel), back up, add to the root's sums -- with the tree
 // and the sums in scratch from launch to launch: the launch with m0 = 0 makes the empty tree, the one that holds the row's last
-// simulation stores the row.  Wave forms: lane 0 walks and updates the tree, depth and code are broadcast before the play.  A
-// refused row answers zeros at m0 = 0.
+// simulation stores the row (sc.preloaded: the start trees are there already, only the sums are zeroed).  Wave forms: lane 0 walks
+// and updates the tree, depth and code are broadcast before the play.  A refused row answers zeros at m0 = 0.
 template <class G>
 __global__ __launch_bounds__(G::BLOCK) void tbx_tree_kernel(G g, TbxEditArgs a, int m0, int m1, int first_env, int count, TbxTreeScratch sc, double* __restrict__ out)
 {
@@ -1624,9 +1640,11 @@ __global__ __launch_bounds__(G::BLOCK) void tbx_tree_kernel(G g, TbxEditArgs a, 
     TbxTreeNode* const nd = sc.nodes(rel);
     if (writer && m0 == 0) {
         for (int i = 0; i < 8; i++) sums[i] = 0;
-        TbxTreeNode root{};
-        root.nodes = 1;
-        nd[0] = root;
+        if (!sc.preloaded) {
+            TbxTreeNode root{};
+            root.nodes = 1;
+            nd[0] = root;
+        }
     }
     for (int m = m0; m < last; m++) {
         int d = 1;

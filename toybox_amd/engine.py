@@ -515,6 +515,88 @@ def tree_args(game, n_envs, frames, depth, simulations=1, explore=0, salt=0, hol
     return args, True
 
 
+TREE_ACT_WIDTH = 14
+
+
+def tree_act_args(game, frames, depth, simulations=1, explore=0, salt=0, reuse=False, hold=1, objective=0, rest=None, seed=0, t=0, env_offset=0):
+    """The shared argument row of TBX_QUERY_LOOKAHEAD_TREE_ACT: tree_args' twelve columns, range-checked there, then reuse (False / 0
+    or True / 1: start from the carried trees where they are live).  The query takes shared arguments only, so there is no
+    n_envs and a per-env value raises ValueError."""
+    if isinstance(reuse, (bool, np.bool_)):
+        reuse = int(reuse)
+    if np.ndim(reuse) or reuse not in (0, 1):
+        raise ValueError("tree act reuse is False / 0 or True / 1, got %r" % (reuse,))
+    args, per_env = tree_args(game, 1, frames, depth, simulations, explore, salt, hold, objective, rest, seed, t, env_offset)
+    if per_env:
+        raise ValueError("tree act takes shared arguments only, got a per-env value")
+    return [float(v) for v in args] + [float(int(reuse))]
+
+
+def tree_carry(game, nodes, a_star, simulations, keep=None, max_visits=None):
+    """The carry of TBX_QUERY_LOOKAHEAD_TREE_ACT in plain Python.  nodes: the L = n_legal(game) final trees of one env, each a list
+    of (n, v_sum, child) in creation order with child a sequence of L links (0 or None: no child); a_star: the picked action
+    index.  Returns the L carried trees in the same form with 0 for a missing link, an empty list where the root of tree a_star has
+    no child k: the subtree under child k, its nodes in ascending source id, the first `keep` (None / 0: simulations + 1; more
+    than that counts as that) kept and renumbered in that order, links to nodes that were not kept cut, and -- where the new
+    root's n exceeds max_visits (None / 0: TREE_CARRY_MAX_VISITS) -- n = (n + 1) // 2 and v_sum = v_sum // 2 in every kept node."""
+    L = len(_abi.LEGAL_ACTIONS[_game_name(game)])
+    if not 1 <= int(simulations) <= _abi.TREE_MAX_SIMULATIONS:
+        raise ValueError("tree simulations must be 1 .. %d, got %r" % (_abi.TREE_MAX_SIMULATIONS, simulations))
+    most = int(simulations) + 1
+    keep = most if not keep else int(keep)
+    if not 1 <= keep <= _abi.TREE_MAX_SIMULATIONS + 1:
+        raise ValueError("tree carry keep must be 1 .. %d, got %r" % (_abi.TREE_MAX_SIMULATIONS + 1, keep))
+    keep = min(keep, most)
+    max_visits = _abi.TREE_CARRY_MAX_VISITS if not max_visits else int(max_visits)
+    if not 1 <= max_visits <= _abi.TREE_CARRY_MAX_VISITS:
+        raise ValueError("tree carry max_visits must be 1 .. %d, got %r" % (_abi.TREE_CARRY_MAX_VISITS, max_visits))
+    if len(nodes) != L or not 0 <= int(a_star) < L:
+        raise ValueError("tree carry takes %d trees and a_star 0 .. %d" % (L, L - 1))
+    src = nodes[int(a_star)]
+    owner = {}                                        # source id -> (tree k, the parent's new id or None, digit)
+    out = [[] for _ in range(L)]
+    halved = [False] * L
+    for k in range(L):
+        if src[0][2][k]:
+            owner[int(src[0][2][k])] = (k, None, k)
+    for i in range(1, len(src)):
+        if i not in owner:
+            continue
+        k, parent, digit = owner[i]
+        if len(out[k]) >= keep:
+            continue
+        n, v_sum, child = src[i]
+        new = len(out[k])
+        if parent is None:
+            halved[k] = int(n) > max_visits
+        else:
+            out[k][parent][2][digit] = new
+        out[k].append([(int(n) + 1) // 2 if halved[k] else int(n), int(v_sum) // 2 if halved[k] else int(v_sum), [0] * L])
+        for j in range(L):
+            if child[j]:
+                owner[int(child[j])] = (k, new, j)
+    return [[(n, v, tuple(c)) for n, v, c in tree] for tree in out]
+
+
+def tree_store_units(game, raw, n_envs, simulations):
+    """The bytes of BUF_PLAN_TREE (a uint8 array) as carried trees: units[env][k] a list of (n, v_sum, child) with child a tuple of
+    n_legal links, empty where tree (env, k) is absent -- tree_carry's form.  Layout: include/toybox_amd.h."""
+    L = len(_abi.LEGAL_ACTIONS[_game_name(game)])
+    stride = (int(simulations) + 2) & ~1
+    block = 64 + 32 * stride
+    raw = np.ascontiguousarray(raw, np.uint8).reshape(int(n_envs), L, block)
+    node = np.dtype([("v_sum", "<i8"), ("n", "<u4"), ("child", "<u2", (6,)), ("nodes", "<u4"), ("pad", "<u4")])
+    units = []
+    for e in range(int(n_envs)):
+        row = []
+        for k in range(L):
+            count = int(raw[e, k, :4].view("<u4")[0])
+            recs = raw[e, k, 64:64 + 32 * count].view(node)
+            row.append([(int(r["n"]), int(r["v_sum"]), tuple(int(c) for c in r["child"][:L])) for r in recs])
+        units.append(row)
+    return units
+
+
 class Engine:
     def __init__(self, game, n_envs=1, device=0, config=None, lib=None):
         self._lib = lib if lib is not None else load()
@@ -876,6 +958,47 @@ class Engine:
     @tree_launch_simulations.setter
     def tree_launch_simulations(self, simulations):
         self.set_option(_abi.OPT_TREE_LAUNCH_SIMULATIONS, simulations)
+
+    def lookahead_tree_act(self, frames, depth, simulations, explore=0, salt=0, reuse=False, hold=1, objective="return", rest=None, seed=0, t=0, env_offset=0):
+        """TBX_QUERY_LOOKAHEAD_TREE_ACT: lookahead_tree with every env's winner picked on the device (plan_pick's sampled rule on
+        the root sums) and the subtree under the winner kept in BUF_PLAN_TREE (tree_carry's rule); reuse=True starts the trees
+        from what the last call kept, where the call's frames, hold, depth, objective and simulations are the same and tree_drop
+        has not named the env.  Returns a dict of [N] arrays: action (the ALE id, also left in BUF_PLAN_ACTION for step_device /
+        agent_step_device), action_index and the winner's TREE_FIELDS (samples = simulations; pv_visits counts carried visits
+        too).  Nothing else in the engine is written."""
+        args = tree_act_args(self.game, frames, depth, simulations, explore, salt, reuse, hold, objective, rest, seed, t, env_offset)
+        return self._tree_act_dict(self.reduce(_abi.QUERY_LOOKAHEAD_TREE_ACT, args))
+
+    def lookahead_tree_act_device(self, out_ptr, frames, depth, simulations, stream=0, **keywords):
+        """lookahead_tree_act, asynchronous on `stream`: rows float64[N][14] = {action, action_index, the winner's tree row} into
+        the device buffer at out_ptr; a step_device(plan_action_ptr, stream=stream) queued behind it reads the finished actions"""
+        self.reduce_device(_abi.QUERY_LOOKAHEAD_TREE_ACT, out_ptr, tree_act_args(self.game, frames, depth, simulations, **keywords), stream=stream)
+
+    def _tree_act_dict(self, out):
+        out = np.asarray(out).reshape(self.n_envs, TREE_ACT_WIDTH)
+        res = {"action": out[:, 0].astype(np.int64), "action_index": out[:, 1].astype(np.int64)}
+        res.update({k: out[:, 2 + i].astype(np.uint64 if k == "code" else np.int64) for i, k in enumerate(TREE_FIELDS)})
+        return res
+
+    def tree_drop(self, mask=None):
+        """TBX_EDIT_TREE_DROP, the host form: the carried trees of the masked envs (a bool array [N]; None: all) are dead for the
+        next lookahead_tree_act.  Raises ToyboxAmdError(E_INVALID) before the first lookahead_tree_act."""
+        self.edit(_abi.EDIT_TREE_DROP, (), mask)
+
+    def tree_drop_device(self, mask_ptr=0, stream=0):
+        """TBX_EDIT_TREE_DROP, asynchronous on `stream`: mask_ptr = device address of uint8[N] (0: every env) -- a step's done
+        buffer, so that a queued loop forgets the trees of games that ended"""
+        self.edit_device(_abi.EDIT_TREE_DROP, (), mask_ptr=mask_ptr, stream=stream)
+
+    def plan_trees(self, simulations):
+        """BUF_PLAN_TREE on the host after everything queued has finished, as tree_store_units gives it: [env][k] lists of
+        (n, v_sum, child).  simulations: that of the call that wrote the store."""
+        from . import hip
+        ptr, nbytes = self.device_buffer(_abi.BUF_PLAN_TREE)
+        raw = np.empty(nbytes, np.uint8)
+        self.sync()
+        hip.memcpy_dtoh(raw, ptr, nbytes)
+        return tree_store_units(self.game, raw, self.n_envs, simulations)
 
     def lookahead_act(self, planner, **planner_keywords):
         """TBX_QUERY_LOOKAHEAD_ACT: the planner's query (a name of ACT_PLANNERS or its id; keywords as act_args takes them) with

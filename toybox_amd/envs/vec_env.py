@@ -210,7 +210,8 @@ def _tree(env, frames, hold, depth, simulations, explore, objective, rest, seed,
 
 class _PlanLoop:
     """What plan_step / plan_rollout of an adapter keep on the device: a stream of their own, the rows of the last rollout's
-    TBX_QUERY_LOOKAHEAD_ACT calls [k][N][11] and its per-step rewards and dones, copied device-to-device behind every step"""
+    TBX_QUERY_LOOKAHEAD_ACT calls [k][N][11] (planner "tree": TBX_QUERY_LOOKAHEAD_TREE_ACT, [k][N][14]) and its per-step rewards and
+    dones, copied device-to-device behind every step"""
 
     def __init__(self, env):
         from .. import hip
@@ -249,31 +250,51 @@ class _PlanLoop:
                 kw["init"] = "carry" if self.planned else -1
         return pid, act_args(self.env.game, pid, frames=frames, hold=hold, depth=int(depth), objective=objective, rest=_ale(self.env, rest), seed=seed, t=t, **kw)
 
-    def run(self, k, planner, frames, hold, depth, objective, rest, seed, t, kw, step, reward_id, reward_bytes, done_id, sub):
+    def tree_args(self, frames, hold, depth, objective, rest, seed, t, kw):
+        """planner "tree": the row of TBX_QUERY_LOOKAHEAD_TREE_ACT; keywords simulations (default 16), explore, salt, reuse (default True)"""
+        from ..engine import tree_act_args
+        kw = dict(kw)
+        row = tree_act_args(self.env.game, frames, int(depth), kw.pop("simulations", 16), kw.pop("explore", 0), kw.pop("salt", 0), kw.pop("reuse", True), hold=hold,
+                            objective=objective, rest=_ale(self.env, rest), seed=seed, t=t)
+        if kw:
+            raise TypeError("planner 'tree' takes simulations, explore, salt and reuse, got %r" % (sorted(kw),))
+        return row
+
+    def run(self, k, planner, frames, hold, depth, objective, rest, seed, t, kw, step, reward_id, reward_bytes, done_id, sub, drop_id=None):
         """k periods queued back to back on the stream: the query, then step(action pointer, stream) `sub` times, the reward and
-        done buffers copied behind each; ONE synchronisation at the end.  -> (reward [k, sub, N], done [k, sub, N])"""
+        done buffers copied behind each; ONE synchronisation at the end.  -> (reward [k, sub, N], done [k, sub, N]).  Planner
+        "tree" with reuse: TBX_EDIT_TREE_DROP is queued behind every step with the buffer drop_id as its mask -- the carried trees
+        of a game that ended do not steer the new one."""
         env, eng, hip, n = self.env, self.env.engine, self.hip, self.env.num_envs
-        rows = self.buf("rows", 8 * 11 * n * k)
+        tree = planner == "tree" or planner == _abi.QUERY_LOOKAHEAD_TREE_ACT
+        width = 14 if tree else 11
+        rows = self.buf("rows", 8 * width * n * k)
         rew, don = self.buf("reward", reward_bytes * n * k * sub), self.buf("done", n * k * sub)
         for i in range(k):
-            pid, args = self.args(planner, frames, hold, depth, objective, rest, seed, int(t) + i, kw)
-            eng.reduce_device(_abi.QUERY_LOOKAHEAD_ACT, rows + 8 * 11 * n * i, args, stream=self.stream.ptr)
-            self.planned = True
+            if tree:
+                pid, args = _abi.QUERY_LOOKAHEAD_TREE_ACT, self.tree_args(frames, hold, depth, objective, rest, seed, int(t) + i, kw)
+                eng.reduce_device(pid, rows + 8 * width * n * i, args, stream=self.stream.ptr)
+            else:
+                pid, args = self.args(planner, frames, hold, depth, objective, rest, seed, int(t) + i, kw)
+                eng.reduce_device(_abi.QUERY_LOOKAHEAD_ACT, rows + 8 * 11 * n * i, args, stream=self.stream.ptr)
+                self.planned = True
             action = eng.plan_action_ptr                 # (made by the engine's first such query; its address stays)
             for j in range(sub):
                 step(action, self.stream.ptr)
                 at = i * sub + j
                 hip.memcpy_dtod_async(rew + reward_bytes * n * at, eng.device_buffer(reward_id)[0], reward_bytes * n, self.stream)
                 hip.memcpy_dtod_async(don + n * at, eng.device_buffer(done_id)[0], n, self.stream)
+                if tree and args[12]:
+                    eng.edit_device(_abi.EDIT_TREE_DROP, (), mask_ptr=eng.device_buffer(drop_id)[0], stream=self.stream.ptr)
         self.stream.synchronize()
-        self.rows = (k, pid)
+        self.rows = (k, pid, width)
         return self.host("reward", (k, sub, n), np.float32 if reward_id == _abi.BUF_AGENT_REWARD else np.int32), self.host("done", (k, sub, n), np.uint8)
 
     def actions(self):
         if self.rows is None:
             raise RuntimeError("plan_actions before the first plan_step / plan_rollout")
-        k, _ = self.rows
-        return self.host("rows", (k, self.env.num_envs, 11), np.float64)[..., 1].astype(np.int64)
+        k, _, width = self.rows
+        return self.host("rows", (k, self.env.num_envs, width), np.float64)[..., 1].astype(np.int64)
 
     def close(self):
         self.stream.synchronize()
@@ -509,7 +530,9 @@ class ToyboxVecEnv:
     def plan_rollout(self, k, planner="evolve", steps=16, depth=4, hold=1, objective="return", rest=None, seed=0, t=0, **planner_keywords):
         """k closed-loop steps queued back to back on a stream of the env's own, no host synchronisation in between
         (Engine.lookahead_act_device): per step the planner ("search", "search_samples", "beam", "beam_samples" or "evolve";
-        planner_keywords: width, samples, salt, population, generations, elite, mutation, plan_seed, init) looks `steps` steps of
+        planner_keywords: width, samples, salt, population, generations, elite, mutation, plan_seed, init; or "tree", the tree
+        search through Engine.lookahead_tree_act_device with simulations, explore, salt and reuse=True: the subtree under the
+        played action starts the next step's trees, and the trees of envs whose game ended are dropped on the device) looks `steps` steps of
         `hold` frames each ahead with plans of `depth` steps, every env's winner is picked on the device, and its first action is
         played for `hold` frames with auto-reset, read by the step from the device buffer the pick wrote.  Step i plans with
         counter t + i, so drawn `rest` actions line up across calls.  The evolution (default population 16, generations 2) is
@@ -525,7 +548,7 @@ class ToyboxVecEnv:
             self._plan = _PlanLoop(self)
         eng = self.engine
         reward, done = self._plan.run(int(k), planner, int(steps) * int(hold), int(hold), depth, objective, rest, seed, t, planner_keywords,
-                                      lambda action, stream: eng.step_device(action, auto_reset=True, stream=stream), _abi.BUF_REWARD, 4, _abi.BUF_DONE, int(hold))
+                                      lambda action, stream: eng.step_device(action, auto_reset=True, stream=stream), _abi.BUF_REWARD, 4, _abi.BUF_DONE, int(hold), _abi.BUF_DONE)
         lives, score = np.empty(self.num_envs, np.int32), np.empty(self.num_envs, np.int32)
         self._plan.hip.memcpy_dtoh(lives, eng.device_buffer(_abi.BUF_LIVES)[0], lives.nbytes)
         self._plan.hip.memcpy_dtoh(score, eng.device_buffer(_abi.BUF_SCORE)[0], score.nbytes)
@@ -932,7 +955,8 @@ class ToyboxPreprocVecEnv:
         return _tree(self, int(steps) * self._skip, self._skip, depth, simulations, explore, objective, rest, seed, t, salt)
 
     def plan_rollout(self, k, planner="evolve", steps=16, depth=4, objective="return", rest=None, seed=0, t=0, **planner_keywords):
-        """ToyboxVecEnv.plan_rollout in agent steps: per step the planner looks steps x skip raw frames ahead with hold = skip
+        """ToyboxVecEnv.plan_rollout in agent steps (planner "tree" included: simulations, explore, salt, reuse; the trees of envs
+        whose EPISODE ended -- a game over, not a lost life -- are dropped): per step the planner looks steps x skip raw frames ahead with hold = skip
         (on the engine pass hold = skip yourself: Engine.lookahead_act_device plans in raw frames) and ONE agent step
         (tbx_agent_step_device) plays the winner's first action, read from the device buffer the pick wrote; raw frames, no
         wrapper in the plan, as in lookahead().  k > 1 needs obs_layout="device_stack" (the host-side stacks of the other layouts
@@ -948,7 +972,7 @@ class ToyboxPreprocVecEnv:
             self._plan = _PlanLoop(self)
         eng = self.engine
         reward, done = self._plan.run(int(k), planner, int(steps) * self._skip, self._skip, depth, objective, rest, seed, t, planner_keywords,
-                                      lambda action, stream: eng.agent_step_device(action, stream=stream), _abi.BUF_AGENT_REWARD, 4, _abi.BUF_AGENT_DONE, 1)
+                                      lambda action, stream: eng.agent_step_device(action, stream=stream), _abi.BUF_AGENT_REWARD, 4, _abi.BUF_AGENT_DONE, 1, _abi.BUF_AGENT_EP_DONE)
         landed, key = self._landing()
         st = self._st
         eng.agent_fetch(ep_done=st["ep_done"], ep_return=st["ep_return"], ep_length=st["ep_length"], **{key: landed})
