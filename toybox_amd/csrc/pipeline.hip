@@ -183,6 +183,11 @@ static int pipe_enter(tbx_engine* e, PipeKind kind)
     if (kind == PIPE_ROLLOUT_CHUNKS) EHIP(tbx_wait_tail(e, p.step_lane));
     p.books = PipeBooks{};
     p.books.kind = kind;
+    // The caller may have queued readers of the current results before this call: it took their addresses while no form was running
+    // (after tbx_sync, or behind a call of another kind), where pipe_reader_joins sees nothing, and after tbx_sync the lanes do not
+    // go behind the caller's stream either.  So the first call of a stay fences that stream like a call that saw a reader -- one
+    // event record per entry -- and the second call, which rewrites that output set and frame buffer, waits for the fence.
+    p.books.reader_seen = true;
     e->pipe_active = true;
     return TBX_OK;
 }
