@@ -496,7 +496,15 @@ int tbx_set_states(tbx_engine* engine, int first_env, int count, const void* pod
 /* Batch-wide config record (tbx_<game>_config_t).  `rand` is env 0's simulator RNG on get.  On set, a `rand` equal to
  * env 0's current simulator RNG (i.e. the caller did not edit it) leaves every env's simulator RNG untouched -- a config
  * edit must not put a seeded batch onto one random stream; any other value is written to every env.  For a one-env engine
- * both cases coincide with the reference.  Does not start a new game.
+ * both cases coincide with the reference.  Does not start a new game: what a running game holds in its state record stays as it is
+ * until that env's next game -- Breakout's bricks keep the colour and the points they were made with, GridWorld's tiles and player
+ * theirs -- while the colours only the config holds (Breakout bg / frame / paddle / ball, Amidar's six) change with the next picture.
+ * A Breakout config with other rows, row scores or row colours takes a running device engine to its per-env brick tables, as a
+ * written non-canonical brick does: every result stays the reference's, at the wave-per-env step's and the generic observation
+ * path's rates, and -- as on any engine with written bricks -- the agent layer's episodic-life / fire-reset / no-op-reset wrappers
+ * are not available there: tbx_agent_step* and tbx_agent_reset return TBX_E_UNSUPPORTED and change nothing.  A tbx_new_game for
+ * every env (mask NULL; write_config_json + new_game, the reference's way to another wall) brings the engine back to the
+ * canonical wall, with or without an agent layer.
  * replaces Toybox.config_to_json / write_config_json (interventions/base.py:390,402). */
 int tbx_get_config(tbx_engine* engine, void* pod_out, size_t size);
 int tbx_set_config(tbx_engine* engine, const void* pod, size_t size);

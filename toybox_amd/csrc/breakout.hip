@@ -1926,6 +1926,7 @@ struct BreakoutOps : GameOps {
     BrkCfg c{};
     tbx_breakout_config_t cfg{};
     bool custom = false;
+    bool wall_switched = false;     // custom only because tbx_set_config changed the wall under running games (set_config, new_game)
     TbxRecordSet<BrkRenderRec> recs;   // fused launches rotate through three (render_step): a launch overlapped on the other lane must not
                                        // rewrite what this launch's rasteriser blocks still read
     BrkCfg* cfg_dev = nullptr;      // device copy of `c` for kernels that index the tables per thread
@@ -1937,12 +1938,19 @@ struct BreakoutOps : GameOps {
     size_t state_size() const override { return sizeof(tbx_breakout_state_t); }
     size_t config_size() const override { return sizeof(tbx_breakout_config_t); }
 
-    int load_cfg(tbx_engine* e, const tbx_breakout_config_t& k)
+    static int check_cfg(tbx_engine* e, const tbx_breakout_config_t& k)
     {
         if (k.n_rows < 1 || k.n_rows > TBX_BRK_MAX_ROWS) return e->fail(TBX_E_UNSUPPORTED, "breakout: n_rows must be 1..14");
         if (k.n_starts < 1 || k.n_starts > TBX_BRK_MAX_STARTS) return e->fail(TBX_E_UNSUPPORTED, "breakout: 1..8 ball_start_positions");
         if (k.paddle_discrete_segments < 1 || k.paddle_discrete_segments > TBX_BRK_MAX_SEGMENTS)
             return e->fail(TBX_E_UNSUPPORTED, "breakout: paddle_discrete_segments must be 1..16 (continuous bounce needs device trig)");
+        return TBX_OK;
+    }
+
+    int load_cfg(tbx_engine* e, const tbx_breakout_config_t& k)
+    {
+        int rc = check_cfg(e, k);
+        if (rc) return rc;
         cfg = k;
         c.start_lives = k.start_lives; c.n_rows = k.n_rows; c.ball_speed_row_depth = k.ball_speed_row_depth;
         c.n_starts = k.n_starts; c.segments = k.paddle_discrete_segments;
@@ -1991,11 +1999,31 @@ struct BreakoutOps : GameOps {
     {
         tbx_breakout_config_t k;
         memcpy(&k, pod, sizeof k);
+        int rc = check_cfg(e, k);
+        if (rc) return rc;
+        // The bricks of a running game are state: they keep the colour and the points they were made with until their env's next
+        // game (tbx_set_config starts none).  The canonical kernels derive both from the config, so a config with another wall
+        // ends that mode first: every env's table is filled from the OLD config, and new games build theirs from the new one.
+        bool same_wall = k.n_rows == cfg.n_rows;
+        for (int i = 0; same_wall && i < k.n_rows; i++)
+            same_wall = k.row_scores[i] == cfg.row_scores[i] && pack_color(k.row_colors[i]) == pack_color(cfg.row_colors[i]);
+        if (!custom && !same_wall) {
+            rc = enable_custom(e, e->stream);
+            if (rc) return rc;
+            TBX_HIP(hipStreamSynchronize(e->stream));
+            recs.valid = false;
+            wall_switched = true;
+        }
         return load_cfg(e, k);
     }
 
     int new_game(tbx_engine* e, const uint8_t* mask_dev, hipStream_t s) override
     {
+        // write_config_json + new_game, the reference's way to another wall: a new game for EVERY env builds every wall from the
+        // config in force, so an engine that left the canonical mode for a config switch alone is canonical again -- under an
+        // agent layer too, whose fused path takes over at the next step (its record slots are the generic path's).  The tables
+        // stay allocated for the next switch.
+        if (custom && wall_switched && !mask_dev) custom = wall_switched = false;
         tbx_dispatch<0, 1>(custom, [&](auto cu) { hipLaunchKernelGGL(brk_new_game_kernel<decltype(cu)::value != 0>, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c, mask_dev); });
         TBX_HIP(hipGetLastError());
         recs.valid = false;
@@ -2327,7 +2355,7 @@ struct BreakoutOps : GameOps {
     int enable_custom(tbx_engine* e, hipStream_t s)
     {
         if (custom) return TBX_OK;
-        TBX_HIP(tbx_alloc_arrays(d, (size_t)e->n, true));      // d.custom
+        if (!d.custom) TBX_HIP(tbx_alloc_arrays(d, (size_t)e->n, true));      // d.custom (new_game keeps it when a config-switched engine returns)
         hipLaunchKernelGGL(brk_fill_custom_kernel, grid_for(e->n), dim3(TBX_BLOCK), 0, s, d, c);
         TBX_HIP(hipGetLastError());
         custom = true;
@@ -2345,6 +2373,7 @@ struct BreakoutOps : GameOps {
             if (st.n_bricks < 0 || st.n_bricks > TBX_BRK_MAX_BRICKS)
                 return e->fail(TBX_E_UNSUPPORTED, "breakout: the device engine holds at most 256 bricks per env");
             if (!custom && all_canonical && !is_canonical(st)) all_canonical = false;
+            if (wall_switched && !is_canonical(st)) wall_switched = false;      // a written table: custom for good
         }
         if (!custom && !all_canonical) {
             int rc = enable_custom(e, s);
