@@ -10,6 +10,9 @@ where a kernel can be wrong with the suite green.  measure() says which branches
   tests/test_gpu_rule_edges.py),
 * runs gcov -b (JSON) and returns, per source file and function, the lines never executed and the (line, branch) pairs never taken.
 
+The scope is whole rule files (minus OUT_OF_SCOPE), or a set of functions of any file of the oracle: tests/test_wrapper_reach.py holds the
+agent wrapper functions of orc_abi.c that way.
+
 The child runs with TBX_ORACLE_THREADS=1: the counters are plain increments, and a racing pair of increments must not be what decides
 between "taken once" and "never"."""
 import gzip
@@ -79,9 +82,17 @@ def _child():
         getattr(importlib.import_module(module), function)(lib)
 
 
-def report(workdir, files):
+def in_scope(scope, f, function):
+    """scope None: every function of the file but OUT_OF_SCOPE's; else {file: names}: those functions alone.  A name also stands for the
+    bodies gcc outlines from it (an OpenMP loop of tbx_agent_reset is reported as tbx_agent_reset._omp_fn.0)"""
+    if scope is None:
+        return function not in OUT_OF_SCOPE.get(f, set())
+    return function.split("._omp_fn.")[0] in scope.get(f, ())
+
+
+def report(workdir, files, scope=None):
     """gcov -b over the counters in workdir -> {file: {function: {"lines": n, "branches": n, "unexecuted": [line], "untaken": [(line, k)]}}}
-    plus, under the key (file, "text"), the file's lines (1-based list index - 1) for allow-lists that go by line text"""
+    plus, under the key (file, "text"), the file's lines (1-based list index - 1) for allow-lists that go by line text.  scope: in_scope"""
     out = {}
     for f in files:
         stem = f[:-2]
@@ -89,8 +100,7 @@ def report(workdir, files):
         with gzip.open(os.path.join(workdir, stem + ".gcov.json.gz"), "rt") as fh:
             js = json.load(fh)
         entry = [x for x in js["files"] if os.path.basename(x["file"]) == f][0]
-        skip = OUT_OF_SCOPE.get(f, set())
-        funcs = {fn["name"]: {"lines": 0, "branches": 0, "unexecuted": [], "untaken": []} for fn in entry["functions"] if fn["name"] not in skip}
+        funcs = {fn["name"]: {"lines": 0, "branches": 0, "unexecuted": [], "untaken": []} for fn in entry["functions"] if in_scope(scope, f, fn["name"])}
         for ln in entry["lines"]:
             fn = funcs.get(ln.get("function_name"))
             if fn is None:
